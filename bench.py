@@ -9,8 +9,11 @@ A "step" = one 2-view clip of `--frames` synthetic 720x1280 frames through the w
 tsmotion, sliding SmoothNet windows, canvas, TPS warp + AVERAGE fusion; warp NORMAL -- the defaults of the reference's
 StabStitch-D script, test_online_ssd.py:440-444), inputs resident in HBM, outputs left in HBM.  One clip per rank
 (independent video pairs, seed = rank: no data-path collective); a single all_gather of per-rank records at the end.
-Prints ONE JSON line (see DESIGN.md "Measurement").  At N=1 the line also carries the other BASELINE.json
-configurations (`other_configs`), the CPU oracle baseline with its per-stage split, and benchmark-time parity.
+Prints ONE JSON line (see DESIGN.md "Measurement").  A plain run sets up, warms up, times `--steps` steps and prints the
+headline (`value`, `ms_per_step`).  `--full` adds everything else: the `roofline` block (HIP events around every conv-engine
+launch of the last timed step), and at N=1 the other BASELINE.json configurations (`other_configs`), the CPU oracle baseline
+with its per-stage split, and benchmark-time parity.  `--dump-outputs DIR` writes what the last timed step returned as
+DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -363,7 +366,16 @@ def parse_args(argv=None):
                          'resolutions at 1 / 2 / 4 / 8 GPUs); N = 1 has it under other_configs already')
     ap.add_argument('--stub-step-ms', type=float, default=0.0,
                     help='launcher self-test without GPUs: every step is a sleep of this many ms (backend gloo)')
-    return ap.parse_args(argv)
+    ap.add_argument('--full', action='store_true',
+                    help='also the roofline / per-kernel probe, the other configurations and the CPU baseline with parity '
+                         '(off: the run measures the headline steps only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64, '
+                         '< 64 MB in all; a fixed seeded sample of the frames where they are larger)')
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def free_port():
@@ -412,6 +424,44 @@ def measure(step, sync, warmup, steps, per_step=False):
         sync()
         single.append(time.perf_counter() - t1)
     return dt, out, single
+
+
+DUMP_MAX_BYTES = 60_000_000        # --dump-outputs: all arrays together (headers aside), under the 64 MB the option promises
+DUMP_SAMPLE_SEED = 0
+
+
+def step_outputs(out, views):
+    """The timed step's result as named arrays, as its caller receives them: (frames, Hc, Wc, *meshes) -> {frames, canvas = [Hc, Wc],
+    the meshes of run_two_view / run_three_view}.  The streaming and host paths return (frames, Hc, Wc) only."""
+    meshes = ('mesh1', 'middle', 'mesh3') if views == 3 else ('smooth_mesh1', 'smooth_mesh2')
+    arrays = {'frames': out[0], 'canvas': [int(out[1]), int(out[2])]}
+    arrays.update(zip(meshes, out[3:]))
+    return arrays
+
+
+def dump_outputs(path, arrays):
+    """Write every array as <path>/<name>.npy: float64 stays float64, everything else (fp32 frames, uint8 frames, sizes) becomes
+    float32.  Arrays are written whole, smallest first, while the total stays within DUMP_MAX_BYTES; one that does not fit is
+    replaced by the elements at a fixed set of flat indices (sorted draws of default_rng(DUMP_SAMPLE_SEED), as many as fit), so
+    that two builds run with the same arguments write the same elements.  -> {name: [elements written, elements of the array]}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    tens = {k: torch.as_tensor(v).detach() for k, v in arrays.items()}
+    left = DUMP_MAX_BYTES
+    written = {}
+    for name in sorted(tens, key=lambda k: tens[k].numel()):
+        t = tens[name].reshape(-1)
+        n, size = t.numel(), (8 if t.dtype == torch.float64 else 4)
+        if n * size > left:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, n, size=left // size))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float64 if size == 8 else torch.float32).cpu().numpy()
+        if a.size == n:
+            a = a.reshape(tuple(tens[name].shape))
+        np.save(os.path.join(path, name + '.npy'), a)
+        left -= a.size * size
+        written[name] = [int(a.size), int(n)]
+    return written
 
 
 def other_configs(nets, dev, args):
@@ -860,8 +910,11 @@ def main():
     nets, sds = build_nets(dev, args.weights)
     # configs[3]: rank r stitches its own clip (seed = rank): N distinct video pairs on N GPUs
     hr, lr = synth.make_clip_device(args.frames, args.height, args.width, seed=rank, views=args.views, device=dev)
+    # --full (or --conv-report): HIP events around the conv-engine and HBM-side launches of the last timed step
+    probing = args.full or args.conv_report
     probe = ConvProbe()
-    probe.install()
+    if probing:
+        probe.install()
 
     def step_online(use_graph=True):
         from stabstitch2_amd.online import OnlineStitcher
@@ -884,8 +937,7 @@ def main():
             runner = pipeline.HostClipRunner(nets, dev, args.warp_mode, args.fusion_mode)
 
     def step_u8():
-        fr, hc_, wc_, _, _ = pipeline.run_two_view_u8(u8[0], u8[1], nets, args.warp_mode, args.fusion_mode, device=dev)
-        return fr, hc_, wc_
+        return pipeline.run_two_view_u8(u8[0], u8[1], nets, args.warp_mode, args.fusion_mode, device=dev)
 
     def steps_host(k):
         """k clips through the overlapped upload / compute / download pipeline; -> last (video, Hc, Wc)."""
@@ -901,7 +953,7 @@ def main():
             return step_u8()
         if args.views == 3:       # BASELINE configs[4]: two 2-view passes (v1,v2),(v2,v3) + three-view composition
             return pipeline.run_three_view(hr[0], hr[1], hr[2], lr[0], lr[1], lr[2], nets, args.warp_mode,
-                                           args.fusion_mode)[:3]
+                                           args.fusion_mode)
         return pipeline.run_two_view(hr[0], hr[1], lr[0], lr[1], nets, args.warp_mode, args.fusion_mode)
 
     if runner is not None:
@@ -918,12 +970,16 @@ def main():
         for i in range(args.steps):
             # HIP events around every conv launch of the last timed step (not inside a HIP-graph capture: the streaming
             # mode is probed on an extra eager pass after the timed region)
-            probe.active = (i == args.steps - 1) and not args.online
+            probe.active = probing and (i == args.steps - 1) and not args.online
             out = step()
     probe.active = False
     sync()
     dt = time.perf_counter() - t0
-    if args.online:
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, step_outputs(out, args.views))
+        print('bench.py: wrote %s to %s' % (', '.join('%s (%d of %d values)' % (k, v[0], v[1]) for k, v in dumped.items()),
+                                            args.dump_outputs), file=sys.stderr)
+    if args.online and probing:
         probe.active = True
         step_online(use_graph=False)
         probe.active = False
@@ -974,23 +1030,6 @@ def main():
     tmax = float(allrec[:, 1].max())
     fps = ssdist.aggregate_fps(allrec)
 
-    conv_ms, conv_flop, conv_n, conv_bytes, conv_exec = probe.summary()
-    if args.conv_report:
-        probe.report()
-    executed = conv_exec / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    equivalent = conv_flop / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    # algorithmic HBM bytes per stitched frame: fp32 frames in, fp32 canvas out, weights once
-    io_bytes = args.views * (3 * args.height * args.width + 3 * 360 * 480) * 4 + 3 * hc * wc * 4 + 70.6e6
-    # HBM bytes per conv launch: STATIC, from the committed PMC passes of this same command (FETCH_SIZE / WRITE_SIZE
-    # are profiler counters and cannot be read from inside the process)
-    traffic = None
-    pmc = None
-    try:
-        with open(os.path.join(ROOT, PMC_PROFILE)) as f:
-            pmc = json.load(f)
-        traffic = pmc['conv_family']['hbm_bytes_per_launch']
-    except Exception:
-        pass
     result = {
         'metric': 'stitched frames/sec, %dp %d-view (StabStitch++ inference hot path)' % (args.height, args.views),
         'value': round(fps, 3), 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -1007,41 +1046,59 @@ def main():
                    'frames_per_step': args.frames, 'canvas': [int(hc), int(wc)], 'parallelism': 'streams%d' % world,
                    'published_reference': '28.3 fps on 1x RTX 4090 at 360x480 (README.md:30); different resolution '
                                           'and hardware, not comparable'},
-        'roofline': {'bound': 'mfma', 'kernel': 'conv engine: conv_wino43_kernel / conv_wino_kernel / conv_igemm_kernel / stem_pool_kernel (fp32 MFMA, %d launches/clip)'
-                     % conv_n, 'achieved': round(executed, 3), 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                     'frac': round(executed / PEAK_FP32_MFMA_TFLOPS, 4),
-                     'achieved_is': 'EXECUTED MFMA flop (Winograd F(2x2,3x3) layers count 16/36 of their direct-conv flop, '
-                                    'F(4x4,3x3) layers 36/144; since round 5 layer1 / layer2 / layer3 all run F(4x4,3x3), 18 of the 44 '
-                                    'launches) / summed launch durations (HIP events); direct_conv_equivalent_tflops prices the same '
-                                    'time on direct-convolution flop',
-                     'direct_conv_equivalent_tflops': round(equivalent, 3),
-                     'traffic': traffic, 'traffic_source': 'static: %s (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE passes of this '
-                                                           'command), not measured in this run' % PMC_PROFILE,
-                     'algorithmic_flop_per_launch': round(conv_flop / max(conv_n, 1)),
-                     'executed_flop_per_launch': round(conv_exec / max(conv_n, 1)),
-                     'algorithmic_bytes_per_launch': round(conv_bytes / max(conv_n, 1)),
-                     'avg_launch_us': round(conv_ms * 1e3 / max(conv_n, 1), 2),
-                     'kernel_ms_per_step': round(conv_ms, 3),
-                     # the two kernels of the engine separately (HIP events of the same step; profiles/r06_kernel_stats.txt holds
-                     # the rocprofv3 kernel trace of this same command, profiled and un-profiled clocks stated there)
-                     'per_kernel': {k: {'launches_per_step': v[0], 'avg_launch_us': round(v[1] * 1e3 / max(v[0], 1), 2),
-                                        'ms_per_step': round(v[1], 3),
-                                        'achieved_tflops_executed': round(v[2] / (v[1] * 1e-3) / 1e12, 2) if v[1] > 0 else 0.0,
-                                        'frac': round(v[2] / (v[1] * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) if v[1] > 0 else 0.0,
-                                        'direct_conv_equivalent_tflops': round(v[3] / (v[1] * 1e-3) / 1e12, 2) if v[1] > 0 else 0.0}
-                                    for k, v in probe.by_kernel().items()},
-                     # the HBM-side kernels (K7 / K8 / max-pool / K12-K13), HIP-event time in this run x STATIC
-                     # HBM bytes of the committed PMC passes / 8 TB/s
-                     'secondary': probe.secondary_report(pmc),
-                     # all profiled kernels together: HBM bytes per clip from the committed PMC passes against the compulsory bytes
-                     'path_hbm_traffic': path_traffic(pmc, io_bytes * args.frames),
-                     'path_hbm_frac': round(fps / world * io_bytes / 1e9 / PEAK_HBM_GBS, 5),
-                     # whole path against the MFMA roof: 41.31 GFLOP of dense contraction per 2-view frame
-                     'path_mfma_frac': round(fps / world * 41.31e9 / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4) if args.views == 2 else None,
-                     'path_mfma_frac_is': 'DIRECT-convolution flop of the path (41.31 GFLOP per frame) x frames/s / peak: may exceed 1 -- the '
-                                          'Winograd layers execute 16/36 (F(2x2,3x3)) and 36/144 (F(4x4,3x3)) of their direct flop; `frac` above '
-                                          'is on executed flop'},
     }
+    if probing:
+        conv_ms, conv_flop, conv_n, conv_bytes, conv_exec = probe.summary()
+        if args.conv_report:
+            probe.report()
+        executed = conv_exec / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+        equivalent = conv_flop / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+        # algorithmic HBM bytes per stitched frame: fp32 frames in, fp32 canvas out, weights once
+        io_bytes = args.views * (3 * args.height * args.width + 3 * 360 * 480) * 4 + 3 * hc * wc * 4 + 70.6e6
+        # HBM bytes per conv launch: STATIC, from the committed PMC passes of this same command (FETCH_SIZE / WRITE_SIZE
+        # are profiler counters and cannot be read from inside the process)
+        traffic = None
+        pmc = None
+        try:
+            with open(os.path.join(ROOT, PMC_PROFILE)) as f:
+                pmc = json.load(f)
+            traffic = pmc['conv_family']['hbm_bytes_per_launch']
+        except Exception:
+            pass
+        result['roofline'] = {'bound': 'mfma', 'kernel': 'conv engine: conv_wino43_kernel / conv_wino_kernel / conv_igemm_kernel / stem_pool_kernel (fp32 MFMA, %d launches/clip)'
+                              % conv_n, 'achieved': round(executed, 3), 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                              'frac': round(executed / PEAK_FP32_MFMA_TFLOPS, 4),
+                              'achieved_is': 'EXECUTED MFMA flop (Winograd F(2x2,3x3) layers count 16/36 of their direct-conv flop, '
+                                             'F(4x4,3x3) layers 36/144; since round 5 layer1 / layer2 / layer3 all run F(4x4,3x3), 18 of the 44 '
+                                             'launches) / summed launch durations (HIP events); direct_conv_equivalent_tflops prices the same '
+                                             'time on direct-convolution flop',
+                              'direct_conv_equivalent_tflops': round(equivalent, 3),
+                              'traffic': traffic, 'traffic_source': 'static: %s (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE passes of this '
+                                                                    'command), not measured in this run' % PMC_PROFILE,
+                              'algorithmic_flop_per_launch': round(conv_flop / max(conv_n, 1)),
+                              'executed_flop_per_launch': round(conv_exec / max(conv_n, 1)),
+                              'algorithmic_bytes_per_launch': round(conv_bytes / max(conv_n, 1)),
+                              'avg_launch_us': round(conv_ms * 1e3 / max(conv_n, 1), 2),
+                              'kernel_ms_per_step': round(conv_ms, 3),
+                              # the two kernels of the engine separately (HIP events of the same step; profiles/r06_kernel_stats.txt holds
+                              # the rocprofv3 kernel trace of this same command, profiled and un-profiled clocks stated there)
+                              'per_kernel': {k: {'launches_per_step': v[0], 'avg_launch_us': round(v[1] * 1e3 / max(v[0], 1), 2),
+                                                 'ms_per_step': round(v[1], 3),
+                                                 'achieved_tflops_executed': round(v[2] / (v[1] * 1e-3) / 1e12, 2) if v[1] > 0 else 0.0,
+                                                 'frac': round(v[2] / (v[1] * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) if v[1] > 0 else 0.0,
+                                                 'direct_conv_equivalent_tflops': round(v[3] / (v[1] * 1e-3) / 1e12, 2) if v[1] > 0 else 0.0}
+                                             for k, v in probe.by_kernel().items()},
+                              # the HBM-side kernels (K7 / K8 / max-pool / K12-K13), HIP-event time in this run x STATIC
+                              # HBM bytes of the committed PMC passes / 8 TB/s
+                              'secondary': probe.secondary_report(pmc),
+                              # all profiled kernels together: HBM bytes per clip from the committed PMC passes against the compulsory bytes
+                              'path_hbm_traffic': path_traffic(pmc, io_bytes * args.frames),
+                              'path_hbm_frac': round(fps / world * io_bytes / 1e9 / PEAK_HBM_GBS, 5),
+                              # whole path against the MFMA roof: 41.31 GFLOP of dense contraction per 2-view frame
+                              'path_mfma_frac': round(fps / world * 41.31e9 / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4) if args.views == 2 else None,
+                              'path_mfma_frac_is': 'DIRECT-convolution flop of the path (41.31 GFLOP per frame) x frames/s / peak: may exceed 1 -- the '
+                                                   'Winograd layers execute 16/36 (F(2x2,3x3)) and 36/144 (F(4x4,3x3)) of their direct flop; `frac` above '
+                                                   'is on executed flop'}
     if dist is not None:
         result['ranks'] = dist.get_world_size()
         result['backend'] = (ssdist.collective_backend_version() or 'rccl') if args.backend == 'nccl' else args.backend
@@ -1065,7 +1122,8 @@ def main():
             result['ranks_sharing_a_device'] = clash
     result['host'] = {'placement': host, 'HIP_VISIBLE_DEVICES': vis or None, 'GPU_MAX_HW_QUEUES': os.environ.get('GPU_MAX_HW_QUEUES'),
                       'logical_cpus': os.cpu_count(), 'rccl_version': ssdist.collective_backend_version()}
-    base = world == 1 and args.views == 2 and not args.online and args.io == 'f32' and not args.force_collective and not args.share_device
+    # the remaining configurations and the CPU baseline: --full only, and at N = 1 on the headline configuration
+    base = args.full and world == 1 and args.views == 2 and not args.online and args.io == 'f32' and not args.force_collective and not args.share_device
     if base and not args.no_other_configs:
         result['other_configs'] = other_configs(nets, dev, args)
         for k, v in result['other_configs'].items():          # the reference's fps definition (D2H inside the clock) beside the resident path
@@ -1075,7 +1133,7 @@ def main():
                 v['frac_of_resident_path_steady'] = round(v['fps_steady'] / ref_fps, 3)
     # Flat scalars of the per-kernel table (the driver's record keeps scalars of `roofline` / `config` / `cpu_baseline` only)
     for kname, tag in (('conv_wino43_kernel', 'wino43'), ('conv_wino_kernel', 'wino22'), ('conv_igemm_kernel', 'igemm'),
-                       ('stem_pool_kernel', 'stem')):
+                       ('stem_pool_kernel', 'stem')) if probing else ():
         pk = result['roofline']['per_kernel'].get(kname)
         if pk:
             result['roofline'][tag + '_launches'] = pk['launches_per_step']

@@ -324,6 +324,7 @@ def test_bench_eight_ranks_share_one_gpu():
     import json
     env = dict(os.environ)
     env['HSA_ENABLE_IPC_MODE_LEGACY'] = '0'
+    env.pop('GPU_MAX_HW_QUEUES', None)          # bench.py's own queue budget is asserted below, not the caller's setting
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--backend', 'gloo', '--share-device',
                         '--steps', '2', '--warmup', '1', '--frames', '8', '--no-cpu-baseline', '--no-other-configs', '--also-360'],
                        capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)

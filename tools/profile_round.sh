@@ -11,7 +11,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-other-configs"
+# --full: the per-kernel HIP-event table (roofline.per_kernel) that prof_vs_events.py sets beside the trace
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs"
 CMD="python $R/bench.py $ARGS"
 # round 4: the PMC passes run the DRIVER'S command too (25 clips), so traffic, clocks and the trace come from
 # the same run shape
