@@ -76,15 +76,20 @@ def _scale_to_hr(mesh, img_h, img_w):
     return torch.stack((mesh[..., 0] * img_w / LR_W, mesh[..., 1] * img_h / LR_H), dim=4)
 
 
-def get_stable_sqe(img1_list, img2_list, smooth_mesh1, smooth_mesh2, warp_mode, fusion_mode):
+def get_stable_sqe(img1_list, img2_list, smooth_mesh1, smooth_mesh2, warp_mode, fusion_mode, canvas=None):
     """HR frames lists of [1,3,H,W] (0..255), meshes [1,N,7,9,2] at LR scale.
+    canvas: optional (wmin, wmax, hmin, hmax) in HR pixels rendered on instead of the bbox over all frames (a stream's
+    fixed canvas); the canvas size is truncated the same way.
     -> (list of ndarray [Hc,Wc,3] fp32, Wc int tensor, Hc int tensor)."""
     b, _, img_h, img_w = img2_list[0].shape
     rigid = G.rigid_mesh(b, img_h, img_w)
     nrigid = G.norm_mesh(rigid, img_h, img_w)
     m1 = _scale_to_hr(smooth_mesh1, img_h, img_w)
     m2 = _scale_to_hr(smooth_mesh2, img_h, img_w)
-    wmin, wmax, hmin, hmax = _bbox([m1, m2])
+    if canvas is None:
+        wmin, wmax, hmin, hmax = _bbox([m1, m2])
+    else:
+        wmin, wmax, hmin, hmax = (torch.as_tensor(float(v), dtype=torch.float32) for v in canvas)
     out_w = wmax - wmin
     out_h = hmax - hmin
     size = (int(out_h.int()), int(out_w.int()))

@@ -65,6 +65,20 @@ def _warmup_stream(dev):
     return s
 
 
+_LR_SHAPES = ((1, 3, pipeline.LR_H, pipeline.LR_W), (3, pipeline.LR_H, pipeline.LR_W))
+
+
+def _check_shapes(what, frames, allowed):
+    """Frame-size check of a push: shapes only (host side, no device sync), run before the push changes any state.  A stitcher's
+    splines, footprints and static buffers are built for ITS height and width, and the render wrappers take H and W from the frame
+    they are given: a frame of another size (or a transposed one of the same element count) would render rescaled, wrong geometry."""
+    for f in frames:
+        shp = None if f is None else tuple(f.shape)
+        if shp not in allowed:
+            raise ValueError('%s must be %s, got %s' % (what, ' or '.join(str(list(a)) for a in allowed),
+                                                        None if shp is None else list(shp)))
+
+
 def _spatial_temporal_heads(spatial, temporal, f64, prev_feat, feat, b, tm_out, chain=False):
     """SpatialNet behind its stage-1 trunk (f64 [2b,45,60,128], view 1 first) and TemporalNet's regressor on the cached /
     current features (prev_feat, feat [2b,45,60,128], view-major) -> (offset_1, offset_2_ref, offset_2_tgt); the temporal
@@ -402,8 +416,16 @@ class OnlineStitcher:
         """One frame pair: hr* [1,3,H,W] (0..255), lr* [1,3,360,480] ([-1,1]), device tensors.
         -> list of newly stitched frames (empty for the first 6 pushes, 7 frames on the 7th, then one per push).
         meshes_only: -> None for the first 6 pushes, then (m1, m2) [k,7,9,2] (k = 7 on the 7th push, then 1)."""
+        self._check_push((hr1, hr2), (lr1, lr2))
         with ops.deterministic(self.deterministic):
             return self._push(hr1, hr2, lr1, lr2)
+
+    def _check_push(self, hr, lr):
+        """hr* [1,3,H,W] / [3,H,W] of this stitcher's H x W (meshes_only: None will do), lr* [1,3,360,480] / [3,360,480]."""
+        if self.meshes_only:
+            hr = [f for f in hr if f is not None]
+        _check_shapes('HR frames', hr, ((1, 3, self.h, self.w), (3, self.h, self.w)))
+        _check_shapes('LR frames', lr, _LR_SHAPES)
 
     @torch.no_grad()
     def push_u8(self, img1, img2):
@@ -416,6 +438,7 @@ class OnlineStitcher:
             raise ValueError('push_u8 renders frames: not for meshes_only stitchers')
         if img1.dtype != torch.uint8 or img1.dim() != 3 or img1.shape[-1] != 3 or tuple(img1.shape) != tuple(img2.shape):
             raise ValueError('push_u8 takes two uint8 [H,W,3] frames')
+        _check_shapes('uint8 frames', (img1, img2), ((self.h, self.w, 3),))
         with ops.deterministic(self.deterministic):
             if self.static is not None and self._direct() and type(self)._push_static is OnlineStitcher._push_static:
                 return self._push_static(None, None, None, None, u8=(img1.contiguous(), img2.contiguous()))
@@ -747,6 +770,7 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
         if self.static is not None and self._direct():
             if img1.dtype != torch.uint8 or img1.dim() != 3 or img1.shape[-1] != 3 or tuple(img1.shape) != tuple(img2.shape):
                 raise ValueError('push_u8 takes two uint8 [H,W,3] frames')
+            _check_shapes('uint8 frames', (img1, img2), ((self.h, self.w, 3),))
             with ops.deterministic(self.deterministic):
                 return self._push_pipelined(img1.contiguous(), img2.contiguous(), None, None)
         return OnlineStitcher.push_u8(self, img1, img2)
@@ -1075,6 +1099,7 @@ class MultiOnlineStitcher:
         for f in (frames1, frames2):
             if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[0] != S or f.shape[-1] != 3 or tuple(f.shape) != tuple(frames1.shape):
                 raise ValueError('push_u8 takes two uint8 [%d,H,W,3] tensors' % S)
+        _check_shapes('uint8 frames', (frames1, frames2), ((S, self.h, self.w, 3),))
         with ops.deterministic(self.deterministic):
             if self.static is not None and self._direct() and type(self)._push_static is MultiOnlineStitcher._push_static:
                 return self._push_static(None, None, None, None, u8=(frames1.contiguous(), frames2.contiguous()))
@@ -1090,6 +1115,9 @@ class MultiOnlineStitcher:
         S = self.S
         if lr1.shape[0] != S or lr2.shape[0] != S or (not self.meshes_only and (hr1.shape[0] != S or hr2.shape[0] != S)):
             raise ValueError('expected %d streams per push' % S)          # (meshes_only: hr1 / hr2 are not looked at, None will do)
+        hr = [f for f in (hr1, hr2) if f is not None] if self.meshes_only else (hr1, hr2)
+        _check_shapes('HR frames', hr, ((S, 3, self.h, self.w),))
+        _check_shapes('LR frames', (lr1, lr2), ((S, 3, pipeline.LR_H, pipeline.LR_W),))
         with ops.deterministic(self.deterministic):
             return self._push(hr1, hr2, lr1, lr2)
 
@@ -1382,6 +1410,7 @@ class ThreeViewOnlineStitcher:
         imgs = (img1, img2, img3)
         if any(i.dtype != torch.uint8 or i.dim() != 3 or i.shape[-1] != 3 or tuple(i.shape) != tuple(img1.shape) for i in imgs):
             raise ValueError('push_u8 takes three uint8 [H,W,3] frames')
+        _check_shapes('uint8 frames', imgs, ((self.h, self.w, 3),))
         if self.static is not None and self._direct() and type(self)._push_static is ThreeViewOnlineStitcher._push_static:
             return self._push_static(None, None, None, None, None, None, u8=tuple(i.contiguous() for i in imgs))
         hr, lr = ops.ingest_u8(torch.stack(imgs, 0), pipeline.LR_H, pipeline.LR_W)
@@ -1392,6 +1421,8 @@ class ThreeViewOnlineStitcher:
     def push(self, hr1, hr2, hr3, lr1, lr2, lr3):
         """One frame triple: hr* [1,3,H,W] (0..255), lr* [1,3,360,480] ([-1,1]), device tensors.
         -> list of newly stitched frames (empty for the first 6 pushes, 7 frames on the 7th, then one per push)."""
+        _check_shapes('HR frames', (hr1, hr2, hr3), ((1, 3, self.h, self.w), (3, self.h, self.w)))
+        _check_shapes('LR frames', (lr1, lr2, lr3), _LR_SHAPES)
         if self.static is not None:
             return self._push_static(hr1, hr2, hr3, lr1, lr2, lr3)
         sh = lambda t, c: t.reshape((1,) + tuple(c))
@@ -1516,6 +1547,8 @@ class HostFrameStream:
 
     def _stage(self, frames):
         src = [torch.from_numpy(f) if not torch.is_tensor(f) else f for f in frames]
+        st = self.st
+        _check_shapes('uint8 frames', src, (((st.S,) if hasattr(st, 'S') else ()) + (st.h, st.w, 3),))   # before the upload
         n = self.prefetch + 3
         if self._in is None or tuple(self._in[0][0].shape) != tuple(src[0].shape) or len(self._in[0]) != len(src):
             torch.cuda.synchronize(self.dev)
