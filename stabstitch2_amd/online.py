@@ -20,6 +20,7 @@ captured ONCE into a HIP graph (state lives in static tensors: the rings are shi
 two input copies + one graph launch: the Python / ctypes launch overhead (~1 ms per pair, more than the kernels'
 own time at batch 1) disappears.  `use_graph=False` runs the same code eagerly.
 """
+import contextlib
 import os
 import time
 
@@ -118,88 +119,114 @@ def _heads_b(spatial, temporal, f64, off1, prev_feat, feat, b, tm_out, chain=Fal
     return off_ref, off_tgt
 
 
-class OnlineStitcher:
-    def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 use_graph=True, grow='never', meshes_only=False, deterministic=False):
-        """canvas: optional (wmin, wmax, hmin, hmax) in HR pixels (e.g. the offline bbox).
-        deterministic: every push under the conv engine's geometry-only kernel policy (ops.deterministic): with the offline canvas the
-        stream's frames equal the resident clip's (pipeline.run_two_view(..., deterministic=True)) bit for bit; ~1.6x slower pushes.
-        meshes_only: no canvas, no render -- `push` returns the newly smoothed meshes (m1, m2) [k,7,9,2] (k = 7 on the 7th push,
-        then 1) or None; the building block of ThreeViewOnlineStitcher, which captures the graph itself (use_graph is ignored).
-        grow: 'never' -- the canvas fixed after the first window stays (frames whose mesh leaves it are cropped and COUNTED:
-        `clipped_frames`); 'recapture' -- the canvas grows (and the steady-state graph is captured again) when a mesh comes within
-        half the margin of its edge; `canvas_epoch` counts the growths, `hc` / `wc` / `bbox` change with them."""
-        if grow not in ('never', 'recapture'):
-            raise ValueError("grow must be 'never' or 'recapture'")
-        self.grow = grow
-        self.deterministic = bool(deterministic)
-        self.meshes_only = bool(meshes_only)
-        self.last_meshes = None
-        self.canvas_epoch = 0
-        self.watch_i = self.watch_f = None          # device-side overflow state of the current canvas (ops.canvas_watch)
-        self._watch_totals = [0, 0, -1]             # frames seen / clipped / first clipped frame on EARLIER canvases
-        self._host_watch = self._host_event = None  # grow='recapture': pinned copy of the state, one push behind
-        self._near_handled = 0
-        self.spatial, self.temporal, self.smooth = nets
-        self.dev = next(self.spatial.parameters()).device
-        self.h, self.w = height, width
-        self.margin = margin
-        self.warp_mode, self.fusion_mode = warp_mode, fusion_mode
-        self.bbox = None if canvas is None else torch.tensor(canvas, dtype=torch.float32, device=self.dev)
-        self.hc = self.wc = None
-        self.nrigid = get_norm_mesh(get_rigid_mesh(1, height, width, device=self.dev), height, width).contiguous()
-        self.frames_in = 0
-        self.prev_feat = None            # TemporalNet stage-1 features of the previous frame, both views [2,45,60,128]
-        self.prev_smotion = None         # [2,7,9,2]
-        self.ring_smesh = [[], []]       # last WINDOW spatial meshes per view, each [1,7,9,2]
-        self.ring_tsm = [[], []]
-        self.ring_hr = []                # HR frames waiting for their smoothed mesh (only until the first window)
-        self.use_graph = use_graph
-        self.static = None               # steady-state buffers (inputs, rings, output) once the window is full
-        self.graph = None
-        self.graph_nodes = None          # nodes of the captured steady-state graph (None: not captured / not exposed)
-        self.trunk_pair = None
-        self.trunk_versions = None
+def _check_u8(what, frames, shape):
+    """push_u8's frames: uint8 tensors alike, each of `shape` ([H,W,3], or [S,H,W,3] for S streams); run before any state changes."""
+    if any(f.dtype != torch.uint8 or f.dim() != len(shape) or f.shape[-1] != 3 or tuple(f.shape) != tuple(frames[0].shape)
+           for f in frames):
+        raise ValueError('push_u8 takes %s' % what)
+    _check_shapes('uint8 frames', frames, (shape,))
 
-    def _set_canvas(self):
-        bb = self.bbox.cpu()
-        self.hc = int((bb[3] - bb[2]).int())
-        self.wc = int((bb[1] - bb[0]).int())
-        self.watch_i, self.watch_f = ops.canvas_watch_state(1, self.dev)
-        self._near_handled = 0
-        self._host_event = None
 
-    # ------------------------------------------------------------------ canvas overflow
-    def _guard(self):
+def _canvas_size(bb):
+    """(Hc, Wc) of a canvas (wmin, wmax, hmin, hmax), CPU fp32 [4]."""
+    return int((bb[3] - bb[2]).int()), int((bb[1] - bb[0]).int())
+
+
+@contextlib.contextmanager
+def _kept(state):
+    """The body may advance the state tensors: their values are put back at its end (and whenever it calls the `restore` it is given)."""
+    keep = [t.clone() for t in state]
+
+    def restore():
+        for t, v in zip(state, keep):
+            t.copy_(v)
+    yield restore
+    restore()
+
+
+def _capture(dev, state, warmup, steps, per_push=1):
+    """Capture each of `steps` into a HIP graph.  The eager warm-up runs first, on the shared warm-up stream and on a copy of the state,
+    so that the push being captured is applied exactly once (by the replay that follows); captures do not execute, and the state is
+    the pre-push state afterwards.  -> (graphs, nodes of one push: the first `per_push` graphs; None where not exposed)."""
+    cur = torch.cuda.current_stream(dev)
+    with _kept(state) as restore:
+        side = _warmup_stream(dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            warmup()
+        cur.wait_stream(side)
+        restore()
+        graphs = []
+        for fn in steps:
+            g = _new_graph()
+            with torch.cuda.graph(g):
+                fn()
+            graphs.append(g)
+    nodes = 0
+    for g in graphs[:per_push]:
+        n = _graph_nodes(g)
+        nodes = None if nodes is None or n is None else nodes + n
+    return graphs, nodes
+
+
+class _CanvasWatch:
+    """Overflow state of N fixed canvases (N = S for MultiOnlineStitcher, else 1).  The device rows that ops.canvas_watch updates on
+    every push (wi [N,4] int32: frames seen / clipped / first clipped / near an edge; wf [N,4] fp32: running normalised extents), the
+    totals of the canvases each row had before, and for grow='recapture' a pinned copy of the rows one push behind and the arithmetic
+    that re-fixes a canvas around everything seen on it."""
+
+    def __init__(self, n, margin, dev):
+        self.n, self.margin, self.dev = n, margin, dev
+        self.wi = self.wf = None                       # device rows of the current canvases (None: no canvas yet)
+        self.boxes = None                              # the current canvases (wmin, wmax, hmin, hmax in HR px), CPU fp32 [N,4]
+        self.totals = [[0, 0, -1] for _ in range(n)]  # frames seen / clipped / first clipped frame on EARLIER canvases
+        self.epoch = [0] * n                           # growths per canvas
+        self.near_handled = [0] * n
+        self._host = self._event = None                # grow='recapture': pinned copy of the rows, one push behind
+
+    @property
+    def guard(self):
         """`near` threshold of the watcher in canvas-normalised units: half the margin the canvas was grown by."""
         return max(0.0, float(self.margin)) * 0.5 / (1.0 + 2.0 * max(0.0, float(self.margin))) * 2.0
 
-    def overflow_report(self):
-        """Synchronises.  -> {'frames_seen', 'clipped_frames', 'first_clipped_frame' (stream frame index, -1 = none), 'near_frames'
-        (current canvas), 'canvas_epoch', 'needed_bbox' (wmin, wmax, hmin, hmax in HR px: the current canvas united with every
-        mesh seen on it)}."""
-        seen, clipped, first = self._watch_totals
-        rep = {'frames_seen': seen, 'clipped_frames': clipped, 'first_clipped_frame': first, 'near_frames': 0,
-               'canvas_epoch': self.canvas_epoch, 'needed_bbox': None}
-        if self.watch_i is None:
-            return rep
-        wi = self.watch_i[0].cpu().tolist()
-        if wi[1] > 0 and first < 0:
-            rep['first_clipped_frame'] = seen + wi[2]
-        rep['frames_seen'] = seen + wi[0]
-        rep['clipped_frames'] = clipped + wi[1]
-        rep['near_frames'] = wi[3]
-        rep['needed_bbox'] = tuple(float(x) for x in self._needed_bbox(self.watch_f[0].cpu()))
-        return rep
+    def args(self, s=None):
+        """(guard, watch_i, watch_f) of all rows, or of row s, for the launches that carry the watcher."""
+        if s is None:
+            return self.guard, self.wi, self.wf
+        return self.guard, self.wi[s:s + 1], self.wf[s:s + 1]
 
-    @property
-    def clipped_frames(self):
-        """Frames emitted so far whose mesh reached outside the canvas they were rendered on (synchronises)."""
-        return self.overflow_report()['clipped_frames']
+    def start(self, boxes, state=None):
+        """Watch these canvases (CPU fp32 [N,4]) from now on: fresh rows, or state = (wi, wf) carried over."""
+        self.boxes = boxes
+        self.wi, self.wf = state if state is not None else ops.canvas_watch_state(self.n, self.dev)
+        self.near_handled = [0] * self.n
+        self._event = None
 
-    def _needed_bbox(self, wf):
-        """Running normalised extents [xmin, xmax, ymin, ymax] on the current canvas -> union with the canvas, HR pixels."""
-        bb = self.bbox.cpu()
+    def report(self):
+        """Synchronises.  -> one dict per canvas: {'frames_seen', 'clipped_frames', 'first_clipped_frame' (stream frame index, -1 =
+        none), 'near_frames' (current canvas), 'canvas_epoch', 'needed_bbox' (wmin, wmax, hmin, hmax in HR px: the current canvas
+        united with every mesh seen on it)}."""
+        wi = None if self.wi is None else self.wi.cpu().tolist()
+        wf = None if self.wf is None else self.wf.cpu()
+        reps = []
+        for s in range(self.n):
+            seen, clipped, first = self.totals[s]
+            rep = {'frames_seen': seen, 'clipped_frames': clipped, 'first_clipped_frame': first, 'near_frames': 0,
+                   'canvas_epoch': self.epoch[s], 'needed_bbox': None}
+            if wi is not None:
+                w = wi[s]
+                if w[1] > 0 and first < 0:
+                    rep['first_clipped_frame'] = seen + w[2]
+                rep['frames_seen'] = seen + w[0]
+                rep['clipped_frames'] = clipped + w[1]
+                rep['near_frames'] = w[3]
+                rep['needed_bbox'] = tuple(float(x) for x in self._needed_bbox(s, wf[s]))
+            reps.append(rep)
+        return reps
+
+    def _needed_bbox(self, s, wf):
+        """Running normalised extents [xmin, xmax, ymin, ymax] on canvas s -> union with the canvas, HR pixels."""
+        bb = self.boxes[s]
         ow, oh = float(bb[1] - bb[0]), float(bb[3] - bb[2])
         x0 = float(bb[0]) + (min(float(wf[0]), -1.0) + 1.0) * ow / 2.0
         x1 = float(bb[0]) + (max(float(wf[1]), 1.0) + 1.0) * ow / 2.0
@@ -207,65 +234,191 @@ class OnlineStitcher:
         y1 = float(bb[2]) + (max(float(wf[3]), 1.0) + 1.0) * oh / 2.0
         return x0, x1, y0, y1
 
-    def _regrow(self, wi, wf):
-        """grow='recapture': re-fix the canvas around everything seen so far (+ margin), fresh watcher state, new output buffer,
-        the steady-state graph captured again at the next push."""
-        x0, x1, y0, y1 = self._needed_bbox(wf)
+    def _regrow(self, s, wi, wf):
+        """Re-fix canvas s around everything seen on it (+ margin), fresh row.  -> False when there is nothing to grow by."""
+        x0, x1, y0, y1 = self._needed_bbox(s, wf)
         gw, gh = self.margin * (x1 - x0), self.margin * (y1 - y0)
-        old = [float(v) for v in self.bbox.cpu()]
+        old = [float(v) for v in self.boxes[s]]
         if max(abs(a - b) for a, b in zip(old, (x0 - gw, x1 + gw, y0 - gh, y1 + gh))) < 0.5:
             # nothing to grow by (e.g. margin 0 and a mesh that only touches the edge): keep the canvas, the output buffer and the
             # captured graph -- a recapture costs a sync, an allocation and a capture, and would be asked for again next push
-            self._near_handled = int(wi[3])
+            self.near_handled[s] = int(wi[3])
             return False
-        seen, clipped, first = self._watch_totals
+        seen, clipped, first = self.totals[s]
         if wi[1] > 0 and first < 0:
             first = seen + wi[2]
-        self._watch_totals = [seen + wi[0], clipped + wi[1], first]
-        self.bbox = torch.tensor([x0 - gw, x1 + gw, y0 - gh, y1 + gh], dtype=torch.float32, device=self.dev)
-        self._set_canvas()
-        self.canvas_epoch += 1
-        if self.static is not None:
-            self.static['out'] = torch.empty((3, self.hc, self.wc), device=self.dev)
-        self.graph = None
+        self.totals[s] = [seen + wi[0], clipped + wi[1], first]
+        self.boxes[s] = torch.tensor([x0 - gw, x1 + gw, y0 - gh, y1 + gh], dtype=torch.float32)
+        fi, ff = ops.canvas_watch_state(1, self.dev)
+        self.wi[s].copy_(fi[0])
+        self.wf[s].copy_(ff[0])
+        self.near_handled[s] = 0
+        self.epoch[s] += 1
         return True
 
-    def _poll_growth(self):
-        """Start of a steady-state push (grow='recapture'): look at the watcher state of the push before, copied to pinned memory
-        behind it -- no wait: if the copy has not landed yet the check happens one push later."""
-        if self._host_event is None or not self._host_event.query():
-            return
-        if int(self._host_watch[0][0, 3]) > self._near_handled:
-            # (rare path, synchronises: the device state may be a push ahead of the pinned copy -- take everything seen so far)
-            self._regrow(self.watch_i[0].cpu().tolist(), self.watch_f[0].cpu())
+    def poll(self):
+        """Start of a steady-state push (grow='recapture'): look at the rows of the push before, copied to pinned memory behind it --
+        no wait: if the copy has not landed yet the check happens one push later.  -> the canvases that were re-fixed."""
+        if self._event is None or not self._event.query():
+            return []
+        near = self._host[0][:, 3].tolist()
+        cand = [s for s in range(self.n) if near[s] > self.near_handled[s]]
+        if not cand:
+            return []
+        # (rare path, synchronises: the device rows may be a push ahead of the pinned copy -- take everything seen so far)
+        wi, wf = self.wi.cpu(), self.wf.cpu()
+        grown = [s for s in cand if self._regrow(s, wi[s].tolist(), wf[s])]
+        self._event = None
+        return grown
 
-    def _post_watch_copy(self):
-        if self._host_watch is None:
-            self._host_watch = (torch.empty((1, 4), dtype=torch.int32).pin_memory(), torch.empty((1, 4), dtype=torch.float32).pin_memory())
-        self._host_watch[0].copy_(self.watch_i, non_blocking=True)
-        self._host_watch[1].copy_(self.watch_f, non_blocking=True)
+    def post_copy(self):
+        """End of a steady-state push (grow='recapture'): copy the rows to pinned memory behind it."""
+        if self._host is None:
+            self._host = (torch.empty((self.n, 4), dtype=torch.int32).pin_memory(),
+                          torch.empty((self.n, 4), dtype=torch.float32).pin_memory())
+        self._host[0].copy_(self.wi, non_blocking=True)
+        self._host[1].copy_(self.wf, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.dev))
-        self._host_event = ev
+        self._event = ev
 
-    @torch.no_grad()
-    def _render(self, hr1, hr2, mesh1, mesh2, out=None):
-        """mesh* [1,7,9,2] LR-scale smoothed meshes of ONE frame -> stitched frame [3,Hc,Wc] (written to `out` if given)."""
-        if FUSED_SPLINES:                    # control points + splines in one launch, the watcher inside the footprint launch
-            src4, T4 = ops.stream_splines([mesh1, mesh2], 126, self.bbox, self.nrigid, self.h, self.w)
-            return self._render_solved(hr1, hr2, src4[0], T4[0], out, watch=(self._guard(), self.watch_i, self.watch_f))
-        src4 = ops.stream_normalize_watch([mesh1, mesh2], 126, self.bbox, self.h, self.w, self._guard(), self.watch_i,
-                                          self.watch_f)                                      # [1,2,63,2], watcher updated
-        src = src4[0]
-        T = ops.tps_solve_shared(src, self.nrigid)
-        return self._render_solved(hr1, hr2, src, T, out)
+
+# ------------------------------------------------------------------ steady state (window full, canvas fixed)
+# State tensors of the steady state (fixed addresses: the step is captured into a HIP graph), with a leading S for S streams:
+#   pair_s [2 views][prev, new][126]   spatial motions of the previous and the current pair
+#   pair_t [2 views][zero, new][126]   temporal motions (slot 0 stays zero: tsmotion of a 2-frame batch reads slot 1 only)
+#   ring   [smesh v0, smesh v1, tsm v0, tsm v1][7][126]     the sliding SmoothNet window
+#   prev_feat [2,45,60,128]            TemporalNet stage-1 features of the previous frame, both views
+# pair_t is rewritten in full by every push; the canvas watcher's rows (ops.canvas_watch) count every run of the step and are state too.
+_STATE = ('prev_feat', 'pair_s', 'ring')
+
+
+class _Stitcher:
+    """What the three plain stitchers share: their common fields, the canvas watcher, the twin trunk and its weights check, and the
+    steady-state push -- poll the watcher (grow='recapture'), recapture after reloaded weights, load the push's inputs, run the step
+    eagerly (use_graph=False) or capture it on first use and replay it, copy the watcher rows behind it, hand the frames out (rendered
+    now from the caller's frames with the direct render, else copies of the graph's output).  A subclass provides _load, _step_static
+    and the window-fill push; one with S canvases also _regrown / _render_direct / overflow_report."""
+    _U8_STEADY = True        # push_u8 in the steady state: the resize writes the graph's LR inputs, the render samples the uint8 frames
+
+    def __init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only=False, canvases=1):
+        if grow not in ('never', 'recapture'):
+            raise ValueError("grow must be 'never' or 'recapture'")
+        self.grow = grow
+        self.nets = nets
+        self.spatial, self.temporal, self.smooth = nets
+        self.dev = next(self.spatial.parameters()).device
+        self.h, self.w = height, width
+        self.margin = margin
+        self.warp_mode, self.fusion_mode = warp_mode, fusion_mode
+        self.use_graph = use_graph
+        self.meshes_only = bool(meshes_only)
+        self._direct_render = bool(DIRECT_RENDER and use_graph and fusion_mode == 'AVERAGE' and not self.meshes_only)
+        self.watch = _CanvasWatch(canvases, margin, self.dev)      # overflow of the fixed canvas(es); meshes_only: never started
+        self.static = None               # steady-state buffers (inputs, rings, output) once the window is full
+        self.graph = None
+        self.graph_nodes = None          # nodes of the captured steady-state graph (None: not captured / not exposed)
+        self.trunk_pair = None
+        self.trunk_versions = None
+        self.frames_in = 0
+
+    # ------------------------------------------------------------------ canvas overflow
+    def overflow_report(self):
+        """Synchronises.  -> {'frames_seen', 'clipped_frames', 'first_clipped_frame' (stream frame index, -1 = none), 'near_frames'
+        (current canvas), 'canvas_epoch', 'needed_bbox' (wmin, wmax, hmin, hmax in HR px: the current canvas united with every
+        mesh seen on it)}."""
+        return self.watch.report()[0]
+
+    @property
+    def clipped_frames(self):
+        """Frames emitted so far whose mesh reached outside the canvas they were rendered on (per stream for S streams; synchronises)."""
+        rep = self.overflow_report()
+        return [r['clipped_frames'] for r in rep] if isinstance(rep, list) else rep['clipped_frames']
+
+    @property
+    def canvas_epoch(self):
+        """Growths of the canvas (grow='recapture'; per stream for MultiOnlineStitcher)."""
+        return list(self.watch.epoch) if isinstance(self, MultiOnlineStitcher) else self.watch.epoch[0]
+
+    def _set_canvas(self):
+        """The canvas is fixed at self.bbox: its size, a fresh watcher on it."""
+        bb = self.bbox.cpu()
+        self.hc, self.wc = _canvas_size(bb)
+        self.watch.start(bb[None])
+
+    def _regrown(self, rows):
+        """grow='recapture': the watcher re-fixed the canvas -- new box, new size, a new output buffer (the graph is captured again)."""
+        self.bbox = self.watch.boxes[0].to(self.dev)
+        self.hc, self.wc = _canvas_size(self.watch.boxes[0])
+        if self.static['out'] is not None:
+            self.static['out'] = torch.empty((3, self.hc, self.wc), device=self.dev)
+
+    # ------------------------------------------------------------------ steady state
+    def _versions(self):
+        return tuple(n.weights_version for n in self.nets)
+
+    def _trunk(self):
+        """The twin stage-1 trunk (SpatialNet's and TemporalNet's stage-1 filters stacked: one grouped launch per layer)."""
+        if self.trunk_pair is None:
+            self.trunk_pair = L.pair_trunks(self.spatial._prepared()['s1'], self.temporal._prepared()['s1'])
+            self.trunk_versions = self._versions()
+        return self.trunk_pair
+
+    def _stale_trunk(self):
+        """Was a net reloaded / moved since the twin trunk was stacked (and the graphs captured)?  Both hold the OLD weights (the graphs
+        by address): the caller drops them, to rebuild and recapture instead of silently stitching with stale filters."""
+        return self.trunk_pair is not None and self.trunk_versions != self._versions()
+
+    def _state(self):
+        st = self.static
+        return [st[k] for k in _STATE] + ([] if self.meshes_only else [self.watch.wi, self.watch.wf])
 
     def _direct(self):
-        """Does the steady-state push launch its render itself (DIRECT_RENDER), outside the graph?"""
-        return bool(DIRECT_RENDER and self.use_graph and self.fusion_mode == 'AVERAGE' and not self.meshes_only)
+        """Does the steady-state push launch its AVERAGE render itself, outside the graph, on the caller's frames (DIRECT_RENDER)?
+        Decided when the stitcher is built."""
+        return self._direct_render
 
-    def _render_solved(self, hr1, hr2, src, T, out=None, watch=None):
-        """src [2,63,2] normalised control points on this stream's canvas, T [2,2,66] their splines -> stitched frame.
+    def _u8_steady(self):
+        return self.static is not None and self._direct() and self._U8_STEADY
+
+    def _push_static(self, *frames, u8=None):
+        """One steady-state push: frames = its HR frames then its LR frames, or u8 = its decoded uint8 frames (push_u8)."""
+        if self.grow == 'recapture' and not self.meshes_only:
+            rows = self.watch.poll()
+            if rows:
+                self._regrown(rows)
+                self.graph = None
+        if self._stale_trunk():
+            self.trunk_pair = None
+            self.graph = None
+        self._load(frames, u8)
+        if not self.use_graph:
+            self._step_static()
+        else:
+            if self.graph is None:
+                (self.graph,), self.graph_nodes = _capture(self.dev, self._state(), self._step_static, [self._step_static])
+            self.graph.replay()
+        self.frames_in += 1
+        if self.meshes_only:             # the newest smoothed meshes (m1, m2): copies, the step's own tensors are reused
+            return tuple(m.clone() for m in self.last_meshes)
+        if self.grow == 'recapture':
+            self.watch.post_copy()
+        return self._take(self._deferred_splines(), self.static['out'], u8 or frames[:len(frames) // 2], u8 is not None)
+
+    def _deferred_splines(self):
+        """Direct render: the splines and footprints (src, T, footprint) the step left for the push's render."""
+        return getattr(self, '_deferred', None)
+
+    def _take(self, deferred, out, imgs, u8):
+        """A push's frames: without the direct render copies of the step's output `out`; with it, rendered now from the caller's
+        frames imgs (HR frames, or uint8 frames when u8) and the step's `deferred` splines into new tensors."""
+        if not self._direct():
+            return [[o.clone()] for o in out] if isinstance(out, list) else [out.clone()]
+        return self._render_direct(deferred, imgs, u8)
+
+    def _render_solved(self, imgs, src, T, out=None, watch=None):
+        """src [V,63,2] normalised control points on this canvas, T [V,2,66] their splines -> the stitched frame of the V = 2 | 3 views
+        imgs [1,3,H,W] (written to `out` if given; out=_DEFER: splines and footprint left in self._deferred for the push's render).
         watch = (guard, watch_i [1,4], watch_f [1,4]): the overflow watcher has not seen `src` yet."""
         if watch is not None and not (self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE):
             ops.canvas_watch(src[None], watch[1], watch[2], watch[0])            # no footprint launch to carry it
@@ -277,19 +430,59 @@ class OnlineStitcher:
             if out is _DEFER:
                 self._deferred = (src, T, fp)
                 return None
-            return ops.render_average([hr1, hr2], src, T, self.hc, self.wc, self.warp_mode, out=out, footprint=fp)
-        w = ops.tps_warp_views([hr1, hr2], src, T, self.hc, self.wc, self.warp_mode)
+            return ops.render_average(imgs, src, T, self.hc, self.wc, self.warp_mode, out=out, footprint=fp)
+        w = ops.tps_warp_views(imgs, src, T, self.hc, self.wc, self.warp_mode)        # [V,4,Hc,Wc]
         res = ops.linear_blend(w[0, 0:3], w[1, 0:3], w[0, 3], w[1, 3])
+        if len(imgs) == 3:
+            res = ops.linear_blend(res, w[2, 0:3], ops.mask_union(w[0, 3], w[1, 3]), w[2, 3])
         return res if out is None else out.copy_(res)
 
-    # ------------------------------------------------------------------ steady state (window full, canvas fixed)
-    # State tensors of the steady state (fixed addresses: the step is captured into a HIP graph):
-    #   pair_s [2 views][prev, new][126]   spatial motions of the previous and the current pair
-    #   pair_t [2 views][zero, new][126]   temporal motions (slot 0 stays zero: tsmotion of a 2-frame batch reads slot 1 only)
-    #   ring   [smesh v0, smesh v1, tsm v0, tsm v1][7][126]     the sliding SmoothNet window
-    #   prev_feat [2,45,60,128]            TemporalNet stage-1 features of the previous frame, both views
-    _STATE = ('prev_feat', 'pair_s', 'ring')
+    def _grown(self, bb):
+        """A box (wmin, wmax, hmin, hmax) grown by the margin on every side, on the device."""
+        bb = bb.cpu()
+        gw, gh = self.margin * (bb[1] - bb[0]), self.margin * (bb[3] - bb[2])
+        return torch.stack((bb[0] - gw, bb[1] + gw, bb[2] - gh, bb[3] + gh)).to(self.dev)
 
+    def _render_direct(self, deferred, imgs, u8):
+        """One canvas, two or three views."""
+        src, T, fp = deferred
+        if u8:                           # uint8 frames in, the uint8 video frame out: no fp32 frame planes, no fp32 canvas
+            return [ops.render_average_u8(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp)]
+        shp = (1, 3, self.h, self.w)
+        return [ops.render_average([f.reshape(shp) for f in imgs], src, T, self.hc, self.wc, self.warp_mode, footprint=fp)]
+
+
+class OnlineStitcher(_Stitcher):
+    def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
+                 use_graph=True, grow='never', meshes_only=False, deterministic=False):
+        """canvas: optional (wmin, wmax, hmin, hmax) in HR pixels (e.g. the offline bbox).
+        deterministic: every push under the conv engine's geometry-only kernel policy (ops.deterministic): with the offline canvas the
+        stream's frames equal the resident clip's (pipeline.run_two_view(..., deterministic=True)) bit for bit; ~1.6x slower pushes.
+        meshes_only: no canvas, no render -- `push` returns the newly smoothed meshes (m1, m2) [k,7,9,2] (k = 7 on the 7th push,
+        then 1) or None; the building block of ThreeViewOnlineStitcher, which captures the graph itself (use_graph is ignored).
+        grow: 'never' -- the canvas fixed after the first window stays (frames whose mesh leaves it are cropped and COUNTED:
+        `clipped_frames`); 'recapture' -- the canvas grows (and the steady-state graph is captured again) when a mesh comes within
+        half the margin of its edge; `canvas_epoch` counts the growths, `hc` / `wc` / `bbox` change with them."""
+        _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only)
+        self.deterministic = bool(deterministic)
+        self.last_meshes = None
+        self.bbox = None if canvas is None else torch.tensor(canvas, dtype=torch.float32, device=self.dev)
+        self.hc = self.wc = None
+        self.nrigid = get_norm_mesh(get_rigid_mesh(1, height, width, device=self.dev), height, width).contiguous()
+        self.prev_feat = None            # TemporalNet stage-1 features of the previous frame, both views [2,45,60,128]
+        self.prev_smotion = None         # [2,7,9,2]
+        self.ring_smesh = [[], []]       # last WINDOW spatial meshes per view, each [1,7,9,2]
+        self.ring_tsm = [[], []]
+        self.ring_hr = []                # HR frames waiting for their smoothed mesh (only until the first window)
+
+    @torch.no_grad()
+    def _render(self, hr1, hr2, mesh1, mesh2, out=None):
+        """mesh* [1,7,9,2] LR-scale smoothed meshes of ONE frame -> stitched frame [3,Hc,Wc] (written to `out` if given).  Control
+        points + splines in one launch, the watcher inside the footprint launch."""
+        src4, T4 = ops.stream_splines([mesh1, mesh2], 126, self.bbox, self.nrigid, self.h, self.w)
+        return self._render_solved([hr1, hr2], src4[0], T4[0], out, watch=self.watch.args())
+
+    # ------------------------------------------------------------------ steady state (window full, canvas fixed)
     def _init_static(self):
         d = self.dev
         e = 126
@@ -298,12 +491,24 @@ class OnlineStitcher:
         ring = torch.stack([torch.cat(r, 0).reshape(WINDOW, e) for r in (self.ring_smesh[0], self.ring_smesh[1],
                                                                           self.ring_tsm[0], self.ring_tsm[1])], 0).contiguous()
         lr = torch.empty((2, 1, 3, pipeline.LR_H, pipeline.LR_W), device=d)       # both views back to back: one layout launch per push
-        st = {'hr1': torch.empty((1, 3, self.h, self.w), device=d), 'hr2': torch.empty((1, 3, self.h, self.w), device=d),
-              'lr1': lr[0], 'lr2': lr[1],
-              'prev_feat': self.prev_feat.clone(), 'pair_s': pair_s, 'pair_t': torch.zeros((2, 2, e), device=d),
-              'ring': ring, 'ts_out': torch.empty((2, 4, e), device=d),
-              'out': None if self.meshes_only else torch.empty((3, self.hc, self.wc), device=d)}
-        self.static = st
+        # frame copies and an output canvas only where the graph renders (meshes_only: no render; direct: the push renders)
+        inside = not self.meshes_only and not self._direct()
+        hr = (lambda: torch.empty((1, 3, self.h, self.w), device=d)) if inside else (lambda: None)
+        self.static = {'hr1': hr(), 'hr2': hr(), 'lr1': lr[0], 'lr2': lr[1],
+                       'prev_feat': self.prev_feat.clone(), 'pair_s': pair_s, 'pair_t': torch.zeros((2, 2, e), device=d),
+                       'ring': ring, 'ts_out': torch.empty((2, 4, e), device=d),
+                       'out': torch.empty((3, self.hc, self.wc), device=d) if inside else None}
+
+    def _load(self, frames, u8):
+        st = self.static
+        if u8 is not None:                   # decoded uint8 frames (push_u8): the cv2-exact resize writes the graph's LR buffers itself
+            ops.ingest_u8(u8[0][None], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr1'])
+            ops.ingest_u8(u8[1][None], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr2'])
+            return
+        hr1, hr2, lr1, lr2 = frames
+        if not self.meshes_only and not self._direct():  # (meshes_only: the frames are not looked at, None will do; direct: rendered in place)
+            st['hr1'].copy_(hr1.reshape(st['hr1'].shape)); st['hr2'].copy_(hr2.reshape(st['hr2'].shape))
+        st['lr1'].copy_(lr1.reshape(st['lr1'].shape)); st['lr2'].copy_(lr2.reshape(st['lr2'].shape))
 
     def _step_static(self):
         """One steady-state push on the static buffers (capturable: no host sync, no data-dependent shapes; every result
@@ -316,10 +521,7 @@ class OnlineStitcher:
         """First half of a steady-state push -- it touches NO stream state: both nets' stage-1 trunks on the two LR frames (one
         grouped launch per layer: SpatialNet and TemporalNet read the same frames through trunks of identical architecture), then
         SpatialNet's stage-2 trunk, contextual correlation and regressNet1 -> (f2 [2(net),2(view),45,60,128], offset_1 [1,8])."""
-        if self.trunk_pair is None:
-            self.trunk_pair = L.pair_trunks(self.spatial._prepared()['s1'], self.temporal._prepared()['s1'])
-            self.trunk_versions = self._versions()
-        f2 = L.run_stage1_pair([lr1, lr2], self.trunk_pair)
+        f2 = L.run_stage1_pair([lr1, lr2], self._trunk())
         if not L.QUAD:
             return f2, None
         return f2, _heads_a(self.spatial, f2[0], 1)
@@ -352,65 +554,6 @@ class OnlineStitcher:
             return
         self._render(hr1, hr2, m1[-1:], m2[-1:], out=out)
 
-    def _versions(self):
-        return (self.spatial.weights_version, self.temporal.weights_version, self.smooth.weights_version)
-
-    def _push_static(self, hr1, hr2, lr1, lr2, u8=None):
-        st = self.static
-        if self.grow == 'recapture' and not self.meshes_only:
-            self._poll_growth()
-        if self.trunk_pair is not None and self.trunk_versions != self._versions():
-            # a net was reloaded / moved since the twin trunk was stacked and the graph captured: both hold the OLD
-            # weights (the graph by address); rebuild and recapture instead of silently stitching with stale filters
-            self.trunk_pair = None
-            self.graph = None
-        direct = self._direct()
-        if u8 is not None:                   # decoded uint8 frames (push_u8): the cv2-exact resize writes the graph's LR buffers itself
-            ops.ingest_u8(u8[0][None], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr1'])
-            ops.ingest_u8(u8[1][None], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr2'])
-        else:
-            if not self.meshes_only and not direct:  # (meshes_only: the frames are not looked at, None will do; direct: rendered in place)
-                st['hr1'].copy_(hr1.reshape(st['hr1'].shape)); st['hr2'].copy_(hr2.reshape(st['hr2'].shape))
-            st['lr1'].copy_(lr1.reshape(st['lr1'].shape)); st['lr2'].copy_(lr2.reshape(st['lr2'].shape))
-        if not self.use_graph:
-            self._step_static()
-        elif self.graph is None:
-            # capture: the eager warm-up runs on a copy of the state so that this push is applied exactly once
-            keep = {k: v.clone() for k, v in st.items() if k in self._STATE}
-            # (the watcher counts every run of the step; meshes_only has no canvas and no watcher)
-            keep_w = None if self.meshes_only else (self.watch_i.clone(), self.watch_f.clone())
-            side = _warmup_stream(self.dev)
-            side.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(side):
-                self._step_static()
-            torch.cuda.current_stream(self.dev).wait_stream(side)
-            for k, v in keep.items():
-                st[k].copy_(v)
-            if keep_w is not None:
-                self.watch_i.copy_(keep_w[0]); self.watch_f.copy_(keep_w[1])
-            g = _new_graph()
-            with torch.cuda.graph(g):
-                self._step_static()
-            self.graph = g
-            self.graph_nodes = _graph_nodes(g)
-            for k, v in keep.items():          # capture does not execute: state is still the pre-push state
-                st[k].copy_(v)
-            self.graph.replay()
-        else:
-            self.graph.replay()
-        self.frames_in += 1
-        if self.meshes_only:             # the newest smoothed meshes (m1, m2) [1,7,9,2]: copies, the step's own tensors are reused
-            return tuple(m.clone() for m in self.last_meshes)
-        if self.grow == 'recapture':
-            self._post_watch_copy()
-        if direct:                       # the graph left splines and footprints; the render reads the caller's frames, writes a new tensor
-            src, T, fp = self._deferred
-            if u8 is not None:               # uint8 frames in, the uint8 video frame out: no fp32 frame planes, no fp32 canvas
-                return [ops.render_average_u8([u8[0], u8[1]], src, T, self.hc, self.wc, self.warp_mode, footprint=fp)]
-            return [ops.render_average([hr1.reshape(st['hr1'].shape), hr2.reshape(st['hr2'].shape)], src, T, self.hc, self.wc,
-                                       self.warp_mode, footprint=fp)]
-        return [st['out'].clone()]
-
     @torch.no_grad()
     def push(self, hr1, hr2, lr1, lr2):
         """One frame pair: hr* [1,3,H,W] (0..255), lr* [1,3,360,480] ([-1,1]), device tensors.
@@ -433,15 +576,15 @@ class OnlineStitcher:
         loop, test_online_tra.py:252-278) -> list of stitched VIDEO frames uint8 [Hc,Wc,3] (`.astype(np.uint8)` of the fused values,
         :413), empty for the first 6 pushes, 7 frames on the 7th, then one per push.  Byte for byte ops.ingest_u8 -> push ->
         ops.canvas_to_u8; in the steady state (DIRECT_RENDER, fusion AVERAGE) the cv2-exact resize writes the graph's LR inputs and
-        the render samples the uint8 frames and writes the uint8 frame itself: no fp32 frame planes, no fp32 canvas."""
+        the render samples the uint8 frames and writes the uint8 frame itself: no fp32 frame planes, no fp32 canvas.
+        PipelinedOnlineStitcher: the frames of the PREVIOUS push come back, `flush_u8()` for the last; a stream is fed through
+        push_u8 or through push, not both."""
         if self.meshes_only:
             raise ValueError('push_u8 renders frames: not for meshes_only stitchers')
-        if img1.dtype != torch.uint8 or img1.dim() != 3 or img1.shape[-1] != 3 or tuple(img1.shape) != tuple(img2.shape):
-            raise ValueError('push_u8 takes two uint8 [H,W,3] frames')
-        _check_shapes('uint8 frames', (img1, img2), ((self.h, self.w, 3),))
+        _check_u8('two uint8 [H,W,3] frames', (img1, img2), (self.h, self.w, 3))
         with ops.deterministic(self.deterministic):
-            if self.static is not None and self._direct() and type(self)._push_static is OnlineStitcher._push_static:
-                return self._push_static(None, None, None, None, u8=(img1.contiguous(), img2.contiguous()))
+            if self._u8_steady():
+                return self._push_static(u8=(img1.contiguous(), img2.contiguous()))
             hr, lr = ops.ingest_u8(torch.stack((img1, img2), 0), pipeline.LR_H, pipeline.LR_W)
             frames = self._push(hr[0:1], hr[1:2], lr[0:1], lr[1:2])
             return [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
@@ -490,9 +633,7 @@ class OnlineStitcher:
             return self.last_meshes
         if self.hc is None:                                                        # first window: fix the canvas, emit 7
             if self.bbox is None:
-                bb = ops.mesh_bbox([m1, m2], self.h, self.w).cpu()
-                gw, gh = self.margin * (bb[1] - bb[0]), self.margin * (bb[3] - bb[2])
-                self.bbox = torch.stack((bb[0] - gw, bb[1] + gw, bb[2] - gh, bb[3] + gh)).to(self.dev)
+                self.bbox = self._grown(ops.mesh_bbox([m1, m2], self.h, self.w))
             self._set_canvas()
             frames = [self._render(h1, h2, m1[i:i + 1], m2[i:i + 1]) for i, (h1, h2) in enumerate(self.ring_hr)]
             self.ring_hr = []
@@ -503,7 +644,8 @@ class OnlineStitcher:
 
 # Steady-state AVERAGE render OUTSIDE the captured graph, on the caller's own HR frames and into a fresh tensor: the graph ends with the
 # splines / footprints, the push saves the copies of the HR frames into static buffers and the clone of the static canvas (720p, three
-# views: 66 + 50 MB of HBM traffic, ~35 us of a 1.1 ms push).  Same kernel, same operands: frames bit-identical.
+# views: 66 + 50 MB of HBM traffic, ~35 us of a 1.1 ms push).  Same kernel, same operands: frames bit-identical.  Read when a stitcher
+# is constructed.
 DIRECT_RENDER = os.environ.get('SS_DIRECT_RENDER', '1') != '0'
 _DEFER = object()                      # `out=_DEFER`: compute splines and footprints, leave the render launch to the push
 FUSED_SPLINES = os.environ.get('SS_FUSED_SPLINES', '1') != '0'   # ThreeViewOnlineStitcher: composition + splines in one launch
@@ -521,42 +663,29 @@ class _TwoInFlight:
     HIP graph per buffer parity; hand-over buffers are double-buffered, events order the halves.  Per frame the launches and their
     operands are the plain stitcher's: results are bit-identical.  What changes is WHEN a result is handed out: `push` returns the
     frames of the PREVIOUS push (valid on the caller's stream), `flush()` the last ones.
-    A subclass provides _pipe_alloc / _pipe_load / _run_a / _run_b / _pipe_take / _pipe_state / _pipe_empty."""
+    A subclass provides _pipe_alloc / _pipe_load / _run_a / _run_b (and _pipe_empty for S streams)."""
 
     def _pipe_init(self):
+        if not L.QUAD:
+            raise ValueError('%s needs the shared regressor launches (SS_QUAD_REGRESSOR=1)' % type(self).__name__)
         self.pipe = None
         self._pending = None             # (event behind it, result) of the newest enqueued push
         self._t = 0
 
     def _capture_pipe(self):
         """Warm both halves up eagerly on a copy of the state (parity 0 holds the current push's inputs), then capture each half for
-        each buffer parity.  Captures do not execute: the state is the pre-push state afterwards."""
+        each buffer parity."""
         torch.cuda.synchronize(self.dev)
-        state = self._pipe_state()
-        keep = [t.clone() for t in state]
-        side = _warmup_stream(self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):
-            self._run_a(0)
-            self._run_b(0)
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        for t, v in zip(state, keep):
-            t.copy_(v)
-        nodes = 0
-        for p in (0, 1):
-            for key, fn in (('ga', self._run_a), ('gb', self._run_b)):
-                g = _new_graph()
-                with torch.cuda.graph(g):
-                    fn(p)
-                self.pipe[key][p] = g
-                if key == 'gb':              # (direct render: the second half left this parity's splines and footprints)
-                    self.pipe.setdefault('deferred', [None, None])[p] = self._pipe_deferred()
-                if p == 0:
-                    n = _graph_nodes(g)
-                    nodes = None if nodes is None or n is None else nodes + n
-        self.graph_nodes = nodes             # nodes of one push (both halves)
-        for t, v in zip(state, keep):
-            t.copy_(v)
+        P = self.pipe
+        P['deferred'] = [None, None]
+
+        def half_b(p):
+            self._run_b(p)
+            P['deferred'][p] = self._deferred_splines()    # (direct render: the second half left this parity's splines and footprints)
+        steps = [lambda p=p, fn=fn: fn(p) for p in (0, 1) for fn in (self._run_a, half_b)]
+        graphs, self.graph_nodes = _capture(self.dev, self._state(), lambda: (self._run_a(0), self._run_b(0)), steps,
+                                            per_push=2)    # nodes of one push (both halves)
+        P['ga'], P['gb'] = graphs[0::2], graphs[1::2]
         torch.cuda.synchronize(self.dev)
 
     def _enqueue(self, p, sa, sb, load=None):
@@ -590,40 +719,41 @@ class _TwoInFlight:
         0.89 ms three-view push into 1.3 - 4 ms (LAB_NOTES R6.5; priorities do not help).  The graphs replay on any stream, so: make
         PIPE_STREAM_CANDIDATES streams, replay the captured halves with the push's own event pattern on every pair, keep the fastest
         pair, restore the state the replays advanced.  ~0.1 s, once."""
-        state = self._pipe_state()
-        keep = [t.clone() for t in state]
         cands = [torch.cuda.Stream(self.dev) for _ in range(PIPE_STREAM_CANDIDATES)]
         cur = torch.cuda.current_stream(self.dev)
         best, self.stream_probe_ms = None, []
-        for i, sa in enumerate(cands):
-            for sb in cands[i + 1:]:
-                ms = None
-                for pushes in (2, PIPE_PROBE_PUSHES):        # the first pass pages the graphs onto the streams
-                    self.pipe['eB'] = [None, None]
-                    torch.cuda.synchronize(self.dev)
-                    t0 = time.perf_counter()
-                    prev = None
-                    for t in range(pushes):
-                        eb = self._enqueue(t & 1, sa, sb)
-                        if prev is not None:
-                            cur.wait_event(prev)
-                        prev = eb
-                    torch.cuda.synchronize(self.dev)
-                    ms = (time.perf_counter() - t0) / pushes * 1e3
-                self.stream_probe_ms.append(round(ms, 4))
-                if best is None or ms < best[0]:
-                    best = (ms, sa, sb)
-        self.pipe['eB'] = [None, None]
-        for t, v in zip(state, keep):
-            t.copy_(v)
+        with _kept(self._state()):
+            for i, sa in enumerate(cands):
+                for sb in cands[i + 1:]:
+                    ms = None
+                    for pushes in (2, PIPE_PROBE_PUSHES):        # the first pass pages the graphs onto the streams
+                        self.pipe['eB'] = [None, None]
+                        torch.cuda.synchronize(self.dev)
+                        t0 = time.perf_counter()
+                        prev = None
+                        for t in range(pushes):
+                            eb = self._enqueue(t & 1, sa, sb)
+                            if prev is not None:
+                                cur.wait_event(prev)
+                            prev = eb
+                        torch.cuda.synchronize(self.dev)
+                        ms = (time.perf_counter() - t0) / pushes * 1e3
+                    self.stream_probe_ms.append(round(ms, 4))
+                    if best is None or ms < best[0]:
+                        best = (ms, sa, sb)
+            self.pipe['eB'] = [None, None]
         torch.cuda.synchronize(self.dev)
         self.pipe['sa'], self.pipe['sb'] = best[1], best[2]
+
+    def _push_static(self, *frames, u8=None):
+        # (push_u8: the uint8 frames take the HR frames' place, there are no LR frames)
+        return self._push_pipelined(*(frames if u8 is None else u8 + (None,) * len(u8)))
 
     def _push_pipelined(self, *inputs):
         if self.pipe is None:
             self.pipe = dict(self._pipe_alloc(), sa=None, sb=None, ga=[None, None], gb=[None, None], eB=[None, None])
-        if self.trunk_pair is not None and self.trunk_versions != self._versions():
-            # a net was reloaded / moved: the twin trunk and ALL four graphs hold the old weights by address -- drain, recapture
+        if self._stale_trunk():
+            # the twin trunk and ALL four graphs hold the old weights by address -- drain, recapture
             torch.cuda.synchronize(self.dev)
             self.trunk_pair = None
             self.pipe['ga'] = [None, None]
@@ -639,7 +769,8 @@ class _TwoInFlight:
         sa, sb = P['sa'], P['sb']
         eb = self._enqueue(p, sa, sb, lambda: self._pipe_load(p, sa, sb, *inputs))
         with torch.cuda.stream(sb):
-            result = self._pipe_take(p, *inputs)
+            imgs = inputs[:len(inputs) // 2]             # the HR frames (push_u8: the uint8 frames)
+            result = self._take(P['deferred'][p], P['out'][p], imgs, imgs[0].dtype == torch.uint8)
             eb = torch.cuda.Event()
             eb.record(sb)
         P['eB'][p] = eb
@@ -648,8 +779,8 @@ class _TwoInFlight:
         self.frames_in += 1
         return self._hand_out(prev)
 
-    def _pipe_deferred(self):
-        return getattr(self, '_deferred', None)
+    def _pipe_empty(self):
+        return []
 
     def _hand_out(self, item):
         if item is None:
@@ -699,8 +830,6 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
     def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE', deterministic=False):
         OnlineStitcher.__init__(self, nets, height, width, canvas, margin, warp_mode, fusion_mode, use_graph=True, grow='never',
                                 meshes_only=False, deterministic=deterministic)
-        if not L.QUAD:
-            raise ValueError('PipelinedOnlineStitcher needs the shared regressor launches (SS_QUAD_REGRESSOR=1)')
         self._pipe_init()
 
     def _pipe_alloc(self):
@@ -710,12 +839,6 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
         return {'lr': two(2, 1, 3, pipeline.LR_H, pipeline.LR_W), 'hr1': hr(), 'hr2': hr(),
                 'f2': two(2, 2, pipeline.LR_H // 8, pipeline.LR_W // 8, 128), 'off1': two(1, 8),
                 'out': [None, None] if self._direct() else two(3, self.hc, self.wc)}
-
-    def _pipe_state(self):
-        return [self.static[k] for k in self._STATE] + [self.watch_i, self.watch_f]
-
-    def _pipe_empty(self):
-        return []
 
     def _pipe_load(self, p, sa, sb, hr1, hr2, lr1, lr2):
         P = self.pipe
@@ -730,7 +853,7 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
         with torch.cuda.stream(sa):
             P['lr'][p][0].copy_(lr1.reshape(P['lr'][p][0].shape))
             P['lr'][p][1].copy_(lr2.reshape(P['lr'][p][1].shape))
-        if not self._direct():               # (direct render: the second stream's render reads the caller's frames)
+        if not self._direct():                  # (direct render: the second stream's render reads the caller's frames)
             with torch.cuda.stream(sb):
                 P['hr1'][p].copy_(hr1.reshape(P['hr1'][p].shape))
                 P['hr2'][p].copy_(hr2.reshape(P['hr2'][p].shape))
@@ -749,34 +872,8 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
         P = self.pipe
         self._stage_b(P['f2'][p], P['off1'][p], P['hr1'][p], P['hr2'][p], _DEFER if self._direct() else P['out'][p])
 
-    def _pipe_take(self, p, hr1, hr2, lr1, lr2):
-        P = self.pipe
-        if self._direct():
-            src, T, fp = P['deferred'][p]
-            if hr1.dtype == torch.uint8:     # push_u8: the uint8 video frame straight from the uint8 frames
-                return [ops.render_average_u8([hr1, hr2], src, T, self.hc, self.wc, self.warp_mode, footprint=fp)]
-            shp = (1, 3, self.h, self.w)
-            return [ops.render_average([hr1.reshape(shp), hr2.reshape(shp)], src, T, self.hc, self.wc,
-                                       self.warp_mode, footprint=fp)]
-        return [P['out'][p].clone()]
 
-    def _push_static(self, hr1, hr2, lr1, lr2):
-        return self._push_pipelined(hr1, hr2, lr1, lr2)
-
-    @torch.no_grad()
-    def push_u8(self, img1, img2):
-        """OnlineStitcher.push_u8 with two pushes in flight: the frames of the PREVIOUS push come back (uint8 [Hc,Wc,3]); `flush_u8()`
-        for the last.  A stream is fed through push_u8 or through push, not both."""
-        if self.static is not None and self._direct():
-            if img1.dtype != torch.uint8 or img1.dim() != 3 or img1.shape[-1] != 3 or tuple(img1.shape) != tuple(img2.shape):
-                raise ValueError('push_u8 takes two uint8 [H,W,3] frames')
-            _check_shapes('uint8 frames', (img1, img2), ((self.h, self.w, 3),))
-            with ops.deterministic(self.deterministic):
-                return self._push_pipelined(img1.contiguous(), img2.contiguous(), None, None)
-        return OnlineStitcher.push_u8(self, img1, img2)
-
-
-class MultiOnlineStitcher:
+class MultiOnlineStitcher(_Stitcher):
     """S independent live video pairs advancing one frame per push as ONE batch (the sharding unit of the
     path -- independent streams -- inside one GPU).  A single stream at batch 1 is launch-bound (~150 small launches per
     pushed pair); S streams run the same launches on S-fold batches, so the aggregate frame rate grows almost linearly until
@@ -787,11 +884,11 @@ class MultiOnlineStitcher:
         st = MultiOnlineStitcher(nets, 720, 1280, streams=8)
         frames = st.push(hr1, hr2, lr1, lr2)      # hr* [S,3,H,W], lr* [S,3,360,480] -> S lists of new frames [3,Hc_s,Wc_s]
 
-    The first WINDOW pushes fill every stream's window through S single-stream stitchers (eager); from then on the step runs
-    on static buffers with a leading S and is captured into one HIP graph.  Results equal S single-stream stitchers up to the
-    conv engine's launch-size-dependent kernel choice (Winograd / implicit GEMM / split-K are picked per launch size, so a
-    batch of S sums in another order than S batches of one: motions differ by ~1e-5 px); within a batch every stream's result
-    is independent of its neighbours bit for bit (tests/test_gpu_round4.py)."""
+    The first WINDOW pushes fill every stream's window through S single-stream stitchers (eager; they hold the streams' canvases
+    afterwards); from then on the step runs on static buffers with a leading S and is captured into one HIP graph.  Results equal S
+    single-stream stitchers up to the conv engine's launch-size-dependent kernel choice (Winograd / implicit GEMM / split-K are picked
+    per launch size, so a batch of S sums in another order than S batches of one: motions differ by ~1e-5 px); within a batch every
+    stream's result is independent of its neighbours bit for bit (tests/test_gpu_round4.py)."""
 
     def __init__(self, nets, height, width, streams, canvases=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
                  use_graph=True, grow='never', meshes_only=False, deterministic=False, chain=False):
@@ -800,9 +897,8 @@ class MultiOnlineStitcher:
         meshes_only: no canvases, no render -- `push` returns the S streams' newly smoothed meshes (m1, m2) [S,k,7,9,2] (k = 7 on the
         7th push, then 1) or None; ThreeViewOnlineStitcher runs its two pair chains as such a batch of two and captures the graph
         itself (use_graph is ignored)."""
-        if grow not in ('never', 'recapture'):
-            raise ValueError("grow must be 'never' or 'recapture'")
-        self.grow = grow
+        _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only,
+                           canvases=max(1, int(streams)))
         self.deterministic = bool(deterministic)      # geometry-only kernel policy: S batched streams == S single streams, bit for bit
         # chain: the S pairs are the neighbours of a chain of S + 1 views (pair s = views s, s + 1: ThreeViewOnlineStitcher's two
         # chains).  The steady-state step then takes the S + 1 LR frames once (static['lrc'] [S+1,3,360,480]) and every inner view
@@ -810,38 +906,20 @@ class MultiOnlineStitcher:
         self.chain = bool(chain)
         if self.chain and not meshes_only:
             raise ValueError('chain=True needs meshes_only=True')
-        self.meshes_only = bool(meshes_only)
         self.last_meshes = None
-        self._host_watch = self._host_event = None
-        self.nets = nets
-        self.spatial, self.temporal, self.smooth = nets
-        self.dev = next(self.spatial.parameters()).device
-        self.h, self.w, self.S = height, width, int(streams)
+        self.S = int(streams)
         if self.S < 1:
             raise ValueError('streams must be >= 1')
         if canvases is not None and len(canvases) != self.S:
             raise ValueError('one canvas per stream')
-        self.warp_mode, self.fusion_mode = warp_mode, fusion_mode
         self.single = [OnlineStitcher(nets, height, width, None if canvases is None else canvases[s], margin, warp_mode,
                                       fusion_mode, use_graph=False, meshes_only=meshes_only, deterministic=deterministic)
-                       for s in range(self.S)]                   # (growth is handled here, batched)
-        self.use_graph = use_graph
-        self.static = None
-        self.graph = None
-        self.graph_nodes = None
-        self.trunk_pair = None
-        self.trunk_versions = None
-        self.frames_in = 0
+                       for s in range(self.S)]                   # window fill; then the streams' canvases (watched and grown here)
 
     @property
     def canvas_sizes(self):
         """[(Hc, Wc)] per stream (None before the first window is complete)."""
         return [(s.hc, s.wc) for s in self.single]
-
-    def _versions(self):
-        return (self.spatial.weights_version, self.temporal.weights_version, self.smooth.weights_version)
-
-    _STATE = ('prev_feat', 'pair_s', 'ring')
 
     def _init_static(self):
         """Batched steady-state buffers from the S single-stream states (each has just completed its first window):
@@ -850,7 +928,8 @@ class MultiOnlineStitcher:
         d, S, e = self.dev, self.S, 126
         one = [s.static for s in self.single]
         lr = torch.empty((2, S, 3, pipeline.LR_H, pipeline.LR_W), device=d)       # both views back to back: one layout launch per push
-        hr = None if self.meshes_only else torch.empty((2, S, 3, self.h, self.w), device=d)
+        # (copies of the frames only where the graph renders: meshes_only has no render, the direct render reads the caller's frames)
+        hr = None if self.meshes_only or self._direct() else torch.empty((2, S, 3, self.h, self.w), device=d)
         st = {'hr1': None if hr is None else hr[0], 'hr2': None if hr is None else hr[1],
               'lr1': lr[0], 'lr2': lr[1],
               'lrc': torch.empty((S + 1, 3, pipeline.LR_H, pipeline.LR_W), device=d) if self.chain else None,
@@ -865,11 +944,13 @@ class MultiOnlineStitcher:
         self.static = st
         if not self.meshes_only:
             st['bboxes'] = torch.stack([s.bbox for s in self.single], 0).contiguous()        # [S,4] the streams' fixed canvases
-            st['watch_i'] = torch.cat([s.watch_i for s in self.single], 0).contiguous()       # [S,4] overflow state (ops.canvas_watch)
-            st['watch_f'] = torch.cat([s.watch_f for s in self.single], 0).contiguous()
+            # the streams' watcher rows (their first windows are counted) go on as rows of one [S,4] state (ops.canvas_watch)
+            self.watch.start(st['bboxes'].cpu(), (torch.cat([s.watch.wi for s in self.single], 0).contiguous(),
+                                                  torch.cat([s.watch.wf for s in self.single], 0).contiguous()))
             self._alloc_outputs()
-        for s in self.single:                     # the per-stream buffers are not needed any more (bbox / canvas stay)
+        for s in self.single:                     # the per-stream buffers and watchers are not needed any more (bbox / canvas stay)
             s.static = None
+            s.watch = None
 
     def _alloc_outputs(self):
         st, S, d = self.static, self.S, self.dev
@@ -883,81 +964,48 @@ class MultiOnlineStitcher:
     # ------------------------------------------------------------------ canvas overflow (per stream)
     def overflow_report(self):
         """Synchronises.  -> one dict per stream (OnlineStitcher.overflow_report)."""
-        if self.static is None or self.meshes_only:          # (meshes_only: no canvases, nothing to overflow -- the empty reports)
-            return [one.overflow_report() for one in self.single]
-        wi, wf = self.static['watch_i'].cpu(), self.static['watch_f'].cpu()
-        reps = []
-        for s, one in enumerate(self.single):
-            seen, clipped, first = one._watch_totals
-            w = wi[s].tolist()
-            if w[1] > 0 and first < 0:
-                first = seen + w[2]
-            reps.append({'frames_seen': seen + w[0], 'clipped_frames': clipped + w[1], 'first_clipped_frame': first,
-                         'near_frames': w[3], 'canvas_epoch': one.canvas_epoch,
-                         'needed_bbox': tuple(float(x) for x in one._needed_bbox(wf[s]))})
-        return reps
+        return self.watch.report()
 
-    @property
-    def clipped_frames(self):
-        """Per stream: frames emitted so far whose mesh reached outside the canvas they were rendered on (synchronises)."""
-        return [r['clipped_frames'] for r in self.overflow_report()]
-
-    def _poll_growth(self):
-        if self._host_event is None or not self._host_event.query():
-            return
-        near = self._host_watch[0][:, 3].tolist()
-        cand = [s for s, one in enumerate(self.single) if near[s] > one._near_handled]
-        if not cand:
-            return
-        st = self.static
-        wi, wf = st['watch_i'].cpu(), st['watch_f'].cpu()              # (rare path: synchronises)
-        fresh_i, fresh_f = ops.canvas_watch_state(1, self.dev)
-        grown = False
-        for s in cand:
+    def _regrown(self, rows):
+        """grow='recapture': the watcher re-fixed the canvases of these streams -- new boxes, sizes and outputs (the graph is captured
+        again)."""
+        for s in rows:
             one = self.single[s]
-            if not one._regrow(wi[s].tolist(), wf[s]):                 # nothing to grow by: canvas, outputs and graph stay
-                continue
-            grown = True
-            st['bboxes'][s].copy_(one.bbox)
-            st['watch_i'][s].copy_(fresh_i[0]); st['watch_f'][s].copy_(fresh_f[0])
-        if grown:
-            self._alloc_outputs()
-            self.graph = None
-        self._host_event = None
+            one.bbox = self.watch.boxes[s].to(self.dev)
+            one.hc, one.wc = _canvas_size(self.watch.boxes[s])
+            self.static['bboxes'][s].copy_(one.bbox)
+        self._alloc_outputs()
 
-    def _post_watch_copy(self):
+    def _load(self, frames, u8):
         st = self.static
-        if self._host_watch is None:
-            self._host_watch = (torch.empty((self.S, 4), dtype=torch.int32).pin_memory(), torch.empty((self.S, 4), dtype=torch.float32).pin_memory())
-        self._host_watch[0].copy_(st['watch_i'], non_blocking=True)
-        self._host_watch[1].copy_(st['watch_f'], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.dev))
-        self._host_event = ev
+        if u8 is not None:               # push_u8: decoded [S,H,W,3] frames of both views -- the cv2-exact resize writes the LR inputs
+            ops.ingest_u8(u8[0], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr1'])
+            ops.ingest_u8(u8[1], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr2'])
+            return
+        hr1, hr2, lr1, lr2 = frames
+        if self.chain:                   # (pair s = views s, s + 1: lr1 holds views 0 .. S-1, lr2's last row is view S)
+            st['lrc'][:self.S].copy_(lr1); st['lrc'][self.S:].copy_(lr2[self.S - 1:])
+        else:
+            st['lr1'].copy_(lr1); st['lr2'].copy_(lr2)
+        if not self.meshes_only and not self._direct():
+            st['hr1'].copy_(hr1); st['hr2'].copy_(hr2)
 
     def _step_static(self):
         st = self.static
         f64, feat, off1 = self._stage_a(st['lrc'] if self.chain else [st['lr1'], st['lr2']])
         self._stage_b(f64, feat, off1, st['hr1'], st['hr2'], st['out_all'], st['out'], defer=self._direct())
 
-    def _direct(self):
-        """DIRECT_RENDER: the captured step stops at splines + footprints, the push renders from the caller's frames."""
-        return bool(DIRECT_RENDER and self.use_graph and self.fusion_mode == 'AVERAGE' and not self.meshes_only)
-
     def _stage_a(self, lr):
         """First half of a steady-state push (no stream state): trunks, SpatialNet's stage-2 trunk, CCL, regressNet1.
         lr: [lr1, lr2] ([S,3,360,480] each) or, chain mode, the S + 1 views' frames [S+1,3,360,480] (each view once)
         -> (f64 SpatialNet trunk features, feat TemporalNet features [2S, view-major] (chain: [S + 1], each view once), offset_1 [S,8] | None)."""
         S = self.S
-        if self.trunk_pair is None:
-            self.trunk_pair = L.pair_trunks(self.spatial._prepared()['s1'], self.temporal._prepared()['s1'])
-            self.trunk_versions = self._versions()
         if self.chain:
-            fc = L.run_stage1_pair([lr], self.trunk_pair)                          # [2(net), S + 1 views, 45,60,128]: each view once
+            fc = L.run_stage1_pair([lr], self._trunk())                            # [2(net), S + 1 views, 45,60,128]: each view once
             feat = fc[1]                                                           # TemporalNet's features of the S + 1 views, each once
             f64 = fc[0]
         else:
-            f2 = L.run_stage1_pair(list(lr), self.trunk_pair)                      # [2(net), 2S (view-major), 45,60,128]
+            f2 = L.run_stage1_pair(list(lr), self._trunk())                        # [2(net), 2S (view-major), 45,60,128]
             feat, f64 = f2[1], f2[0]
         return f64, feat, (_heads_a(self.spatial, f64, S, self.chain) if L.QUAD else None)
 
@@ -990,20 +1038,15 @@ class MultiOnlineStitcher:
         if self.meshes_only:
             self.last_meshes = (m1[:, -1:], m2[:, -1:])                                       # [S,1,7,9,2]
             return
-        # every stream's newest smoothed mesh on its own canvas: one normalisation launch per view and ONE batched TPS solve for
-        # the 2 S splines (a solve is latency-bound, ~48 us whether it holds 2 systems or 16), then the render stream by stream
-        guard = self.single[0]._guard()
+        # every stream's newest smoothed mesh on its own canvas: control points and ONE batched TPS solve for the 2 S splines in one
+        # launch (a solve is latency-bound, ~48 us whether it holds 2 systems or 16), the watcher on the footprint launch(es), then
+        # the render stream by stream
+        src, T = ops.stream_splines([m1[0, -1], m2[0, -1]], WINDOW * e, st['bboxes'], self.single[0].nrigid, self.h, self.w)
         watch = None
-        if FUSED_SPLINES:                    # control points + splines in one launch; the watcher rides on the footprint launch(es)
-            src, T = ops.stream_splines([m1[0, -1], m2[0, -1]], WINDOW * e, st['bboxes'], self.single[0].nrigid, self.h, self.w)
-            if self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE:
-                watch = (guard, st['watch_i'], st['watch_f'])
-            else:
-                ops.canvas_watch(src, st['watch_i'], st['watch_f'], guard)
+        if self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE:
+            watch = self.watch.args()
         else:
-            src = ops.stream_normalize_watch([m1[0, -1], m2[0, -1]], WINDOW * e, st['bboxes'], self.h, self.w, guard,
-                                             st['watch_i'], st['watch_f'])                                         # [S,2,63,2]
-            T = ops.tps_solve_shared(src.view(2 * S, 63, 2), self.single[0].nrigid).view(S, 2, 2, 66)
+            ops.canvas_watch(src, self.watch.wi, self.watch.wf, self.watch.guard)
         if out_all is not None:
             # all streams render onto canvases of ONE size (e.g. the caller fixed them): the S current frames are a clip
             hc, wc = self.single[0].hc, self.single[0].wc
@@ -1017,77 +1060,31 @@ class MultiOnlineStitcher:
                 ops.render_linear_clip([hr1, hr2], src, T, hc, wc, self.warp_mode, out=out_all)
             return
         for s, one in enumerate(self.single):
-            one._render_solved(None if defer else hr1[s:s + 1], None if defer else hr2[s:s + 1], src[s], T[s], out=_DEFER if defer else out[s],
-                               watch=None if watch is None else (guard, st['watch_i'][s:s + 1], st['watch_f'][s:s + 1]))
+            one._render_solved(None if defer else [hr1[s:s + 1], hr2[s:s + 1]], src[s], T[s], out=_DEFER if defer else out[s],
+                               watch=None if watch is None else self.watch.args(s))
 
-    def _push_static(self, hr1, hr2, lr1, lr2, u8=None):
-        st = self.static
-        if self.grow == 'recapture' and not self.meshes_only:
-            self._poll_growth()
-        if self.trunk_pair is not None and self.trunk_versions != self._versions():
-            self.trunk_pair = None           # a net was reloaded / moved: restack the twin trunk and recapture
-            self.graph = None
-        direct = self._direct()
-        if u8 is not None:               # push_u8: decoded [S,H,W,3] frames of both views -- the cv2-exact resize writes the LR inputs
-            ops.ingest_u8(u8[0], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr1'])
-            ops.ingest_u8(u8[1], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr2'])
-        else:
-            if self.chain:               # (pair s = views s, s + 1: lr1 holds views 0 .. S-1, lr2's last row is view S)
-                st['lrc'][:self.S].copy_(lr1); st['lrc'][self.S:].copy_(lr2[self.S - 1:])
-            else:
-                st['lr1'].copy_(lr1); st['lr2'].copy_(lr2)
-            if not self.meshes_only and not direct:
-                st['hr1'].copy_(hr1); st['hr2'].copy_(hr2)
-        if not self.use_graph:
-            self._step_static()
-        elif self.graph is None:
-            keep = {k: st[k].clone() for k in self._STATE + (() if self.meshes_only else ('watch_i', 'watch_f'))}
-            side = _warmup_stream(self.dev)
-            side.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(side):
-                self._step_static()
-            torch.cuda.current_stream(self.dev).wait_stream(side)
-            for k, v in keep.items():
-                st[k].copy_(v)
-            g = _new_graph()
-            with torch.cuda.graph(g):
-                self._step_static()
-            self.graph = g
-            self.graph_nodes = _graph_nodes(g)
-            for k, v in keep.items():
-                st[k].copy_(v)
-            self.graph.replay()
-        else:
-            self.graph.replay()
-        self.frames_in += 1
-        if self.meshes_only:             # (m1, m2) [S,1,7,9,2]: copies of the step's own tensors
-            return tuple(m.clone() for m in self.last_meshes)
-        if self.grow == 'recapture':
-            self._post_watch_copy()
-        if direct and u8 is not None:    # uint8 frames in, uint8 video frames out: one clip-style launch, or one launch per canvas size
-            if st['out_all'] is not None:
-                src, T, fp = self._deferred
-                one = self.single[0]
-                frames = ops.render_average_clip_u8([u8[0], u8[1]], src, T, one.hc, one.wc, self.warp_mode, footprint=fp)
-                return [[frames[s]] for s in range(self.S)]
-            res = []
-            for s, one in enumerate(self.single):
-                src, T, fp = one._deferred
-                res.append([ops.render_average_u8([u8[0][s], u8[1][s]], src, T, one.hc, one.wc, self.warp_mode, footprint=fp)])
-            return res
-        if direct:                       # the graph left splines and footprints: render from the caller's frames into new tensors
-            hr1, hr2 = hr1.reshape(st['hr1'].shape), hr2.reshape(st['hr2'].shape)
-            if st['out_all'] is not None:
-                src, T, fp = self._deferred
-                one = self.single[0]
-                frames = ops.render_average_clip([hr1.contiguous(), hr2.contiguous()], src, T, one.hc, one.wc, self.warp_mode, footprint=fp)
-                return [[frames[s]] for s in range(self.S)]
-            res = []
-            for s, one in enumerate(self.single):
-                src, T, fp = one._deferred
-                res.append([ops.render_average([hr1[s:s + 1], hr2[s:s + 1]], src, T, one.hc, one.wc, self.warp_mode, footprint=fp)])
-            return res
-        return [[o.clone()] for o in st['out']]
+    def _deferred_splines(self):
+        if self.static['out_all'] is not None:
+            return getattr(self, '_deferred', None)
+        return [getattr(one, '_deferred', None) for one in self.single]
+
+    def _render_direct(self, deferred, imgs, u8):
+        """S canvases, two views: one clip-style launch when the canvases share a size, else one launch per stream."""
+        S = self.S
+        if not u8:
+            imgs = [f.reshape(S, 3, self.h, self.w) for f in imgs]
+        if self.static['out_all'] is not None:
+            src, T, fp = deferred
+            one = self.single[0]
+            render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
+            frames = render([f.contiguous() for f in imgs], src, T, one.hc, one.wc, self.warp_mode, footprint=fp)
+            return [[frames[s]] for s in range(S)]
+        render = ops.render_average_u8 if u8 else ops.render_average          # (uint8 frames [H,W,3], fp32 ones [1,3,H,W])
+        res = []
+        for s, one in enumerate(self.single):
+            src, T, fp = deferred[s]
+            res.append([render([f[s] if u8 else f[s:s + 1] for f in imgs], src, T, one.hc, one.wc, self.warp_mode, footprint=fp)])
+        return res
 
     @torch.no_grad()
     def push_u8(self, frames1, frames2):
@@ -1096,13 +1093,10 @@ class MultiOnlineStitcher:
         S = self.S
         if self.meshes_only or self.chain:
             raise ValueError('push_u8 renders frames of independent streams: not for meshes_only / chain stitchers')
-        for f in (frames1, frames2):
-            if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[0] != S or f.shape[-1] != 3 or tuple(f.shape) != tuple(frames1.shape):
-                raise ValueError('push_u8 takes two uint8 [%d,H,W,3] tensors' % S)
-        _check_shapes('uint8 frames', (frames1, frames2), ((S, self.h, self.w, 3),))
+        _check_u8('two uint8 [%d,H,W,3] tensors' % S, (frames1, frames2), (S, self.h, self.w, 3))
         with ops.deterministic(self.deterministic):
-            if self.static is not None and self._direct() and type(self)._push_static is MultiOnlineStitcher._push_static:
-                return self._push_static(None, None, None, None, u8=(frames1.contiguous(), frames2.contiguous()))
+            if self._u8_steady():
+                return self._push_static(u8=(frames1.contiguous(), frames2.contiguous()))
             hr1, lr1 = ops.ingest_u8(frames1, pipeline.LR_H, pipeline.LR_W)
             hr2, lr2 = ops.ingest_u8(frames2, pipeline.LR_H, pipeline.LR_W)
             outs = self._push(hr1, hr2, lr1, lr2)
@@ -1122,7 +1116,6 @@ class MultiOnlineStitcher:
             return self._push(hr1, hr2, lr1, lr2)
 
     def _push(self, hr1, hr2, lr1, lr2):
-        S = self.S
         if self.static is not None:
             return self._push_static(hr1, hr2, lr1, lr2)
         hs = (lambda h, s: None) if self.meshes_only else (lambda h, s: h[s:s + 1])
@@ -1145,13 +1138,12 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
         for batch in source: per_stream = st.push(*batch)        # S lists: [] x 6, 7 frames, [] (one push of lag), then 1 frame each
         per_stream = st.flush()
     Canvases are fixed after the first window (grow='never')."""
+    _U8_STEADY = False       # push_u8: ingest_u8 -> push -> canvas_to_u8
 
     def __init__(self, nets, height, width, streams, canvases=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
                  deterministic=False):
         MultiOnlineStitcher.__init__(self, nets, height, width, streams, canvases, margin, warp_mode, fusion_mode, use_graph=True,
                                      grow='never', meshes_only=False, deterministic=deterministic)
-        if not L.QUAD:
-            raise ValueError('PipelinedMultiOnlineStitcher needs the shared regressor launches (SS_QUAD_REGRESSOR=1)')
         self._pipe_init()
 
     def _pipe_alloc(self):
@@ -1169,9 +1161,6 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
             P['out'] = [[torch.empty_like(o) for o in self.static['out']] for _ in range(2)]
         return P
 
-    def _pipe_state(self):
-        return [self.static[k] for k in self._STATE + ('watch_i', 'watch_f')]
-
     def _pipe_empty(self):
         return [[] for _ in range(self.S)]
 
@@ -1179,7 +1168,7 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
         P = self.pipe
         with torch.cuda.stream(sa):
             P['lr'][p][0].copy_(lr1); P['lr'][p][1].copy_(lr2)
-        if not self._direct():               # (direct render: the second stream's render reads the caller's frames)
+        if not self._direct():                  # (direct render: the second stream's render reads the caller's frames)
             with torch.cuda.stream(sb):
                 P['hr'][p][0].copy_(hr1); P['hr'][p][1].copy_(hr2)
         for t in (hr1, hr2):
@@ -1199,32 +1188,8 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
         self._stage_b(P['f64'][p], P['feat'][p], P['off1'][p], P['hr'][p][0], P['hr'][p][1], P['out_all'][p], P['out'][p],
                       defer=self._direct())
 
-    def _pipe_deferred(self):
-        if self.static['out_all'] is not None:
-            return getattr(self, '_deferred', None)
-        return [getattr(one, '_deferred', None) for one in self.single]
 
-    def _pipe_take(self, p, hr1, hr2, lr1, lr2):
-        P = self.pipe
-        if not self._direct():
-            return [[o.clone()] for o in P['out'][p]]
-        hr1, hr2 = hr1.reshape(self.S, 3, self.h, self.w), hr2.reshape(self.S, 3, self.h, self.w)
-        if self.static['out_all'] is not None:
-            src, T, fp = P['deferred'][p]
-            one = self.single[0]
-            frames = ops.render_average_clip([hr1.contiguous(), hr2.contiguous()], src, T, one.hc, one.wc, self.warp_mode, footprint=fp)
-            return [[frames[s]] for s in range(self.S)]
-        res = []
-        for s, one in enumerate(self.single):
-            src, T, fp = P['deferred'][p][s]
-            res.append([ops.render_average([hr1[s:s + 1], hr2[s:s + 1]], src, T, one.hc, one.wc, self.warp_mode, footprint=fp)])
-        return res
-
-    def _push_static(self, hr1, hr2, lr1, lr2):
-        return self._push_pipelined(hr1, hr2, lr1, lr2)
-
-
-class ThreeViewOnlineStitcher:
+class ThreeViewOnlineStitcher(_Stitcher):
     """Streaming form of the three-view script (test_online_tra_threeview.py:154-505, whose frame loops run the same sliding
     windows as the two-view script): one frame TRIPLE per push.  Two pair chains -- (view 1, view 2) and (view 2, view 3), run as ONE
     batch of two streams (`MultiOnlineStitcher(streams=2, meshes_only=True, chain=True)`: ring buffers, cached TemporalNet features,
@@ -1244,49 +1209,20 @@ class ThreeViewOnlineStitcher:
 
     def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
                  use_graph=True, grow='never'):
-        if grow not in ('never', 'recapture'):
-            raise ValueError("grow must be 'never' or 'recapture'")
-        self.grow = grow
-        self.nets = nets
-        self.dev = next(nets[0].parameters()).device
-        self.h, self.w = height, width
-        self.margin = margin
-        self.warp_mode, self.fusion_mode = warp_mode, fusion_mode
-        self.use_graph = use_graph
         # the two pair chains as a batch of two streams over the CHAIN of three views: every launch serves both pairs, view 2's
         # trunk features are computed once
         self.chains = MultiOnlineStitcher(nets, height, width, streams=2, margin=margin, warp_mode=warp_mode, fusion_mode=fusion_mode,
                                           use_graph=False, meshes_only=True, chain=True)
+        _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow)
         box = lambda b: None if b is None else torch.tensor(b, dtype=torch.float32, device=self.dev)
         self.bbox, self.first_canvas = box(canvas), box(first_canvas)
         self.hc = self.wc = None
         self.nrigid = get_norm_mesh(get_rigid_mesh(1, height, width, device=self.dev), height, width).contiguous()
         self.ring_hr = []
-        self.frames_in = 0
-        self.static = None
-        self.graph = None
-        self.graph_nodes = None
-        self.versions = None
-        # overflow state of the output canvas (the methods are OnlineStitcher's)
-        self.canvas_epoch = 0
-        self.watch_i = self.watch_f = None
-        self._watch_totals = [0, 0, -1]
-        self._host_watch = self._host_event = None
-        self._near_handled = 0
 
-    # ------------------------------------------------------------------ overflow / growth of the output canvas: as OnlineStitcher
-    _guard = OnlineStitcher._guard
-    _set_canvas = OnlineStitcher._set_canvas
-
-    def _direct(self):
-        return bool(DIRECT_RENDER and self.use_graph and self.fusion_mode == 'AVERAGE')
-
-    _needed_bbox = OnlineStitcher._needed_bbox
-    _regrow = OnlineStitcher._regrow
-    _poll_growth = OnlineStitcher._poll_growth
-    _post_watch_copy = OnlineStitcher._post_watch_copy
-    overflow_report = OnlineStitcher.overflow_report
-    clipped_frames = OnlineStitcher.clipped_frames
+    # the twin trunk lives in the pair chains
+    trunk_pair = property(lambda self: self.chains.trunk_pair, lambda self, v: setattr(self.chains, 'trunk_pair', v))
+    trunk_versions = property(lambda self: self.chains.trunk_versions, lambda self, v: setattr(self.chains, 'trunk_versions', v))
 
     # ------------------------------------------------------------------ composition + render of k frames
     def _compose(self, m12, m23):
@@ -1301,118 +1237,52 @@ class ThreeViewOnlineStitcher:
         composition + the render's splines as ONE launch (FUSED_SPLINES; else the seven launches it replaces), then the render."""
         if FUSED_SPLINES:
             meshes, src, T = ops.three_view_splines(m1[0], m2[0], m1[1], m2[1], self.first_canvas, self.bbox, self.nrigid, self.h, self.w)
-            self.last_composed = meshes
-            return self._render(imgs, meshes, out=out, splines=(src[0], T[0]))
-        meshes = self._compose((m1[0], m2[0]), (m1[1], m2[1]))
+            splines = (src[0], T[0])
+        else:
+            meshes, splines = self._compose((m1[0], m2[0]), (m1[1], m2[1])), None
         self.last_composed = meshes
-        return self._render(imgs, meshes, out=out)
-
-    def _grown(self, bb):
-        bb = bb.cpu()
-        gw, gh = self.margin * (bb[1] - bb[0]), self.margin * (bb[3] - bb[2])
-        return torch.stack((bb[0] - gw, bb[1] + gw, bb[2] - gh, bb[3] + gh)).to(self.dev)
+        return self._render(imgs, meshes, out=out, splines=splines)
 
     def _render(self, imgs, meshes, out=None, splines=None):
         """imgs: three [1,3,H,W]; meshes: (mesh1, middle, mesh3) [1,1,7,9,2] in first-canvas pixels -> [3,Hc,Wc].
         splines = (src [3,63,2], T [3,2,66]) from ops.three_view_splines: the steady-state push has them already, and the overflow
         watcher runs inside the footprint launch (or as a launch of its own when there is none)."""
-        watch = None
-        if splines is None:
-            src4 = ops.stream_normalize_watch([m.contiguous() for m in meshes], 126, self.bbox, 0.0, 0.0, self._guard(), self.watch_i,
-                                              self.watch_f)                          # [1,3,63,2] on the output canvas
-            src = src4[0]
-            T = ops.tps_solve_shared(src, self.nrigid)
-        else:
-            src, T = splines
-            if self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE:
-                watch = (self._guard(), self.watch_i, self.watch_f)
-            else:
-                ops.canvas_watch(src[None], self.watch_i, self.watch_f, self._guard())
-        if self.fusion_mode == 'AVERAGE':
-            fp = ops.render_footprints(src[None], T[None], self.h, self.w, self.hc, self.wc, watch=watch)[0] if pipeline.SKIP_OUTSIDE else None
-            if out is _DEFER:
-                self._deferred = (src, T, fp)
-                return None
-            return ops.render_average(imgs, src, T, self.hc, self.wc, self.warp_mode, out=out, footprint=fp)
-        w = ops.tps_warp_views(imgs, src, T, self.hc, self.wc, self.warp_mode)        # [3,4,Hc,Wc]
-        f = ops.linear_blend(w[0, 0:3], w[1, 0:3], w[0, 3], w[1, 3])
-        res = ops.linear_blend(f, w[2, 0:3], ops.mask_union(w[0, 3], w[1, 3]), w[2, 3])
-        return res if out is None else out.copy_(res)
+        if splines is not None:
+            return self._render_solved(imgs, splines[0], splines[1], out, watch=self.watch.args())
+        src = ops.stream_normalize_watch([m.contiguous() for m in meshes], 126, self.bbox, 0.0, 0.0,
+                                         *self.watch.args())[0]                   # [3,63,2] on the output canvas, watcher updated
+        return self._render_solved(imgs, src, ops.tps_solve_shared(src, self.nrigid), out)
 
     # ------------------------------------------------------------------ steady state
-    def _versions(self):
-        return tuple(n.weights_version for n in self.nets)
+    def _state(self):
+        return [self.chains.static[k] for k in _STATE] + [self.watch.wi, self.watch.wf]
 
     def _step_static(self):
-        ch, st = self.chains, self.static
+        ch, hr = self.chains, self.static['hr']
         ch._step_static()
         m1, m2 = ch.last_meshes                                  # [2,1,7,9,2]: stream 0 = pair (1,2), stream 1 = pair (2,3)
-        hr = st['hr']
-        self._compose_render(m1, m2, [hr[0:1], hr[1:2], hr[2:3]], _DEFER if self._direct() else st['out'])
+        imgs = None if hr is None else [hr[0:1], hr[1:2], hr[2:3]]
+        self._compose_render(m1, m2, imgs, _DEFER if self._direct() else self.static['out'])
 
-    def _state(self):
-        return [self.chains.static[k] for k in MultiOnlineStitcher._STATE] + [self.watch_i, self.watch_f]
-
-    def _push_static(self, hr1, hr2, hr3, lr1, lr2, lr3, u8=None):
+    def _load(self, frames, u8):
         c, st = self.chains.static, self.static
-        if self.grow == 'recapture':
-            self._poll_growth()
-        if self.versions != self._versions():         # a net was reloaded / moved: stale twin trunk and graph
-            self.chains.trunk_pair = None
-            self.graph = None
-            self.versions = self._versions()
-        direct = self._direct()
-        for k, (h, l) in enumerate(((hr1, lr1), (hr2, lr2), (hr3, lr3))):      # each view once: three frames, three LR frames
+        for k in range(3):                                                     # each view once: three frames, three LR frames
             if u8 is not None:                                                 # decoded uint8 frames: resized into the graph's LR inputs
                 ops.ingest_u8(u8[k][None], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=c['lrc'][k:k + 1])
                 continue
-            if not direct:                                                     # (direct: the render reads the caller's frames)
+            h, l = frames[k], frames[3 + k]
+            if not self._direct():                                                # (direct: the render reads the caller's frames)
                 st['hr'][k:k + 1].copy_(h.reshape(st['hr'][k:k + 1].shape))
             c['lrc'][k:k + 1].copy_(l.reshape(c['lrc'][k:k + 1].shape))
-        if not self.use_graph:
-            self._step_static()
-        elif self.graph is None:
-            state = self._state()
-            keep = [t.clone() for t in state]
-            side = _warmup_stream(self.dev)
-            side.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(side):
-                self._step_static()
-            torch.cuda.current_stream(self.dev).wait_stream(side)
-            for t, v in zip(state, keep):
-                t.copy_(v)
-            g = _new_graph()
-            with torch.cuda.graph(g):
-                self._step_static()
-            self.graph = g
-            self.graph_nodes = _graph_nodes(g)
-            for t, v in zip(state, keep):          # capture does not execute: state is still the pre-push state
-                t.copy_(v)
-            self.graph.replay()
-        else:
-            self.graph.replay()
-        self.frames_in += 1
-        if self.grow == 'recapture':
-            self._post_watch_copy()
-        if direct:                       # the graph left splines and footprints; the render reads the caller's frames, writes a new tensor
-            src, T, fp = self._deferred
-            if u8 is not None:
-                return [ops.render_average_u8(list(u8), src, T, self.hc, self.wc, self.warp_mode, footprint=fp)]
-            shp = st['hr'][0:1].shape
-            return [ops.render_average([hr1.reshape(shp), hr2.reshape(shp), hr3.reshape(shp)], src, T, self.hc, self.wc, self.warp_mode,
-                                       footprint=fp)]
-        return [st['out'].clone()]
 
     @torch.no_grad()
     def push_u8(self, img1, img2, img3):
         """One DECODED frame triple: uint8 [H,W,3] device tensors (cv2 layout) -> list of stitched video frames uint8 [Hc,Wc,3]; byte for
         byte ops.ingest_u8 -> push -> ops.canvas_to_u8 (see OnlineStitcher.push_u8)."""
         imgs = (img1, img2, img3)
-        if any(i.dtype != torch.uint8 or i.dim() != 3 or i.shape[-1] != 3 or tuple(i.shape) != tuple(img1.shape) for i in imgs):
-            raise ValueError('push_u8 takes three uint8 [H,W,3] frames')
-        _check_shapes('uint8 frames', imgs, ((self.h, self.w, 3),))
-        if self.static is not None and self._direct() and type(self)._push_static is ThreeViewOnlineStitcher._push_static:
-            return self._push_static(None, None, None, None, None, None, u8=tuple(i.contiguous() for i in imgs))
+        _check_u8('three uint8 [H,W,3] frames', imgs, (self.h, self.w, 3))
+        if self._u8_steady():
+            return self._push_static(u8=tuple(i.contiguous() for i in imgs))
         hr, lr = ops.ingest_u8(torch.stack(imgs, 0), pipeline.LR_H, pipeline.LR_W)
         frames = self.push(hr[0:1], hr[1:2], hr[2:3], lr[0:1], lr[1:2], lr[2:3])
         return [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
@@ -1445,9 +1315,9 @@ class ThreeViewOnlineStitcher:
         self._set_canvas()
         frames = [self._render(list(hr), [m[:, i:i + 1] for m in meshes]) for i, hr in enumerate(self.ring_hr)]
         self.ring_hr = []
-        self.static = {'out': torch.empty((3, self.hc, self.wc), device=self.dev),
-                       'hr': torch.empty((3, 3, self.h, self.w), device=self.dev)}
-        self.versions = self._versions()
+        # (frame copies and an output canvas only where the graph renders: the direct render reads the caller's frames)
+        self.static = {'out': None if self._direct() else torch.empty((3, self.hc, self.wc), device=self.dev),
+                       'hr': None if self._direct() else torch.empty((3, 3, self.h, self.w), device=self.dev)}
         return frames
 
 
@@ -1455,17 +1325,12 @@ class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
     """ThreeViewOnlineStitcher with TWO pushes in flight (round 6; opt-in; see _TwoInFlight): the three views' trunks and the two
     pairs' stage-1 heads of triple t + 1 run beside triple t's regressor heads, smoothing, composition and three-image render.  Frames
     bit-identical to ThreeViewOnlineStitcher's, handed out one push late (`flush()` for the last); boxes fixed after the first window."""
+    _U8_STEADY = False       # push_u8: ingest_u8 -> push -> canvas_to_u8
 
     def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE'):
         ThreeViewOnlineStitcher.__init__(self, nets, height, width, canvas, first_canvas, margin, warp_mode, fusion_mode,
                                          use_graph=True, grow='never')
-        if not L.QUAD:
-            raise ValueError('PipelinedThreeViewOnlineStitcher needs the shared regressor launches (SS_QUAD_REGRESSOR=1)')
         self._pipe_init()
-
-    # the twin trunk lives in the pair chains
-    trunk_pair = property(lambda self: self.chains.trunk_pair, lambda self, v: setattr(self.chains, 'trunk_pair', v))
-    trunk_versions = property(lambda self: self.chains.trunk_versions, lambda self, v: setattr(self.chains, 'trunk_versions', v))
 
     def _pipe_alloc(self):
         d = self.dev
@@ -1475,18 +1340,12 @@ class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
                 'f64': two(3, fh, fw, 128),
                 'feat': two(3, fh, fw, 128), 'off1': two(2, 8), 'out': [None, None] if self._direct() else two(3, self.hc, self.wc)}
 
-    def _pipe_state(self):
-        return self._state()
-
-    def _pipe_empty(self):
-        return []
-
     def _pipe_load(self, p, sa, sb, hr1, hr2, hr3, lr1, lr2, lr3):
         P = self.pipe
         for k, (h, l) in enumerate(((hr1, lr1), (hr2, lr2), (hr3, lr3))):
             with torch.cuda.stream(sa):
                 P['lrc'][p][k:k + 1].copy_(l.reshape(P['lrc'][p][k:k + 1].shape))
-            if not self._direct():           # (direct render: the second stream's render reads the caller's frames)
+            if not self._direct():              # (direct render: the second stream's render reads the caller's frames)
                 with torch.cuda.stream(sb):
                     P['hr'][p][k:k + 1].copy_(h.reshape(P['hr'][p][k:k + 1].shape))
             h.record_stream(sb)
@@ -1506,18 +1365,6 @@ class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
         hr = P['hr'][p]
         imgs = None if hr is None else [hr[0:1], hr[1:2], hr[2:3]]
         self._compose_render(m1, m2, imgs, _DEFER if self._direct() else P['out'][p])
-
-    def _pipe_take(self, p, hr1, hr2, hr3, lr1, lr2, lr3):
-        P = self.pipe
-        if self._direct():
-            src, T, fp = P['deferred'][p]
-            shp = (1, 3, self.h, self.w)
-            return [ops.render_average([hr1.reshape(shp), hr2.reshape(shp), hr3.reshape(shp)], src, T, self.hc, self.wc, self.warp_mode,
-                                       footprint=fp)]
-        return [P['out'][p].clone()]
-
-    def _push_static(self, hr1, hr2, hr3, lr1, lr2, lr3):
-        return self._push_pipelined(hr1, hr2, hr3, lr1, lr2, lr3)
 
 
 class HostFrameStream:

@@ -546,6 +546,7 @@ def test_direct_render_is_frame_neutral(dev, hip_nets, clip16, monkeypatch):
             out[(direct, cls.__name__)] = [f.clone() for f in frames]
             if direct and cls is OnlineStitcher:
                 assert st._direct() and frames[-1].data_ptr() != frames[-2].data_ptr()
+                assert st.static['hr1'] is None and st.static['hr2'] is None          # no static HR buffers for a render outside the graph
     for name in ('OnlineStitcher', 'PipelinedOnlineStitcher'):
         a, b = out[(True, name)], out[(False, name)]
         assert len(a) == len(b) == 20
