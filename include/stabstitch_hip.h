@@ -397,6 +397,12 @@ SS_API int ss_stream_splines(const float* const* meshes, int views, long long me
  *   watch_f [streams][4] fp32  = running {xmin, xmax, ymin, ymax} of the normalised coordinates (what a grown canvas must cover)
  * Initialise to {0, 0, -1, 0} / {+inf, -inf, +inf, -inf}. */
 SS_API int ss_canvas_watch(const float* src, int streams, int views, float guard, int* watch_i, float* watch_f, void* stream);
+/* k consecutive frames of ONE stream (OnlineStitcher.push_many: the frames of test_online_tra.py:359-392 taken k at a time): src
+ * [frames][views][63][2] on the stream's canvas -> its single watcher row watch_i [4] / watch_f [4] (layout as above), updated frame
+ * by frame in stream order by one wave: the row ends exactly as `frames` calls of ss_canvas_watch (streams = 1) leave it -- frames
+ * seen + frames, clipped and near frames counted one by one, the first clipped index = frames seen before + the index within the
+ * batch, extents folded, a NaN point outside. */
+SS_API int ss_canvas_watch_frames(const float* src, int frames, int views, float guard, int* watch_i, float* watch_f, void* stream);
 /* One streaming push's control points of ALL views + the watcher above in ONE launch (one wave per stream; a batch-1 push is
  * bound by its launch count): meshes[v] = view v's newest LR-scale meshes, stream s at meshes[v] + s * mesh_frame_stride floats;
  * bboxes [4] (bbox_frame_stride 0: one canvas) or [streams][4] (4: a canvas per stream); out [streams][views][63][2] = what `views`
@@ -453,6 +459,18 @@ SS_API int ss_window_push(float* ring, const float* src, const long long* src_of
  * state block, stride >= delta + block (the blocks move without ordering between them). */
 SS_API int ss_window_push_groups(float* ring, const float* src, const long long* src_off, int groups, int per, int window,
                           int elems, float* state, int blocks, int block, long long stride, long long delta, void* stream);
+/* k frames of ONE stream per launch (OnlineStitcher.push_many; the sliding windows of test_online_tra.py:359-392 for k
+ * consecutive frames): for each ring r of `rings` <= 8, ring [rings][window][elems] and work [rings][window - 1 + k][elems] (1 <= k
+ * <= 32, window * elems <= 2048, work not overlapping the rings):
+ *   work[r] <- ring[r] rows 1 .. window - 1, then the k new rows at src + src_off[r] + j * elems (src_off: HOST array), j < k
+ *   ring[r] <- the last `window` rows of work[r]
+ * -- the rings end bit for bit as k calls of ss_window_push leave them, and window j of the batch is work rows j .. j + window - 1.
+ * In the same launch `blocks` <= 8 state blocks of `block` floats are copied: block b at state + b * stride <- the block at
+ * state_src + b * src_stride (no destination block may overlap a source block; state_src = state + delta, src_stride = stride is
+ * ss_window_push's move).  One workgroup per ring: it reads every value it writes back before its barrier. */
+SS_API int ss_window_advance(float* ring, float* work, const float* src, const long long* src_off, int rings, int window, int elems,
+                             int k, float* state, const float* state_src, int blocks, int block, long long stride,
+                             long long src_stride, void* stream);
 
 /* canvas-sized elementwise helpers of the harnesses: out = (in + add) * mul  ((img+1)*127.5,
  * test_metric_ssd.py:166);  out = a + b - a*b  (three-view mask union, test_online_tra_threeview.py:501) */

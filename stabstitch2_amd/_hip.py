@@ -91,6 +91,7 @@ SIGNATURES = {
     'ss_mesh_bbox': (c_i, [c_fp, c_i, c_f, c_f, c_fp, c_i, c_st]),
     'ss_mesh_normalize': (c_i, [c_fp, c_fp, c_fp, c_i, c_f, c_f, c_st]),
     'ss_canvas_watch': (c_i, [c_fp, c_i, c_i, c_f, c_fp, c_fp, c_st]),
+    'ss_canvas_watch_frames': (c_i, [c_fp, c_i, c_i, c_f, c_fp, c_fp, c_st]),
     'ss_stream_normalize_watch': (c_i, [ctypes.c_void_p, c_i, c_ll, c_fp, c_i, c_fp, c_i, c_f, c_f, c_f, c_fp, c_fp, c_st]),
     'ss_mesh_normalize_views': (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_f, c_f, c_st]),
     'ss_mesh_normalize_views_boxes': (c_i, [c_fp, c_ll, c_fp, c_fp, c_i, c_i, c_i, c_f, c_f, c_st]),
@@ -106,6 +107,7 @@ SIGNATURES = {
     'ss_smooth_stitch': (c_i, [c_fp] * 11 + [c_i] * 2 + [c_st]),
     'ss_window_push': (c_i, [c_fp, c_fp, ctypes.c_void_p, c_i, c_i, c_i, c_fp, c_i, c_i, c_ll, c_ll, c_st]),
     'ss_window_push_groups': (c_i, [c_fp, c_fp, ctypes.c_void_p, c_i, c_i, c_i, c_i, c_fp, c_i, c_i, c_ll, c_ll, c_st]),
+    'ss_window_advance': (c_i, [c_fp, c_fp, c_fp, ctypes.c_void_p, c_i, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_ll, c_ll, c_st]),
     'ss_alignment_psnr_ssim': (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_st]),
     'ss_stability_score': (c_i, [c_fp, c_fp, c_i, c_st]),
     'ss_distortion_score': (c_i, [c_fp, c_fp, c_fp, c_i, c_st]),

@@ -991,6 +991,32 @@ extern "C" int ss_canvas_watch(const float* src, int streams, int views, float g
     return ss_launch_status();
 }
 
+// k consecutive frames of ONE stream (OnlineStitcher.push_many): src [frames][views][63][2] -> the stream's single watcher row, frame
+// by frame in stream order -- the row ends as `frames` launches of canvas_watch_kernel leave it (frames seen, clipped and near counted
+// one by one, the first clipped index taken from the running count, extents folded).  One wave; lane 0 owns the row.
+__global__ __launch_bounds__(64) void canvas_watch_frames_kernel(const float* __restrict__ src, int frames, int npts, float guard,
+                                                                 int* __restrict__ watch_i, float* __restrict__ watch_f) {
+    for (int f = 0; f < frames; ++f) {
+        const float* s = src + (long long)f * npts * 2;
+        float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+        bool bad = false;
+        for (int i = threadIdx.x; i < npts; i += 64) {
+            const float x = s[2 * i], y = s[2 * i + 1];
+            bad = bad || x != x || y != y;
+            xmin = fminf(xmin, x); xmax = fmaxf(xmax, x);
+            ymin = fminf(ymin, y); ymax = fmaxf(ymax, y);
+        }
+        canvas_watch_update(xmin, xmax, ymin, ymax, bad, guard, watch_i, watch_f);
+    }
+}
+extern "C" int ss_canvas_watch_frames(const float* src, int frames, int views, float guard, int* watch_i, float* watch_f,
+                                      void* stream) {
+    if (!src || !watch_i || !watch_f || frames <= 0 || views <= 0 || !(guard >= 0.f)) return SS_ERR_ARG;
+    hipLaunchKernelGGL(canvas_watch_frames_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, src, frames, views * SS_NV, guard,
+                       watch_i, watch_f);
+    return ss_launch_status();
+}
+
 // The streaming push's normalisation of ALL views + the overflow watcher as ONE launch (round 6; it was `views` launches of
 // mesh_normalize_views_kernel + canvas_watch_kernel per push): one wave per stream, same arithmetic per point, same watcher update.
 struct StreamMeshes {

@@ -229,3 +229,72 @@ extern "C" int ss_window_push(float* ring, const float* src, const long long* sr
                               float* state, int blocks, int block, long long stride, long long delta, void* stream) {
     return ss_window_push_groups(ring, src, src_off, rings, 1, window, elems, state, blocks, block, stride, delta, stream);
 }
+
+// k frames of ONE stream in one launch (OnlineStitcher.push_many; test_online_tra.py:359-392 for k consecutive frames): ring r
+// [W][E] and the k new rows at src + src_off[r] + j * E give the work rows [W-1+k][E] = ring rows 1..W-1, then the new rows (the
+// k sliding windows of the batch: window j = work rows j .. j+W-1), and the ring keeps the last W work rows -- what k calls of
+// window_push_kernel leave.  Each ring is one workgroup: every value it writes back to the ring is read (from the old ring or from
+// src, never from `work`) before the barrier.  The last workgroup copies `blocks` state blocks (block b at b * stride <- the block
+// at state_src + b * src_stride; no block overlaps another, host-checked).
+constexpr int WIN_ADV_MAXV = 8;                          // window * elems <= 2048 floats per ring (host-checked)
+__global__ __launch_bounds__(256) void window_advance_kernel(float* __restrict__ ring, float* __restrict__ work,
+                                                             const float* __restrict__ src, WinPushArgs a, int R, int W, int E,
+                                                             int k, float* __restrict__ state, const float* __restrict__ state_src,
+                                                             int blocks, int block, long long stride, long long src_stride) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    if (r == R) {
+        for (int i = tid; i < blocks * block; i += 256) {
+            const int b = i / block, e = i - b * block;
+            state[(long long)b * stride + e] = state_src[(long long)b * src_stride + e];
+        }
+        return;
+    }
+    float* g = ring + (long long)r * W * E;
+    float* wk = work + (long long)r * (W - 1 + k) * E;
+    const float* s = src + a.src_off[r];
+    const int keep = (W - 1) * E, n = W * E, nw = keep + k * E;
+    // work rows: the old ring's rows 1..W-1, then the k new rows
+    for (int i = tid; i < nw; i += 256) wk[i] = i < keep ? g[E + i] : s[i - keep];
+    // the new ring = work rows k-1 .. k+W-2, taken from where the work rows came from
+    float v[WIN_ADV_MAXV];
+#pragma unroll
+    for (int m = 0; m < WIN_ADV_MAXV; ++m) {
+        const int i = tid + 256 * m;
+        const int p = (k - 1) * E + i;
+        v[m] = i < n ? (p < keep ? g[E + p] : s[p - keep]) : 0.f;
+    }
+    __syncthreads();                                     // every old slot is read before any is overwritten
+#pragma unroll
+    for (int m = 0; m < WIN_ADV_MAXV; ++m) {
+        const int i = tid + 256 * m;
+        if (i < n) g[i] = v[m];
+    }
+}
+
+extern "C" int ss_window_advance(float* ring, float* work, const float* src, const long long* src_off, int rings, int window,
+                                 int elems, int k, float* state, const float* state_src, int blocks, int block, long long stride,
+                                 long long src_stride, void* stream) {
+    if (!ring || !work || !src || !src_off || rings <= 0 || rings > 8 || window < 2 || elems <= 0 || k < 1 || k > 32 ||
+        (long long)window * elems > 256 * WIN_ADV_MAXV || blocks < 0 || blocks > 8)
+        return SS_ERR_ARG;
+    const long long ring_n = (long long)rings * window * elems, work_n = (long long)rings * (window - 1 + k) * elems;
+    const uintptr_t g0 = (uintptr_t)ring, g1 = g0 + ring_n * 4, w0 = (uintptr_t)work, w1 = w0 + work_n * 4;
+    if (w0 < g1 && g0 < w1) return SS_ERR_ARG;           // the work rows must not overlap the rings
+    for (int r = 0; r < rings; ++r)
+        if (src_off[r] < 0) return SS_ERR_ARG;
+    if (blocks > 0) {
+        if (!state || !state_src || block <= 0 || stride < 0 || src_stride < 0 || (blocks > 1 && (stride < block || src_stride < block)))
+            return SS_ERR_ARG;
+        // no destination block may overlap a source block (they are copied without ordering between them)
+        for (int b = 0; b < blocks; ++b)
+            for (int c = 0; c < blocks; ++c) {
+                const uintptr_t d0 = (uintptr_t)(state + (long long)b * stride), s0 = (uintptr_t)(state_src + (long long)c * src_stride);
+                if (d0 < s0 + (uintptr_t)block * 4 && s0 < d0 + (uintptr_t)block * 4) return SS_ERR_ARG;
+            }
+    }
+    WinPushArgs a;
+    for (int r = 0; r < 8; ++r) a.src_off[r] = r < rings ? src_off[r] : 0;
+    hipLaunchKernelGGL(window_advance_kernel, dim3(rings + (blocks > 0 ? 1 : 0)), dim3(256), 0, (hipStream_t)stream, ring, work,
+                       src, a, rings, window, elems, k, state, state_src, blocks, block, stride, src_stride);
+    return ss_launch_status();
+}

@@ -20,6 +20,7 @@ captured ONCE into a HIP graph (state lives in static tensors: the rings are shi
 two input copies + one graph launch: the Python / ctypes launch overhead (~1 ms per pair, more than the kernels'
 own time at batch 1) disappears.  `use_graph=False` runs the same code eagerly.
 """
+import collections
 import contextlib
 import os
 import time
@@ -373,6 +374,10 @@ class _Stitcher:
         st = self.static
         return [st[k] for k in _STATE] + ([] if self.meshes_only else [self.watch.wi, self.watch.wf])
 
+    def _drop_graphs(self):
+        """The canvas grew or a net was reloaded: the captured steady-state graphs hold the old canvas / weights by address."""
+        self.graph = None
+
     def _direct(self):
         """Does the steady-state push launch its AVERAGE render itself, outside the graph, on the caller's frames (DIRECT_RENDER)?
         Decided when the stitcher is built."""
@@ -387,10 +392,10 @@ class _Stitcher:
             rows = self.watch.poll()
             if rows:
                 self._regrown(rows)
-                self.graph = None
+                self._drop_graphs()
         if self._stale_trunk():
             self.trunk_pair = None
-            self.graph = None
+            self._drop_graphs()
         self._load(frames, u8)
         if not self.use_graph:
             self._step_static()
@@ -474,6 +479,9 @@ class OnlineStitcher(_Stitcher):
         self.ring_smesh = [[], []]       # last WINDOW spatial meshes per view, each [1,7,9,2]
         self.ring_tsm = [[], []]
         self.ring_hr = []                # HR frames waiting for their smoothed mesh (only until the first window)
+        self._batch = collections.OrderedDict()   # push_many: batch size k -> its work buffers and graph, least recently used first
+        self.graph_nodes_batch = {}      # push_many: nodes of the steady-state graph captured for batch size k (None: not exposed)
+        self.batch_captures = 0          # push_many: graphs captured so far
 
     @torch.no_grad()
     def _render(self, hr1, hr2, mesh1, mesh2, out=None):
@@ -640,6 +648,173 @@ class OnlineStitcher(_Stitcher):
             self._init_static()              # from the next push on: static buffers (+ HIP graph)
             return frames
         return [self._render(hr1, hr2, m1[-1:], m2[-1:])]
+
+    # ------------------------------------------------------------------ k frame pairs of the stream per call
+    @torch.no_grad()
+    def push_many(self, hr1, hr2, lr1, lr2):
+        """k consecutive frame pairs of the stream in one call, 1 <= k <= BATCH_MAX: hr* [k,3,H,W] (0..255), lr* [k,3,360,480]
+        ([-1,1]), fp32 device tensors -> the newly stitched frames [3,Hc,Wc] in stream order: what k calls of `push` return, joined
+        (nothing for the first 6 frames, 7 at the 7th, then one per frame).  The frames of one call are views of one new tensor that
+        no later call writes.  Frames before the first window is complete go through `push` one at a time; the rest of the call runs
+        as ONE batched step (per frame the arithmetic of `push`; the networks see the k frames as one batch), captured into a HIP graph
+        per batch size (BATCH_GRAPHS sizes kept, least recently used dropped).  The canvas is fixed within a call: with
+        grow='recapture' a drift inside one call can crop up to k frames (counted) before the canvas grows at the next call.
+        `push`, `push_u8` and `push_many(_u8)` interleave freely on one stitcher."""
+        k = self._check_many((hr1, hr2, lr1, lr2))
+        _check_shapes('HR frames', (hr1, hr2), ((k, 3, self.h, self.w),))
+        _check_shapes('LR frames', (lr1, lr2), ((k, 3, pipeline.LR_H, pipeline.LR_W),))
+        if any(f.dtype != torch.float32 for f in (hr1, hr2, lr1, lr2)):
+            raise ValueError('push_many takes fp32 frames')
+        hr1, hr2, lr1, lr2 = (f.contiguous() for f in (hr1, hr2, lr1, lr2))
+        with ops.deterministic(self.deterministic):
+            out, i = [], 0
+            while self.static is None and i < k:          # window fill: one pair at a time
+                out += self._push(hr1[i:i + 1], hr2[i:i + 1], lr1[i:i + 1], lr2[i:i + 1])
+                i += 1
+            if i < k:
+                out += self._push_batch(k - i, (hr1[i:], hr2[i:], lr1[i:], lr2[i:]), None)
+            return out
+
+    @torch.no_grad()
+    def push_many_u8(self, frames1, frames2):
+        """k DECODED frame pairs: uint8 [k,H,W,3] device tensors (cv2 layout) -> stitched video frames uint8 [Hc,Wc,3], byte for byte
+        what k calls of `push_u8` return, joined (see push_many)."""
+        k = self._check_many((frames1, frames2))
+        _check_u8('two uint8 [k,H,W,3] tensors', (frames1, frames2), (k, self.h, self.w, 3))
+        frames1, frames2 = frames1.contiguous(), frames2.contiguous()
+        with ops.deterministic(self.deterministic):
+            out, i = [], 0
+            while self.static is None and i < k:
+                out += self.push_u8(frames1[i], frames2[i])
+                i += 1
+            if i < k:
+                out += self._push_batch(k - i, None, (frames1[i:], frames2[i:]))
+            return out
+
+    def _check_many(self, frames):
+        """push_many's refusals that do not depend on the frame type -> k."""
+        if self.meshes_only:
+            raise ValueError('push_many renders frames: not for meshes_only stitchers')
+        if not L.QUAD:
+            raise ValueError('push_many needs the shared regressor launches (SS_QUAD_REGRESSOR=1)')
+        if any(not torch.is_tensor(f) or f.dim() == 0 for f in frames):
+            raise ValueError('push_many takes batched device tensors')
+        k = int(frames[0].shape[0])
+        if any(int(f.shape[0]) != k for f in frames):
+            raise ValueError('push_many: the frame batches differ in length: %s' % [int(f.shape[0]) for f in frames])
+        if not 1 <= k <= BATCH_MAX:
+            raise ValueError('push_many takes 1 to %d frame pairs per call, got %d' % (BATCH_MAX, k))
+        return k
+
+    def _drop_graphs(self):
+        self.graph = None
+        for B in self._batch.values():
+            B['graph'] = None
+
+    def _batch_entry(self, k):
+        """Work buffers (and graph) of batch size k, allocated once; the least recently used size beyond BATCH_GRAPHS is dropped."""
+        B = self._batch.pop(k, None)
+        if B is None:
+            d, e = self.dev, 126
+            fh, fw = pipeline.LR_H // 8, pipeline.LR_W // 8
+            B = {'k': k, 'graph': None, 'deferred': None,
+                 'lr': torch.empty((2, k, 3, pipeline.LR_H, pipeline.LR_W), device=d),     # both views back to back
+                 'feat': torch.empty((2, k + 1, fh, fw, 128), device=d),        # TemporalNet features [view][previous frame, the k frames]
+                 'sw': torch.zeros((2, k + 1, e), device=d),                    # spatial motions [view][previous frame, the k frames]
+                 'tt': torch.zeros((2, k + 1, e), device=d),                    # temporal motions [view][zero, the k frames]
+                 'ts': torch.empty((2, 2 * (k + 1), e), device=d),              # tsmotion's (smesh, tsmotion) rows of both
+                 'work': torch.empty((4, WINDOW - 1 + k, e), device=d)}         # the k sliding windows of the four rings
+        self._batch[k] = B
+        while len(self._batch) > BATCH_GRAPHS:
+            self._batch.popitem(last=False)
+        return B
+
+    def _push_batch(self, k, frames, u8):
+        """k steady-state frame pairs (hr1, hr2, lr1, lr2 [k,...]) or k decoded ones (u8 = (frames1, frames2) [k,H,W,3])."""
+        if self.grow == 'recapture':
+            rows = self.watch.poll()
+            if rows:
+                self._regrown(rows)
+                self._drop_graphs()
+        if self._stale_trunk():
+            self.trunk_pair = None
+            self._drop_graphs()
+        B = self._batch_entry(k)
+        if u8 is not None:                   # the cv2-exact resize writes the step's LR inputs
+            ops.ingest_u8(u8[0], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=B['lr'][0])
+            ops.ingest_u8(u8[1], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=B['lr'][1])
+        else:
+            B['lr'][0].copy_(frames[2])
+            B['lr'][1].copy_(frames[3])
+        if not self.use_graph:
+            self._step_batch(B)
+        else:
+            if B['graph'] is None:
+                (B['graph'],), self.graph_nodes_batch[k] = _capture(self.dev, self._state(), lambda: self._step_batch(B),
+                                                                    [lambda: self._step_batch(B)])
+                self.batch_captures += 1
+            B['graph'].replay()
+        self.frames_in += k
+        if self.grow == 'recapture':
+            self.watch.post_copy()
+        return self._render_batch(B['deferred'], u8 if u8 is not None else frames[:2], u8 is not None)
+
+    def _step_batch(self, B):
+        """k consecutive steady-state frame pairs of the stream from B['lr'] (capturable; the state is read once and left as k
+        `_step_static` runs leave it).  Per frame the launches of `_stage_a` / `_stage_b` at batch k: TemporalNet's pair (t - 1, t)
+        is shifted by one image inside [previous frame, the k frames], tsmotion pairs each row with the one before, the k SmoothNet
+        windows slide over the UNsmoothed work rows.  Ends with the splines, the watcher and the footprints in B['deferred']."""
+        st, k, e = self.static, B['k'], 126
+        F, sw, tt, ts = B['feat'], B['sw'], B['tt'], B['ts']
+        f2 = L.run_stage1_pair([B['lr'][0], B['lr'][1]], self._trunk())          # [2(net), 2k (view-major), 45,60,128]
+        f64 = f2[0]
+        off1 = _heads_a(self.spatial, f64, k)
+        F[:, 0].copy_(st['prev_feat'])
+        F[:, 1:].copy_(f2[1].view(F[:, 1:].shape))
+        cv_s = self.spatial.cv_from_offset1(f64[:k], f64[k:], off1, pipeline.LR_H, pipeline.LR_W)
+        Ff = F.view((2 * (k + 1),) + tuple(F.shape[2:]))
+        cv_t = ops.cost_volume(Ff[:-1], Ff[1:], 3, n=2 * k, split=k, shift=1)     # volume (v, j) = (frame j - 1, frame j) of view v
+        off_ref = torch.empty((k, e), device=self.dev, dtype=torch.float32)
+        off_tgt = torch.empty((k, e), device=self.dev, dtype=torch.float32)
+        L.run_regressor_quad(cv_s, cv_t.view((2, k) + tuple(cv_t.shape[1:])), L.get_quad(self.spatial, self.temporal),
+                             [off_ref, off_tgt, tt[0, 1:], tt[1, 1:]])
+        st['prev_feat'].copy_(F[:, k])
+        ops.spatial_meshes(off1, off_ref, off_tgt, pipeline.LR_H, pipeline.LR_W,
+                           out=(sw[0, 1:].view(k, 7, 9, 2), sw[1, 1:].view(k, 7, 9, 2)))
+        sw[:, 0].copy_(st['pair_s'][:, 0])
+        # tsmotion of both views as ONE batch of 2 (k + 1) rows [view][previous, the k frames]: row j pairs with row j - 1; the
+        # rows of slot 0 are computed and ignored
+        ops.tsmotion(sw.view(2 * (k + 1), 7, 9, 2), tt.view(2 * (k + 1), 7, 9, 2), pipeline.LR_H, pipeline.LR_W, out=(ts[0], ts[1]))
+        # the k windows of every ring in `work`, the rings advanced by k frames, the newest spatial motions made the previous ones
+        n1 = k + 1
+        ops.window_advance(st['ring'], B['work'], ts, [(0 * n1 + 1) * e, (1 * n1 + 1) * e, (2 * n1 + 1) * e, (3 * n1 + 1) * e], k,
+                           state=st['pair_s'], state_src=sw.view(-1)[k * e:], blocks=2, block=e, stride=2 * e, src_stride=n1 * e)
+        wk = B['work'].view(4, WINDOW - 1 + k, 7, 9, 2)
+        outs, _ = self.smooth.run_windows(wk[0], wk[1], wk[2], wk[3], k, WINDOW, 1, 1)
+        m1, m2 = outs['smooth_mesh1'], outs['smooth_mesh2']                      # [k,7,7,9,2]: frame j's mesh is window j's last
+        src, T = ops.stream_splines([m1[0, -1], m2[0, -1]], WINDOW * e, self.bbox, self.nrigid, self.h, self.w, frames=k)
+        guard, wi, wf = self.watch.args()
+        ops.canvas_watch_frames(src, wi, wf, guard)
+        fp = None
+        if self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE:
+            fp = ops.render_footprints(src, T, self.h, self.w, self.hc, self.wc)
+        B['deferred'] = (src, T, fp)
+
+    def _render_batch(self, deferred, imgs, u8):
+        """The batch's frames from the caller's frames imgs ([k,3,H,W] fp32, or [k,H,W,3] uint8 when u8) in one render: AVERAGE with
+        the footprints, LINEAR through the fused clip render (bit-identical per frame to the push's tps_warp_views + linear_blend)."""
+        src, T, fp = deferred
+        views = [f.contiguous() for f in imgs]
+        if self.fusion_mode == 'AVERAGE':
+            render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
+            out = render(views, src, T, self.hc, self.wc, self.warp_mode, footprint=fp)
+        else:
+            out = ops.render_linear_clip(views, src, T, self.hc, self.wc, self.warp_mode)
+        return list(out.unbind(0))
+
+
+BATCH_MAX = 32                         # OnlineStitcher.push_many: frame pairs per call
+BATCH_GRAPHS = 4                       # batch sizes whose steady-state graphs (and work buffers) push_many keeps
 
 
 # Steady-state AVERAGE render OUTSIDE the captured graph, on the caller's own HR frames and into a fresh tensor: the graph ends with the
@@ -831,6 +1006,12 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
         OnlineStitcher.__init__(self, nets, height, width, canvas, margin, warp_mode, fusion_mode, use_graph=True, grow='never',
                                 meshes_only=False, deterministic=deterministic)
         self._pipe_init()
+
+    def push_many(self, *frames):
+        raise ValueError('PipelinedOnlineStitcher has no push_many: use OnlineStitcher.push_many')
+
+    def push_many_u8(self, *frames):
+        raise ValueError('PipelinedOnlineStitcher has no push_many_u8: use OnlineStitcher.push_many_u8')
 
     def _pipe_alloc(self):
         d = self.dev

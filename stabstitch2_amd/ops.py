@@ -584,21 +584,29 @@ def l2norm(x):
     return out
 
 
-def cost_volume(x1, x2, r, out=None, chain=0):
+def cost_volume(x1, x2, r, out=None, chain=0, n=None, split=0, shift=0):
     """nhwc in -> nhwc [n,h,w,pad4((2r+1)^2)] (padding channels are zero).
     chain = S > 0: x1 / x2 hold the S + 1 views of a chain of S pairs ONCE; -> the 2 S volumes [first views | second views] of the
-    pairs (ss_cost_volume_shifted), equal to the volumes of cat(x[:S], x[1:])."""
-    n, h, w, c = x1.shape
+    pairs (ss_cost_volume_shifted), equal to the volumes of cat(x[:S], x[1:]).
+    n volumes with split / shift (ss_cost_volume_shifted): volume b reads image b + (b >= split ? shift : 0) of x1 and x2 (k frames of
+    one stream: x1 = the [2 views][k + 1] features, x2 the same one image further, split = k, shift = 1)."""
     d = (2 * r + 1) ** 2
     cs = ((d + 3) // 4) * 4
+    images, h, w, c = x1.shape
+    shifted = n is not None
     if chain:
-        assert n == chain + 1 and tuple(x2.shape) == tuple(x1.shape)
-        n = 2 * chain
+        assert not shifted and images == chain + 1 and tuple(x2.shape) == tuple(x1.shape)
+        n, split, shift = 2 * chain, chain, 1 - chain
+    elif shifted:
+        assert 0 <= split and 0 <= split + shift and tuple(x2.shape) == tuple(x1.shape)
+        assert max(min(split, n) - 1, n - 1 + (shift if n > split else 0)) < images, 'cost_volume: a shifted volume reads past the inputs'
+    else:
+        n = images
     if out is None:
         out = torch.empty((n, h, w, cs), device=x1.device, dtype=torch.float32)
     assert tuple(out.shape) == (n, h, w, cs)
-    if chain:
-        H.call('ss_cost_volume_shifted', H.dptr(x1), H.dptr(x2), H.dptr(out), n, h, w, c, r, cs, chain, 1 - chain, H.stream())
+    if chain or shifted:
+        H.call('ss_cost_volume_shifted', H.dptr(x1), H.dptr(x2), H.dptr(out), n, h, w, c, r, cs, split, shift, H.stream())
     else:
         H.call('ss_cost_volume', H.dptr(x1), H.dptr(x2), H.dptr(out), n, h, w, c, r, cs, H.stream())
     return out
@@ -766,6 +774,24 @@ def window_push(ring, src, src_off, state=None, blocks=0, block=0, stride=0, del
     H.call('ss_window_push_groups', H.dptr(ring), H.dptr(src), ctypes.cast(offs, ctypes.c_void_p), r, per, w, e,
            H.dptr(state, True), blocks, block, stride, delta, H.stream())
     return ring
+
+
+def window_advance(ring, work, src, src_off, k, state=None, state_src=None, blocks=0, block=0, stride=0, src_stride=0):
+    """k frames of one stream (ss_window_advance): ring [R,W,...] and work [R,W-1+k,...] (contiguous) -- work[r] <- ring[r] rows
+    1..W-1 then the k rows at src.flatten()[src_off[r] + j * E:][:E]; ring[r] <- the last W rows of work[r]; in the same launch
+    `blocks` blocks of `block` floats: state.flatten()[b * stride:][:block] <- state_src.flatten()[b * src_stride:][:block]."""
+    r, w = ring.shape[0], ring.shape[1]
+    e = ring[0, 0].numel()
+    assert ring.is_contiguous() and work.is_contiguous() and src.is_contiguous() and len(src_off) == r
+    assert tuple(work.shape[:2]) == (r, w - 1 + k) and work[0, 0].numel() == e
+    assert all(0 <= o and o + k * e <= src.numel() for o in src_off)
+    if blocks:
+        assert state.is_contiguous() and state_src.is_contiguous()
+        assert (blocks - 1) * stride + block <= state.numel() and (blocks - 1) * src_stride + block <= state_src.numel()
+    offs = (ctypes.c_longlong * r)(*src_off)
+    H.call('ss_window_advance', H.dptr(ring), H.dptr(work), H.dptr(src), ctypes.cast(offs, ctypes.c_void_p), r, w, e, int(k),
+           H.dptr(state, True), H.dptr(state_src, True), blocks, block, stride, src_stride, H.stream())
+    return work
 
 
 # ------------------------------------------------------------------ render
@@ -1018,6 +1044,14 @@ def canvas_watch(src, watch_i, watch_f, guard):
     H.call('ss_canvas_watch', H.dptr(src), s, v, float(guard), H.dptr(watch_i, dtype=torch.int32), H.dptr(watch_f), H.stream())
 
 
+def canvas_watch_frames(src, watch_i, watch_f, guard):
+    """src [k,V,63,2] canvas-normalised control points of k consecutive frames of ONE stream -> its watcher row watch_i [1,4] /
+    watch_f [1,4] updated frame by frame (ss_canvas_watch_frames; equal to k canvas_watch calls)."""
+    k, v = src.shape[0], src.shape[1]
+    assert src.is_contiguous() and tuple(watch_i.shape) == (1, 4) and tuple(watch_f.shape) == (1, 4)
+    H.call('ss_canvas_watch_frames', H.dptr(src), k, v, float(guard), H.dptr(watch_i, dtype=torch.int32), H.dptr(watch_f), H.stream())
+
+
 def stream_normalize_watch(meshes, frame_stride, bboxes, img_h, img_w, guard=0.0, watch_i=None, watch_f=None):
     """One push's render control points of all views + the overflow watcher in ONE launch: meshes = V tensors whose stream s starts
     `frame_stride` floats after stream s - 1; bboxes [4] (one canvas) or [S,4] (a canvas per stream) -> [S,V,63,2]; equal, bit for
@@ -1033,12 +1067,16 @@ def stream_normalize_watch(meshes, frame_stride, bboxes, img_h, img_w, guard=0.0
     return out
 
 
-def stream_splines(meshes, frame_stride, bboxes, nrigid, img_h, img_w):
+def stream_splines(meshes, frame_stride, bboxes, nrigid, img_h, img_w, frames=None):
     """One push's render control points AND their splines in ONE launch (ss_stream_splines): arguments as stream_normalize_watch
     -> (src [S,V,63,2], T [S,V,2,66]), equal bit for bit to stream_normalize_watch + tps_solve_shared.  The overflow watcher is not
-    touched: render_footprints(..., watch=...) or canvas_watch(src, ...)."""
+    touched: render_footprints(..., watch=...) or canvas_watch(src, ...).
+    frames = k with ONE canvas bboxes [4]: k frames of one stream on it (frame i's meshes i * frame_stride floats further) -> [k,...]."""
     v = len(meshes)
     s = 1 if bboxes.dim() == 1 else bboxes.shape[0]
+    if frames is not None:
+        assert bboxes.dim() == 1 and frames >= 1
+        s = int(frames)
     for m in meshes:
         assert m.is_contiguous() and m.dtype == torch.float32
     assert nrigid.numel() == 126 and nrigid.is_contiguous()
