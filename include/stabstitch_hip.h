@@ -204,6 +204,13 @@ SS_API int ss_cost_volume_bidir(const float* x1, const float* x2, float* out, in
  * views] with split = S, shift = 1 - S (temporal_network.py:120-147 per view). */
 SS_API int ss_cost_volume_shifted(const float* x1, const float* x2, float* out, int n, int h, int w, int c, int r, int out_cs,
                                   int split, int shift, void* stream);
+/* The temporal cost volumes of a chain of `views` >= 2 views over k consecutive frames (1 <= k <= 32; a three-view stream's k frame
+ * triples per call, ThreeViewOnlineStitcher.push_many) in ONE launch from the features stored once: x [views][k + 1][h][w][c]
+ * (slot 0 = each view's previous frame) -> out [2][views - 1][k][h][w][out_cs], the volumes [first views | second views] of the
+ * views - 1 pairs, pair-major, frame-minor: volume (hh, s, j) = ss_cost_volume(x[s + hh][j], x[s + hh][j + 1], r) (TemporalNet's
+ * cost volume of frames j - 1 and j, temporal_network.py:120-174), bit for bit.  r = 3 or 5, c % 4 == 0, out_cs >= (2r+1)^2. */
+SS_API int ss_cost_volume_chain_frames(const float* x, float* out, int views, int k, int h, int w, int c, int r, int out_cs,
+                                       void* stream);
 /* tile height of the cost-volume kernel (spatial_network.py:333-358; process-wide A/B knob): 0 = the library's choice, 4 or 8 output rows x 16 columns per
  * workgroup; identical results. */
 SS_API int ss_cost_volume_set_tile(int ty);

@@ -21,7 +21,7 @@ extern "C" int ss_conv_nhwc(const float*, const float*, const float*, const floa
 template <int R, int CV_TY>
 __global__ __launch_bounds__(64 * ((4 * CV_TY * (2 * R + 1) + 63) / 64)) void cost_volume_kernel(
     const float* __restrict__ x1, const float* __restrict__ x2, float* __restrict__ out, int h, int w, int c,
-    int out_cs, int n_fwd, int n_img, int tiles_x, int tiles_y, int split, int shift) {
+    int out_cs, int n_fwd, int n_img, int tiles_x, int tiles_y, int split, int shift, int group) {
     constexpr int KD = 2 * R + 1;
     constexpr int D = KD * KD;
     constexpr int PG = 4 * CV_TY;                      // threads per displacement row: CV_TY rows x 4 pixel quads
@@ -76,8 +76,10 @@ __global__ __launch_bounds__(64 * ((4 * CV_TY * (2 * R + 1) + 63) / 64)) void co
     const int py = pg >> 2, g4 = (pg & 3) * 4;
     // (Eight lanes of a 16-byte read = the four g4 of two ADJACENT window rows.  Round 3 tried a lane map that pairs rows half a
     // bank cycle apart -- 256 threads with 80 idle lanes at R = 5: slower.  Round 4 rotates the odd rows' chunks instead, above.)
-    // volume n reads image n + (n >= split ? shift : 0) of both inputs (a chain of pairs stores every view once: ss_cost_volume_shifted)
-    const int ni = n + (n >= split ? shift : 0);
+    // volume n reads image n + n / group + (n >= split ? shift : 0) of both inputs (a chain of pairs stores every view once:
+    // ss_cost_volume_shifted, group >= n; k frames of every view of a chain: ss_cost_volume_chain_frames, group = k).  n is uniform
+    // over the workgroup: the division is scalar, once per workgroup.
+    const int ni = n + n / group + (n >= split ? shift : 0);
     const float* x1n = x1 + (long long)ni * h * w * c;
     const float* x2n = x2 + (long long)ni * h * w * c;
 
@@ -256,7 +258,7 @@ extern "C" int ss_cost_volume_set_tile(int ty) {
 }
 
 static int cv_launch(const float* x1, const float* x2, float* out, int n_fwd, int n_img, int h, int w, int c, int r, int out_cs,
-                     hipStream_t st, int split = 1 << 30, int shift = 0) {
+                     hipStream_t st, int split = 1 << 30, int shift = 0, int group = 1 << 30) {
     if (r != 5 && r != 3) return SS_ERR_UNSUPPORTED;
     // measured (tools/bench_cv.py, 32 / 62 pairs): R = 5: 93-106 us at TY 4, 119-128 at TY 8; R = 3: 91 at TY 4, 79 at TY 8
     const int TY = g_cv_ty ? g_cv_ty : (r == 3 ? 8 : CV_DEFAULT_TY);
@@ -264,11 +266,11 @@ static int cv_launch(const float* x1, const float* x2, float* out, int n_fwd, in
     if ((long long)tx * ty * n_img > (1ll << 30)) return SS_ERR_UNSUPPORTED;
     dim3 g(8 * ss_cdiv((long long)tx * ty * n_img, 8));
     if (TY == 8) {
-        if (r == 5) hipLaunchKernelGGL((cost_volume_kernel<5, 8>), g, dim3(384), 0, st, x1, x2, out, h, w, c, out_cs, n_fwd, n_img, tx, ty, split, shift);
-        else hipLaunchKernelGGL((cost_volume_kernel<3, 8>), g, dim3(256), 0, st, x1, x2, out, h, w, c, out_cs, n_fwd, n_img, tx, ty, split, shift);
+        if (r == 5) hipLaunchKernelGGL((cost_volume_kernel<5, 8>), g, dim3(384), 0, st, x1, x2, out, h, w, c, out_cs, n_fwd, n_img, tx, ty, split, shift, group);
+        else hipLaunchKernelGGL((cost_volume_kernel<3, 8>), g, dim3(256), 0, st, x1, x2, out, h, w, c, out_cs, n_fwd, n_img, tx, ty, split, shift, group);
     } else {
-        if (r == 5) hipLaunchKernelGGL((cost_volume_kernel<5, 4>), g, dim3(192), 0, st, x1, x2, out, h, w, c, out_cs, n_fwd, n_img, tx, ty, split, shift);
-        else hipLaunchKernelGGL((cost_volume_kernel<3, 4>), g, dim3(128), 0, st, x1, x2, out, h, w, c, out_cs, n_fwd, n_img, tx, ty, split, shift);
+        if (r == 5) hipLaunchKernelGGL((cost_volume_kernel<5, 4>), g, dim3(192), 0, st, x1, x2, out, h, w, c, out_cs, n_fwd, n_img, tx, ty, split, shift, group);
+        else hipLaunchKernelGGL((cost_volume_kernel<3, 4>), g, dim3(128), 0, st, x1, x2, out, h, w, c, out_cs, n_fwd, n_img, tx, ty, split, shift, group);
     }
     return ss_launch_status();
 }
@@ -290,6 +292,27 @@ extern "C" int ss_cost_volume_shifted(const float* x1, const float* x2, float* o
     int D = (2 * r + 1) * (2 * r + 1);
     if (out_cs < D) return SS_ERR_ARG;
     return cv_launch(x1, x2, out, n, n, h, w, c, r, out_cs, (hipStream_t)stream, split, shift);
+}
+
+// The temporal cost volumes of a chain of `views` views over k consecutive frames in ONE launch, from features stored once:
+// x [views][k + 1][h][w][c] (slot 0 = each view's previous frame) -> out [2][views - 1][k] volumes [first views | second views] of
+// the views - 1 pairs, pair-major, frame-minor: volume (hh, s, j) = cv(x[s + hh][j], x[s + hh][j + 1]) (temporal_network.py:120-174
+// per view and frame).  Volume b = (hh (views - 1) + s) k + j reads image (s + hh)(k + 1) + j of x and the image after it:
+// b + b / k + (b >= (views - 1) k ? (2 - views)(k + 1) : 0).  Per volume the kernel body of ss_cost_volume.
+extern "C" int ss_cost_volume_chain_frames(const float* x, float* out, int views, int k, int h, int w, int c, int r, int out_cs,
+                                           void* stream) {
+    if (!x || !out || views < 2 || k < 1 || k > 32 || h <= 0 || w <= 0 || c <= 0 || (c & 3)) return SS_ERR_ARG;
+    if (r != 3 && r != 5) return SS_ERR_ARG;
+    const int D = (2 * r + 1) * (2 * r + 1);
+    if (out_cs < D) return SS_ERR_ARG;
+    // grid: one workgroup per 16-column tile of (at least) 4 rows of every volume; 32-bit volume indices and offsets in an image
+    const long long n = 2ll * (views - 1) * k;
+    if ((long long)views * (k + 1) > (1ll << 24) || (long long)h * w * c >= (1ll << 31) ||
+        (long long)ss_cdiv(w, CV_TX) * ss_cdiv(h, CV_DEFAULT_TY) * n > (1ll << 30))
+        return SS_ERR_ARG;
+    const int pairs = views - 1;
+    return cv_launch(x, x + (long long)h * w * c, out, (int)n, (int)n, h, w, c, r, out_cs, (hipStream_t)stream, pairs * k,
+                     (1 - pairs) * (k + 1), k);
 }
 
 // both directions in ONE launch: out [2][n][h][w][out_cs] = cv(x1, x2), cv(x2, x1)

@@ -101,8 +101,10 @@ def _spatial_temporal_heads(spatial, temporal, f64, prev_feat, feat, b, tm_out, 
 
 def _heads_a(spatial, f64, b, chain=False):
     """First half of the heads (up to the global homography offsets): SpatialNet's stage-2 trunk + contextual correlation +
-    regressNet1 -> offset_1 [b,8].  (PipelinedOnlineStitcher cuts the push between the halves.)"""
-    o2 = 1 if chain else b
+    regressNet1 -> offset_1 [b,8].  (PipelinedOnlineStitcher cuts the push between the halves.)
+    chain: True -- pair i = images (i, i + 1) of f64 (a chain of views); an int o -- pair i = images (i, i + o) (a chain of views
+    holding o frames each, view-major: ThreeViewOnlineStitcher.push_many); False -- pair i = images (i, i + b)."""
+    o2 = (1 if chain is True else int(chain)) if chain else b
     f32 = L.run_stage2(f64, spatial._prepared()['s2'])
     return spatial.offset1_from_features(f32[:b], f32[o2:o2 + b])
 
@@ -322,6 +324,9 @@ class _Stitcher:
         self.trunk_pair = None
         self.trunk_versions = None
         self.frames_in = 0
+        self._batch = collections.OrderedDict()   # push_many: batch size k -> its work buffers and graph, least recently used first
+        self.graph_nodes_batch = {}      # push_many: nodes of the steady-state graph captured for batch size k (None: not exposed)
+        self.batch_captures = 0          # push_many: graphs captured so far
 
     # ------------------------------------------------------------------ canvas overflow
     def overflow_report(self):
@@ -377,6 +382,8 @@ class _Stitcher:
     def _drop_graphs(self):
         """The canvas grew or a net was reloaded: the captured steady-state graphs hold the old canvas / weights by address."""
         self.graph = None
+        for B in self._batch.values():
+            B['graph'] = None
 
     def _direct(self):
         """Does the steady-state push launch its AVERAGE render itself, outside the graph, on the caller's frames (DIRECT_RENDER)?
@@ -386,8 +393,9 @@ class _Stitcher:
     def _u8_steady(self):
         return self.static is not None and self._direct() and self._U8_STEADY
 
-    def _push_static(self, *frames, u8=None):
-        """One steady-state push: frames = its HR frames then its LR frames, or u8 = its decoded uint8 frames (push_u8)."""
+    def _refresh(self):
+        """Start of a steady-state push or batch: the watcher's growth check (grow='recapture'), then the weights check; either drops
+        the captured graphs."""
         if self.grow == 'recapture' and not self.meshes_only:
             rows = self.watch.poll()
             if rows:
@@ -396,6 +404,10 @@ class _Stitcher:
         if self._stale_trunk():
             self.trunk_pair = None
             self._drop_graphs()
+
+    def _push_static(self, *frames, u8=None):
+        """One steady-state push: frames = its HR frames then its LR frames, or u8 = its decoded uint8 frames (push_u8)."""
+        self._refresh()
         self._load(frames, u8)
         if not self.use_graph:
             self._step_static()
@@ -456,6 +468,102 @@ class _Stitcher:
         shp = (1, 3, self.h, self.w)
         return [ops.render_average([f.reshape(shp) for f in imgs], src, T, self.hc, self.wc, self.warp_mode, footprint=fp)]
 
+    # ------------------------------------------------------------------ k frames of every view per call (one canvas)
+    # A subclass provides _push (one plain push), push_u8, _batch_buffers (the per-k work buffers, 'lr' [V,k,3,360,480] among
+    # them) and _step_batch (the capturable batched step, leaving (src, T, footprints) in B['deferred']).
+    def _push_many(self, frames):
+        """push_many of V views: frames = the V HR batches [k,3,H,W] then the V LR batches [k,3,360,480]."""
+        k = self._check_many(frames)
+        v = len(frames) // 2
+        _check_shapes('HR frames', frames[:v], ((k, 3, self.h, self.w),))
+        _check_shapes('LR frames', frames[v:], ((k, 3, pipeline.LR_H, pipeline.LR_W),))
+        if any(f.dtype != torch.float32 for f in frames):
+            raise ValueError('push_many takes fp32 frames')
+        frames = tuple(f.contiguous() for f in frames)
+        with ops.deterministic(self.deterministic):
+            out, i = [], 0
+            while self.static is None and i < k:          # window fill: one frame of every view at a time
+                out += self._push(*[f[i:i + 1] for f in frames])
+                i += 1
+            if i < k:
+                out += self._push_batch(k - i, tuple(f[i:] for f in frames), None)
+            return out
+
+    def _push_many_u8(self, frames):
+        """push_many_u8 of V views: frames = the V decoded uint8 batches [k,H,W,3]."""
+        k = self._check_many(frames)
+        _check_u8('%d uint8 [k,H,W,3] tensors' % len(frames), frames, (k, self.h, self.w, 3))
+        frames = tuple(f.contiguous() for f in frames)
+        with ops.deterministic(self.deterministic):
+            out, i = [], 0
+            while self.static is None and i < k:
+                out += self.push_u8(*[f[i] for f in frames])
+                i += 1
+            if i < k:
+                out += self._push_batch(k - i, None, tuple(f[i:] for f in frames))
+            return out
+
+    def _check_many(self, frames):
+        """push_many's refusals that do not depend on the frame type -> k."""
+        if self.meshes_only:
+            raise ValueError('push_many renders frames: not for meshes_only stitchers')
+        if not L.QUAD:
+            raise ValueError('push_many needs the shared regressor launches (SS_QUAD_REGRESSOR=1)')
+        if any(not torch.is_tensor(f) or f.dim() == 0 for f in frames):
+            raise ValueError('push_many takes batched device tensors')
+        k = int(frames[0].shape[0])
+        if any(int(f.shape[0]) != k for f in frames):
+            raise ValueError('push_many: the frame batches differ in length: %s' % [int(f.shape[0]) for f in frames])
+        if not 1 <= k <= BATCH_MAX:
+            raise ValueError('push_many takes 1 to %d frames of every view per call, got %d' % (BATCH_MAX, k))
+        return k
+
+    def _batch_entry(self, k):
+        """Work buffers (and graph) of batch size k, allocated once; the least recently used size beyond BATCH_GRAPHS is dropped."""
+        B = self._batch.pop(k, None)
+        if B is None:
+            B = dict(self._batch_buffers(k), k=k, graph=None, deferred=None)
+        self._batch[k] = B
+        while len(self._batch) > BATCH_GRAPHS:
+            self._batch.popitem(last=False)
+        return B
+
+    def _push_batch(self, k, frames, u8):
+        """k steady-state frames of every view: frames = (V HR batches, V LR batches) [k,...], or u8 = V decoded batches [k,H,W,3]."""
+        self._refresh()
+        B = self._batch_entry(k)
+        views = len(u8) if u8 is not None else len(frames) // 2
+        for v in range(views):
+            if u8 is not None:               # the cv2-exact resize writes the step's LR inputs
+                ops.ingest_u8(u8[v], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=B['lr'][v])
+            else:
+                B['lr'][v].copy_(frames[views + v])
+        if not self.use_graph:
+            self._step_batch(B)
+        else:
+            if B['graph'] is None:
+                (B['graph'],), self.graph_nodes_batch[k] = _capture(self.dev, self._state(), lambda: self._step_batch(B),
+                                                                    [lambda: self._step_batch(B)])
+                self.batch_captures += 1
+            B['graph'].replay()
+        self.frames_in += k
+        if self.grow == 'recapture':
+            self.watch.post_copy()
+        return self._render_batch(B['deferred'], u8 if u8 is not None else frames[:views], u8 is not None)
+
+    def _render_batch(self, deferred, imgs, u8):
+        """The batch's frames from the caller's frames imgs (V x [k,3,H,W] fp32, or [k,H,W,3] uint8 when u8) in one render: AVERAGE
+        with the footprints, LINEAR through the fused clip render (bit-identical per frame to the push's tps_warp_views +
+        linear_blend)."""
+        src, T, fp = deferred
+        views = [f.contiguous() for f in imgs]
+        if self.fusion_mode == 'AVERAGE':
+            render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
+            out = render(views, src, T, self.hc, self.wc, self.warp_mode, footprint=fp)
+        else:
+            out = ops.render_linear_clip(views, src, T, self.hc, self.wc, self.warp_mode)
+        return list(out.unbind(0))
+
 
 class OnlineStitcher(_Stitcher):
     def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
@@ -479,9 +587,6 @@ class OnlineStitcher(_Stitcher):
         self.ring_smesh = [[], []]       # last WINDOW spatial meshes per view, each [1,7,9,2]
         self.ring_tsm = [[], []]
         self.ring_hr = []                # HR frames waiting for their smoothed mesh (only until the first window)
-        self._batch = collections.OrderedDict()   # push_many: batch size k -> its work buffers and graph, least recently used first
-        self.graph_nodes_batch = {}      # push_many: nodes of the steady-state graph captured for batch size k (None: not exposed)
-        self.batch_captures = 0          # push_many: graphs captured so far
 
     @torch.no_grad()
     def _render(self, hr1, hr2, mesh1, mesh2, out=None):
@@ -660,104 +765,23 @@ class OnlineStitcher(_Stitcher):
         per batch size (BATCH_GRAPHS sizes kept, least recently used dropped).  The canvas is fixed within a call: with
         grow='recapture' a drift inside one call can crop up to k frames (counted) before the canvas grows at the next call.
         `push`, `push_u8` and `push_many(_u8)` interleave freely on one stitcher."""
-        k = self._check_many((hr1, hr2, lr1, lr2))
-        _check_shapes('HR frames', (hr1, hr2), ((k, 3, self.h, self.w),))
-        _check_shapes('LR frames', (lr1, lr2), ((k, 3, pipeline.LR_H, pipeline.LR_W),))
-        if any(f.dtype != torch.float32 for f in (hr1, hr2, lr1, lr2)):
-            raise ValueError('push_many takes fp32 frames')
-        hr1, hr2, lr1, lr2 = (f.contiguous() for f in (hr1, hr2, lr1, lr2))
-        with ops.deterministic(self.deterministic):
-            out, i = [], 0
-            while self.static is None and i < k:          # window fill: one pair at a time
-                out += self._push(hr1[i:i + 1], hr2[i:i + 1], lr1[i:i + 1], lr2[i:i + 1])
-                i += 1
-            if i < k:
-                out += self._push_batch(k - i, (hr1[i:], hr2[i:], lr1[i:], lr2[i:]), None)
-            return out
+        return self._push_many((hr1, hr2, lr1, lr2))
 
     @torch.no_grad()
     def push_many_u8(self, frames1, frames2):
         """k DECODED frame pairs: uint8 [k,H,W,3] device tensors (cv2 layout) -> stitched video frames uint8 [Hc,Wc,3], byte for byte
         what k calls of `push_u8` return, joined (see push_many)."""
-        k = self._check_many((frames1, frames2))
-        _check_u8('two uint8 [k,H,W,3] tensors', (frames1, frames2), (k, self.h, self.w, 3))
-        frames1, frames2 = frames1.contiguous(), frames2.contiguous()
-        with ops.deterministic(self.deterministic):
-            out, i = [], 0
-            while self.static is None and i < k:
-                out += self.push_u8(frames1[i], frames2[i])
-                i += 1
-            if i < k:
-                out += self._push_batch(k - i, None, (frames1[i:], frames2[i:]))
-            return out
+        return self._push_many_u8((frames1, frames2))
 
-    def _check_many(self, frames):
-        """push_many's refusals that do not depend on the frame type -> k."""
-        if self.meshes_only:
-            raise ValueError('push_many renders frames: not for meshes_only stitchers')
-        if not L.QUAD:
-            raise ValueError('push_many needs the shared regressor launches (SS_QUAD_REGRESSOR=1)')
-        if any(not torch.is_tensor(f) or f.dim() == 0 for f in frames):
-            raise ValueError('push_many takes batched device tensors')
-        k = int(frames[0].shape[0])
-        if any(int(f.shape[0]) != k for f in frames):
-            raise ValueError('push_many: the frame batches differ in length: %s' % [int(f.shape[0]) for f in frames])
-        if not 1 <= k <= BATCH_MAX:
-            raise ValueError('push_many takes 1 to %d frame pairs per call, got %d' % (BATCH_MAX, k))
-        return k
-
-    def _drop_graphs(self):
-        self.graph = None
-        for B in self._batch.values():
-            B['graph'] = None
-
-    def _batch_entry(self, k):
-        """Work buffers (and graph) of batch size k, allocated once; the least recently used size beyond BATCH_GRAPHS is dropped."""
-        B = self._batch.pop(k, None)
-        if B is None:
-            d, e = self.dev, 126
-            fh, fw = pipeline.LR_H // 8, pipeline.LR_W // 8
-            B = {'k': k, 'graph': None, 'deferred': None,
-                 'lr': torch.empty((2, k, 3, pipeline.LR_H, pipeline.LR_W), device=d),     # both views back to back
-                 'feat': torch.empty((2, k + 1, fh, fw, 128), device=d),        # TemporalNet features [view][previous frame, the k frames]
-                 'sw': torch.zeros((2, k + 1, e), device=d),                    # spatial motions [view][previous frame, the k frames]
-                 'tt': torch.zeros((2, k + 1, e), device=d),                    # temporal motions [view][zero, the k frames]
-                 'ts': torch.empty((2, 2 * (k + 1), e), device=d),              # tsmotion's (smesh, tsmotion) rows of both
-                 'work': torch.empty((4, WINDOW - 1 + k, e), device=d)}         # the k sliding windows of the four rings
-        self._batch[k] = B
-        while len(self._batch) > BATCH_GRAPHS:
-            self._batch.popitem(last=False)
-        return B
-
-    def _push_batch(self, k, frames, u8):
-        """k steady-state frame pairs (hr1, hr2, lr1, lr2 [k,...]) or k decoded ones (u8 = (frames1, frames2) [k,H,W,3])."""
-        if self.grow == 'recapture':
-            rows = self.watch.poll()
-            if rows:
-                self._regrown(rows)
-                self._drop_graphs()
-        if self._stale_trunk():
-            self.trunk_pair = None
-            self._drop_graphs()
-        B = self._batch_entry(k)
-        if u8 is not None:                   # the cv2-exact resize writes the step's LR inputs
-            ops.ingest_u8(u8[0], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=B['lr'][0])
-            ops.ingest_u8(u8[1], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=B['lr'][1])
-        else:
-            B['lr'][0].copy_(frames[2])
-            B['lr'][1].copy_(frames[3])
-        if not self.use_graph:
-            self._step_batch(B)
-        else:
-            if B['graph'] is None:
-                (B['graph'],), self.graph_nodes_batch[k] = _capture(self.dev, self._state(), lambda: self._step_batch(B),
-                                                                    [lambda: self._step_batch(B)])
-                self.batch_captures += 1
-            B['graph'].replay()
-        self.frames_in += k
-        if self.grow == 'recapture':
-            self.watch.post_copy()
-        return self._render_batch(B['deferred'], u8 if u8 is not None else frames[:2], u8 is not None)
+    def _batch_buffers(self, k):
+        d, e = self.dev, 126
+        fh, fw = pipeline.LR_H // 8, pipeline.LR_W // 8
+        return {'lr': torch.empty((2, k, 3, pipeline.LR_H, pipeline.LR_W), device=d),     # both views back to back
+                'feat': torch.empty((2, k + 1, fh, fw, 128), device=d),        # TemporalNet features [view][previous frame, the k frames]
+                'sw': torch.zeros((2, k + 1, e), device=d),                    # spatial motions [view][previous frame, the k frames]
+                'tt': torch.zeros((2, k + 1, e), device=d),                    # temporal motions [view][zero, the k frames]
+                'ts': torch.empty((2, 2 * (k + 1), e), device=d),              # tsmotion's (smesh, tsmotion) rows of both
+                'work': torch.empty((4, WINDOW - 1 + k, e), device=d)}         # the k sliding windows of the four rings
 
     def _step_batch(self, B):
         """k consecutive steady-state frame pairs of the stream from B['lr'] (capturable; the state is read once and left as k
@@ -800,20 +824,8 @@ class OnlineStitcher(_Stitcher):
             fp = ops.render_footprints(src, T, self.h, self.w, self.hc, self.wc)
         B['deferred'] = (src, T, fp)
 
-    def _render_batch(self, deferred, imgs, u8):
-        """The batch's frames from the caller's frames imgs ([k,3,H,W] fp32, or [k,H,W,3] uint8 when u8) in one render: AVERAGE with
-        the footprints, LINEAR through the fused clip render (bit-identical per frame to the push's tps_warp_views + linear_blend)."""
-        src, T, fp = deferred
-        views = [f.contiguous() for f in imgs]
-        if self.fusion_mode == 'AVERAGE':
-            render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
-            out = render(views, src, T, self.hc, self.wc, self.warp_mode, footprint=fp)
-        else:
-            out = ops.render_linear_clip(views, src, T, self.hc, self.wc, self.warp_mode)
-        return list(out.unbind(0))
 
-
-BATCH_MAX = 32                         # OnlineStitcher.push_many: frame pairs per call
+BATCH_MAX = 32                         # push_many: frames of every view per call
 BATCH_GRAPHS = 4                       # batch sizes whose steady-state graphs (and work buffers) push_many keeps
 
 
@@ -1386,15 +1398,19 @@ class ThreeViewOnlineStitcher(_Stitcher):
         for frame in st.push(hr1, hr2, hr3, lr1, lr2, lr3): ...      # [], ..., 7 frames on the 7th push, then 1: [3,Hc,Wc] fp32
 
     Overflow of the fixed output canvas is watched as in OnlineStitcher (`clipped_frames`, `overflow_report()`); grow='recapture'
-    re-fixes the OUTPUT canvas (and captures the graph again) when a mesh comes within half the margin of its edge."""
+    re-fixes the OUTPUT canvas (and captures the graph again) when a mesh comes within half the margin of its edge.
+    `push_many` / `push_many_u8` take k consecutive triples per call (see OnlineStitcher.push_many)."""
 
     def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 use_graph=True, grow='never'):
+                 use_graph=True, grow='never', deterministic=False):
+        """deterministic: every push under the conv engine's geometry-only kernel policy (ops.deterministic; as OnlineStitcher's):
+        push_many's frames then equal single pushes' bit for bit."""
         # the two pair chains as a batch of two streams over the CHAIN of three views: every launch serves both pairs, view 2's
         # trunk features are computed once
         self.chains = MultiOnlineStitcher(nets, height, width, streams=2, margin=margin, warp_mode=warp_mode, fusion_mode=fusion_mode,
-                                          use_graph=False, meshes_only=True, chain=True)
+                                          use_graph=False, meshes_only=True, deterministic=deterministic, chain=True)
         _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow)
+        self.deterministic = bool(deterministic)
         box = lambda b: None if b is None else torch.tensor(b, dtype=torch.float32, device=self.dev)
         self.bbox, self.first_canvas = box(canvas), box(first_canvas)
         self.hc = self.wc = None
@@ -1462,11 +1478,12 @@ class ThreeViewOnlineStitcher(_Stitcher):
         byte ops.ingest_u8 -> push -> ops.canvas_to_u8 (see OnlineStitcher.push_u8)."""
         imgs = (img1, img2, img3)
         _check_u8('three uint8 [H,W,3] frames', imgs, (self.h, self.w, 3))
-        if self._u8_steady():
-            return self._push_static(u8=tuple(i.contiguous() for i in imgs))
-        hr, lr = ops.ingest_u8(torch.stack(imgs, 0), pipeline.LR_H, pipeline.LR_W)
-        frames = self.push(hr[0:1], hr[1:2], hr[2:3], lr[0:1], lr[1:2], lr[2:3])
-        return [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
+        with ops.deterministic(self.deterministic):
+            if self._u8_steady():
+                return self._push_static(u8=tuple(i.contiguous() for i in imgs))
+            hr, lr = ops.ingest_u8(torch.stack(imgs, 0), pipeline.LR_H, pipeline.LR_W)
+            frames = self.push(hr[0:1], hr[1:2], hr[2:3], lr[0:1], lr[1:2], lr[2:3])
+            return [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
 
     @torch.no_grad()
     def push(self, hr1, hr2, hr3, lr1, lr2, lr3):
@@ -1474,6 +1491,10 @@ class ThreeViewOnlineStitcher(_Stitcher):
         -> list of newly stitched frames (empty for the first 6 pushes, 7 frames on the 7th, then one per push)."""
         _check_shapes('HR frames', (hr1, hr2, hr3), ((1, 3, self.h, self.w), (3, self.h, self.w)))
         _check_shapes('LR frames', (lr1, lr2, lr3), _LR_SHAPES)
+        with ops.deterministic(self.deterministic):
+            return self._push(hr1, hr2, hr3, lr1, lr2, lr3)
+
+    def _push(self, hr1, hr2, hr3, lr1, lr2, lr3):
         if self.static is not None:
             return self._push_static(hr1, hr2, hr3, lr1, lr2, lr3)
         sh = lambda t, c: t.reshape((1,) + tuple(c))
@@ -1501,6 +1522,87 @@ class ThreeViewOnlineStitcher(_Stitcher):
                        'hr': None if self._direct() else torch.empty((3, 3, self.h, self.w), device=self.dev)}
         return frames
 
+    # ------------------------------------------------------------------ k frame triples of the stream per call
+    @torch.no_grad()
+    def push_many(self, hr1, hr2, hr3, lr1, lr2, lr3):
+        """k consecutive frame triples of the stream in one call, 1 <= k <= BATCH_MAX: hr* [k,3,H,W] (0..255), lr* [k,3,360,480]
+        ([-1,1]), fp32 device tensors -> the newly stitched frames [3,Hc,Wc] in stream order: what k calls of `push` return, joined.
+        Frames before the first window is complete go through `push` one at a time; the rest of the call runs as ONE batched step
+        (per frame the arithmetic of `push`: both pair chains, composition, splines), captured into a HIP graph per batch size
+        (BATCH_GRAPHS sizes kept); the render runs outside the graph on the caller's frames.  Canvas growth, reloads and
+        interleaving with `push` / `push_u8` as in OnlineStitcher.push_many."""
+        return self._push_many((hr1, hr2, hr3, lr1, lr2, lr3))
+
+    @torch.no_grad()
+    def push_many_u8(self, frames1, frames2, frames3):
+        """k DECODED frame triples: uint8 [k,H,W,3] device tensors (cv2 layout) -> stitched video frames uint8 [Hc,Wc,3], byte for
+        byte what k calls of `push_u8` return, joined (see push_many)."""
+        return self._push_many_u8((frames1, frames2, frames3))
+
+    def _batch_buffers(self, k):
+        d, e, S = self.dev, 126, 2
+        fh, fw = pipeline.LR_H // 8, pipeline.LR_W // 8
+        return {'lr': torch.empty((3, k, 3, pipeline.LR_H, pipeline.LR_W), device=d),     # the three views back to back
+                'feat': torch.empty((3, k + 1, fh, fw, 128), device=d),        # TemporalNet features [view][previous frame, the k frames]
+                'sn': torch.empty((2, S * k, e), device=d),                    # new spatial motions [first | second view][pair][k]
+                'tn': torch.empty((2, S * k, e), device=d),                    # their temporal motions, same layout
+                'sw': torch.empty((2, S, k + 1, e), device=d),                 # spatial motions [pair view][pair][previous, the k frames]
+                'tt': torch.zeros((2, S, k + 1, e), device=d),                 # temporal motions [pair view][pair][zero, the k frames]
+                'ts': torch.empty((2, 2 * S * (k + 1), e), device=d),          # tsmotion's (smesh, tsmotion) rows
+                'work': torch.empty((4 * S, WINDOW - 1 + k, e), device=d)}     # the k sliding windows of the eight rings
+
+    def _step_batch(self, B):
+        """k consecutive steady-state frame triples from B['lr'] (capturable; the chains' state is read once and left as k
+        `_step_static` runs leave it).  The three views' k frames pass the twin trunks once (3k images); pair (s, j) -- chain s,
+        frame j -- is images (s k + j, (s + 1) k + j) of the [view][frame] trunk output; TemporalNet's 2 S k volumes come from the
+        features stored once, [view][previous frame, the k frames] (ss_cost_volume_chain_frames); tsmotion pairs each row of
+        [pair view][pair][previous, the k frames] with the one before; the eight rings advance by k; SmoothNet runs the windows of
+        both chains as ONE run over each ring kind's rows (the W - 1 windows that straddle the two chains are computed and
+        ignored); composition + splines of the k frames in one launch.  Ends with the watcher and the footprints (B['deferred'])."""
+        ch = self.chains
+        cs, k, e, S = ch.static, B['k'], 126, 2
+        F, sn, tn, sw, tt, ts = B['feat'], B['sn'], B['tn'], B['sw'], B['tt'], B['ts']
+        fc = L.run_stage1_pair([B['lr'].view(3 * k, 3, pipeline.LR_H, pipeline.LR_W)], ch._trunk())   # [2(net), 3k, 45,60,128]
+        f64 = fc[0]
+        off1 = _heads_a(self.spatial, f64, S * k, k)
+        F[:, 0].copy_(cs['prev_feat'])
+        F[:, 1:].copy_(fc[1].view(F[:, 1:].shape))
+        cv_s = self.spatial.cv_from_offset1(f64[:S * k], f64[k:k + S * k], off1, pipeline.LR_H, pipeline.LR_W)
+        cv_t = ops.cost_volume_chain_frames(F, 3)                               # [2 (pair view), S, k, 45,60,52]
+        off_ref = torch.empty((S * k, e), device=self.dev, dtype=torch.float32)
+        off_tgt = torch.empty((S * k, e), device=self.dev, dtype=torch.float32)
+        L.run_regressor_quad(cv_s, cv_t.view((2, S * k) + tuple(cv_t.shape[3:])), L.get_quad(self.spatial, self.temporal),
+                             [off_ref, off_tgt, tn[0], tn[1]])
+        cs['prev_feat'].copy_(F[:, k])
+        ops.spatial_meshes(off1, off_ref, off_tgt, pipeline.LR_H, pipeline.LR_W,
+                           out=(sn[0].view(S * k, 7, 9, 2), sn[1].view(S * k, 7, 9, 2)))
+        ps = cs['pair_s']                                                       # [pair view][previous, new][S][126]
+        torch.cat((ps[:, 0].view(2, S, 1, e), sn.view(2, S, k, e)), 2, out=sw)
+        tt[:, :, 1:].copy_(tn.view(2, S, k, e))
+        ps[:, 0].copy_(sw[:, :, k])                                             # the newest spatial motions become the previous ones
+        # tsmotion of every (pair view, pair) sequence as ONE batch of 2 S (k + 1) rows: row j pairs with row j - 1; slot 0's rows
+        # are computed and ignored
+        ops.tsmotion(sw.view(-1, 7, 9, 2), tt.view(-1, 7, 9, 2), pipeline.LR_H, pipeline.LR_W, out=(ts[0], ts[1]))
+        # ring r = kind q * S + s (kinds: smesh of the first / second view, tsmotion of the first / second view) <- rows 1 .. k of its
+        # sequence in ts
+        n1 = k + 1
+        offs = [((q // 2) * 2 * S * n1 + ((q % 2) * S + s) * n1 + 1) * e for q in range(4) for s in range(S)]
+        ops.window_advance(cs['ring'].view(4 * S, WINDOW, e), B['work'], ts, offs, k)
+        wk = B['work'].view(4, S * (WINDOW - 1 + k), 7, 9, 2)
+        nw = (S - 1) * (WINDOW - 1 + k) + k                     # window w starts at row w: chain s's frame j is window s (W - 1 + k) + j
+        outs, _ = self.smooth.run_windows(wk[0], wk[1], wk[2], wk[3], nw, WINDOW, 1, 1)
+        m1, m2 = outs['smooth_mesh1'], outs['smooth_mesh2']                      # [nw,7,7,9,2]: a frame's mesh is its window's last
+        c1 = WINDOW - 1 + k
+        meshes, src, T = ops.three_view_splines(m1[0, -1], m2[0, -1], m1[c1, -1], m2[c1, -1], self.first_canvas, self.bbox,
+                                                self.nrigid, self.h, self.w, frames=k, frame_stride=WINDOW * e)
+        self.last_composed = meshes
+        guard, wi, wf = self.watch.args()
+        ops.canvas_watch_frames(src, wi, wf, guard)
+        fp = None
+        if self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE:
+            fp = ops.render_footprints(src, T, self.h, self.w, self.hc, self.wc)
+        B['deferred'] = (src, T, fp)
+
 
 class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
     """ThreeViewOnlineStitcher with TWO pushes in flight (round 6; opt-in; see _TwoInFlight): the three views' trunks and the two
@@ -1512,6 +1614,12 @@ class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
         ThreeViewOnlineStitcher.__init__(self, nets, height, width, canvas, first_canvas, margin, warp_mode, fusion_mode,
                                          use_graph=True, grow='never')
         self._pipe_init()
+
+    def push_many(self, *frames):
+        raise ValueError('PipelinedThreeViewOnlineStitcher has no push_many: use ThreeViewOnlineStitcher.push_many')
+
+    def push_many_u8(self, *frames):
+        raise ValueError('PipelinedThreeViewOnlineStitcher has no push_many_u8: use ThreeViewOnlineStitcher.push_many_u8')
 
     def _pipe_alloc(self):
         d = self.dev

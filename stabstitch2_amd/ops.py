@@ -612,6 +612,22 @@ def cost_volume(x1, x2, r, out=None, chain=0, n=None, split=0, shift=0):
     return out
 
 
+def cost_volume_chain_frames(x, r, out=None):
+    """x [V,k+1,h,w,c] contiguous: the features of V >= 2 views of a chain over k frames, slot 0 = each view's previous frame ->
+    [2,V-1,k,h,w,pad4((2r+1)^2)]: the volumes [first views | second views] of the V - 1 pairs, volume (hh, s, j) = cost_volume of
+    (x[s + hh, j], x[s + hh, j + 1]), in ONE launch (ss_cost_volume_chain_frames)."""
+    views, k1, h, w, c = x.shape
+    k = k1 - 1
+    cs = ((((2 * r + 1) ** 2) + 3) // 4) * 4
+    assert x.is_contiguous() and x.dtype == torch.float32
+    shape = (2, views - 1, k, h, w, cs)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    assert tuple(out.shape) == shape and out.is_contiguous()
+    H.call('ss_cost_volume_chain_frames', H.dptr(x), H.dptr(out), views, k, h, w, c, r, cs, H.stream())
+    return out
+
+
 def cost_volume_bidir(x1, x2, r, out=None):
     """Both directions in one launch: nhwc in -> [2,n,h,w,pad4((2r+1)^2)] = (cost_volume(x1, x2), cost_volume(x2, x1))."""
     n, h, w, c = x1.shape
@@ -1139,22 +1155,32 @@ def three_view_finish(n1, n3, mid, bbox):
     return outs
 
 
-def three_view_splines(m12_1, m12_2, m23_1, m23_2, first_box, out_box, nrigid, img_h, img_w):
+def three_view_splines(m12_1, m12_2, m23_1, m23_2, first_box, out_box, nrigid, img_h, img_w, frames=None, frame_stride=126):
     """The streaming three-view push between the chains' smoothed meshes and the render in ONE launch (ss_three_view_splines =
     three_view_align -> three_view_normalize -> tps_solve -> tps_points -> three_view_finish on the first canvas, then the final
     meshes normalised on the output canvas and tps_solve_shared onto the rigid mesh; bit-identical to those launches).
     m*: [k,7,9,2] contiguous, LR scale -> ((mesh1, middle, mesh3) [1,k,7,9,2] first-canvas pixels, src [k,3,63,2], T [k,3,2,66]).
+    frames = k: each m* is frame 0's mesh [7,9,2] and frame f's lies f * frame_stride floats further in the same storage (the
+    window-last meshes of SmoothNet's windows: frame_stride = 7 * 126).
     The overflow watcher is not touched: render_footprints(..., watch=...) or canvas_watch(src, ...)."""
-    k = m12_1.numel() // 126
-    for m in (m12_1, m12_2, m23_1, m23_2):
-        assert m.is_contiguous() and m.dtype == torch.float32 and m.numel() == k * 126
+    if frames is None:
+        assert frame_stride == 126
+        k = m12_1.numel() // 126
+        for m in (m12_1, m12_2, m23_1, m23_2):
+            assert m.is_contiguous() and m.dtype == torch.float32 and m.numel() == k * 126
+    else:
+        k = int(frames)
+        assert k >= 1 and frame_stride >= 126
+        for m in (m12_1, m12_2, m23_1, m23_2):
+            assert m.is_contiguous() and m.dtype == torch.float32 and m.numel() == 126
+            assert m.storage_offset() + (k - 1) * frame_stride + 126 <= m.untyped_storage().nbytes() // 4, 'frames past the storage'
     assert nrigid.numel() == 126 and nrigid.is_contiguous()
     d = m12_1.device
     outs = [torch.empty((1, k, 7, 9, 2), device=d, dtype=torch.float32) for _ in range(3)]
     src = torch.empty((k, 3, 63, 2), device=d, dtype=torch.float32)
     T = torch.empty((k, 3, 2, 66), device=d, dtype=torch.float32)
-    H.call('ss_three_view_splines', H.dptr(m12_1), H.dptr(m12_2), H.dptr(m23_1), H.dptr(m23_2), 126, H.dptr(first_box), H.dptr(out_box),
-           H.dptr(nrigid), *[H.dptr(o) for o in outs], H.dptr(src), H.dptr(T), k, float(img_h), float(img_w), H.stream())
+    H.call('ss_three_view_splines', H.dptr(m12_1), H.dptr(m12_2), H.dptr(m23_1), H.dptr(m23_2), int(frame_stride), H.dptr(first_box),
+           H.dptr(out_box), H.dptr(nrigid), *[H.dptr(o) for o in outs], H.dptr(src), H.dptr(T), k, float(img_h), float(img_w), H.stream())
     return tuple(outs), src, T
 
 
