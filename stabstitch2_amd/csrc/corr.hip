@@ -430,7 +430,9 @@ __global__ void ccl_softmax_kernel(const float* __restrict__ Dm, float* __restri
 
 extern "C" long long ss_ccl_workspace_floats(int n, int h, int w, int c) {
     long long P = (long long)h * w;
-    return (long long)n * P * (2ll * c + P) + 64;      // + slack: the softmax reads D in 16-byte pieces at shifted columns
+    // + slack: the softmax reads D in 16-byte pieces at shifted columns, up to w + 4 floats past the last row's end (the tap one
+    // row down of the last 4-column piece); 64 covered maps up to 60 columns wide, all the pipeline has
+    return (long long)n * P * (2ll * c + P) + (w + 8 > 64 ? w + 8 : 64);
 }
 
 extern "C" int ss_ccl(const float* f1, const float* f2, float* flow_nchw, float* flow_nhwc4, int n, int h, int w,
