@@ -1,6 +1,7 @@
-"""Plain float64 statements of the non-convolution operations of the hot path, one function per operation.
+"""Plain float64 statements of the operations of the hot path, one function per operation.
 
-Written from the definitions in oracle/ (nets.py cost volume and CCL, samplers.py, metrics.py, pipeline.py) and the comments
+Written from the definitions in oracle/ (nets.py cost volume, CCL and the layers' nn.Conv2d / nn.Conv3d, samplers.py, metrics.py,
+pipeline.py), Lavin & Gray 2015 for the Winograd forms and the comments
 of include/stabstitch_hip.h; numpy only, no tiling, no tricks -- loops over displacements and taps.  Every function takes
 what the kernel takes (fp32 values, promoted here) and returns, beside the value, what the caller's tolerance needs (the sum
 of the absolute products of a dot product, the denominator of a projective map).
@@ -32,7 +33,7 @@ def dot_bound(k, s, extra=4):
     """Forward bound of an fp32 sum of k products in ANY order, s = sum of the absolute products: (k + extra) u s, u = 2^-24
     (|fl(x . y) - x . y| <= gamma_k |x| . |y|; the 1.01 is gamma_k's 1 / (1 - k u) for k u < 0.01).  `extra` roundings follow
     the sum (a division, a leaky-ReLU multiply, a final store)."""
-    assert k * U24 < 0.01
+    assert np.all(np.asarray(k) * U24 < 0.01)
     return (1.01 * k + extra) * U24 * s
 
 
@@ -316,3 +317,175 @@ def distortion_score(mesh):
         intra = np.maximum(dx - 120.0, 0).mean() + np.maximum(dy - 120.0, 0).mean()
         best = max(best, inter + intra)
     return float(best)
+
+
+# ------------------------------------------------------------------------------------------------ convolution
+def _conv_geometry(x, w, stride, pad):
+    """2-D operands get a temporal axis of 1; pad: a number (h and w), (ph, pw) or (pt, ph, pw).  The temporal stride is 1."""
+    if x.ndim == 4:
+        x, w = x[:, :, None], w[:, :, None]
+    pad = (0, pad, pad) if np.isscalar(pad) else ((0,) + tuple(pad) if len(pad) == 2 else tuple(pad))
+    n, c, t, h, wd = x.shape
+    co, cw, kt, kh, kw = w.shape
+    assert cw == c, (x.shape, w.shape)
+    to, ho, wo = t + 2 * pad[0] - kt + 1, (h + 2 * pad[1] - kh) // stride + 1, (wd + 2 * pad[2] - kw) // stride + 1
+    assert to > 0 and ho > 0 and wo > 0, (x.shape, w.shape, stride, pad)
+    return x, w, pad, (to, ho, wo)
+
+
+def conv(x, w, bias=None, res=None, stride=1, pad=0, relu=False):
+    """nn.Conv2d / nn.Conv3d (+ bias, + residual, + ReLU): x [n,c,(t,)h,w], w [cout,c,(kt,)kh,kw], zero padding `pad` on h and w (and
+    t when three are given), stride on h and w -> (value, S), both [n,cout,(to,)ho,wo]; S is the same loop on absolute values,
+    sum |x||w| + |bias| + |res|: the scale of dot_bound.  Per image (and block of output rows) the taps are gathered one by one into
+    [tap][c][to][rows][wo] and contracted with w in one product over (tap, c) -- the definition, in no particular order."""
+    two = np.ndim(x) == 4
+    x, w, (pt, ph, pw), (to, ho, wo) = _conv_geometry(f64(x), f64(w), stride, pad)
+    n, c, t, h, wd = x.shape
+    co, _, kt, kh, kw = w.shape
+    xp = np.zeros((n, c, t + 2 * pt, h + 2 * ph, wd + 2 * pw))
+    xp[:, :, pt:pt + t, ph:ph + h, pw:pw + wd] = x
+    wk = w.reshape(co, c, kt * kh * kw).transpose(0, 2, 1)                      # [cout][tap][c]
+    val = np.empty((n, co, to, ho, wo))
+    s = np.empty_like(val)
+    rows = max(1, (1 << 23) // (kt * kh * kw * c * to * wo))                  # output rows per pass: the gathered taps stay <= 64 MB
+    for b in range(n):
+        for y0 in range(0, ho, rows):
+            y1 = min(y0 + rows, ho)
+            cols = np.empty((kt * kh * kw, c, to, y1 - y0, wo))
+            for dt in range(kt):
+                for dy in range(kh):
+                    for dx in range(kw):
+                        ys = y0 * stride + dy
+                        cols[(dt * kh + dy) * kw + dx] = xp[b, :, dt:dt + to, ys:ys + (y1 - y0 - 1) * stride + 1:stride,
+                                                            dx:dx + (wo - 1) * stride + 1:stride]
+            val[b, :, :, y0:y1] = np.tensordot(wk, cols, axes=([1, 2], [0, 1]))
+            s[b, :, :, y0:y1] = np.tensordot(np.abs(wk), np.abs(cols), axes=([1, 2], [0, 1]))
+    if bias is not None:
+        bb = f64(bias).reshape(1, co, 1, 1, 1)
+        val, s = val + bb, s + np.abs(bb)
+    if res is not None:
+        rr = f64(res).reshape(val.shape)
+        val, s = val + rr, s + np.abs(rr)
+    if relu:
+        val = np.maximum(val, 0.0)
+    return (val[:, :, 0], s[:, :, 0]) if two else (val, s)
+
+
+def conv_terms(x_shape, w_shape, stride=1, pad=0):
+    """How many REAL products every output element of `conv` sums (taps that fall into the zero padding do not count; nor may the
+    caller count channels that exist only as layout padding: w_shape carries the real channel count) -> [(to,)ho,wo]."""
+    two = len(x_shape) == 4
+    x, w, pad, out = _conv_geometry(np.empty(x_shape, np.int8), np.empty(w_shape, np.int8), stride, pad)
+    cnt = []
+    for size, k, p, st, o in zip(x.shape[2:], w.shape[2:], pad, (1, stride, stride), out):
+        pos = np.arange(o)[:, None] * st - p + np.arange(k)[None, :]
+        cnt.append(((pos >= 0) & (pos < size)).sum(axis=1))
+    terms = w.shape[1] * cnt[0][:, None, None] * cnt[1][None, :, None] * cnt[2][None, None, :]
+    return terms[0] if two else terms
+
+
+def pool_max(v, k, stride, pad):
+    """nn.MaxPool2d(k, stride, pad), floor mode, -inf padding, over the last two axes of any array: of a value it is the pooled
+    value; of a per-element error bound it is the bound of the pooled element (the maximum of the bounds in its window)."""
+    v = f64(v)
+    h, w = v.shape[-2:]
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    vp = np.full(v.shape[:-2] + (h + 2 * pad, w + 2 * pad), -np.inf)
+    vp[..., pad:pad + h, pad:pad + w] = v
+    out = np.full(v.shape[:-2] + (ho, wo), -np.inf)
+    for dy in range(k):
+        for dx in range(k):
+            out = np.maximum(out, vp[..., dy:dy + (ho - 1) * stride + 1:stride, dx:dx + (wo - 1) * stride + 1:stride])
+    return out
+
+
+def conv_bound(x, w, bias=None, res=None, stride=1, pad=0, relu=False, extra=4):
+    """-> (value, bound) of `conv`: bound = dot_bound(K_real + 2, S, extra) per element, K_real from conv_terms (+ 2: bias, residual).
+    It holds for every order of the sum, so a split-K kernel needs nothing added; ReLU is exact."""
+    val, s = conv(x, w, bias, res, stride, pad, relu)
+    k = conv_terms(np.shape(x), np.shape(w), stride, pad) + 2
+    return val, dot_bound(k[None, None], s, extra)
+
+
+def conv_pool2(x, w, bias=None, stride=1, pad=0, relu=True, extra=4):
+    """`conv` followed by nn.MaxPool2d(2, 2) (floor: the last row / column of an odd map is dropped) -> (value, bound)."""
+    val, b = conv_bound(x, w, bias, None, stride, pad, relu, extra)
+    return pool_max(val, 2, 2, 0), pool_max(b, 2, 2, 0)
+
+
+def stem(x, w, bias=None, extra=4):
+    """The network stem: Conv2d(3, cout, 7, stride 2, pad 3) with BatchNorm folded into (w, bias), ReLU -> (value, bound), and
+    stem_pool: the same followed by MaxPool2d(3, 2, 1)."""
+    return conv_bound(x, w, bias, None, 2, 3, True, extra)
+
+
+def stem_pool(x, w, bias=None, extra=4):
+    val, b = stem(x, w, bias, extra)
+    return pool_max(val, 3, 2, 1), pool_max(b, 3, 2, 1)
+
+
+# Winograd minimal filtering F(m x m, 3 x 3), Y = A^T [ (G g G^T) . (B^T d B) ] A  (Lavin & Gray 2015), m = 2 and 4
+WINO = {
+    2: dict(BT=np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=np.float64),
+            G=np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=np.float64),
+            AT=np.array([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=np.float64)),
+    4: dict(BT=np.array([[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0],
+                         [0, 4, 0, -5, 0, 1]], dtype=np.float64),
+            G=np.array([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6],
+                        [0, 0, 1]], dtype=np.float64),
+            AT=np.array([[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 1]], dtype=np.float64)),
+}
+
+
+def wino_tiles(x, m):
+    """x [n,c,h,w] -> d [n,c,th,tw,m+2,m+2]: the (m + 2)^2 input windows of the m x m output tiles of a 3 x 3 / pad 1 convolution,
+    tiles laid out from output pixel (0, 0) (th = ceil(h / m)), zeros outside the image."""
+    n, c, h, w = x.shape
+    th, tw, a = -(-h // m), -(-w // m), m + 2
+    xp = np.zeros((n, c, th * m + 2, tw * m + 2), dtype=x.dtype)
+    xp[:, :, 1:1 + h, 1:1 + w] = x
+    d = np.empty((n, c, th, tw, a, a), dtype=x.dtype)
+    for i in range(a):
+        for j in range(a):
+            d[..., i, j] = xp[:, :, i:i + th * m:m, j:j + tw * m:m]
+    return d
+
+
+def wino_untile(y, h, w):
+    """[n,co,th,tw,m,m] -> [n,co,h,w]"""
+    n, co, th, tw, m, _ = y.shape
+    return y.transpose(0, 1, 2, 4, 3, 5).reshape(n, co, th * m, tw * m)[:, :, :h, :w]
+
+
+def wino_scale(x, w, m, bias=None, res=None):
+    """The scale of the rounding error of F(m x m, 3 x 3) on x [n,c,h,w], w [cout,c,3,3] -> S_w [n,cout,h,w]:
+    |A^T| [ sum_c (|G||g_c||G^T|) . (|B^T||d_c||B|) ] |A| per output tile (+ |bias| + |res|), the Winograd form evaluated on
+    absolute values -- what dot_bound's S is to a direct sum.  It exceeds the direct S by the growth of the transforms
+    (|B^T| . |B| has row sums up to 4 for m = 2 and 100 for m = 4)."""
+    x, w = f64(x), f64(w)
+    k = WINO[m]
+    bt, g, at = np.abs(k['BT']), np.abs(k['G']), np.abs(k['AT'])
+    u = np.einsum('ia,ocab,jb->ocij', g, np.abs(w), g)
+    v = np.einsum('ia,nctuab,jb->nctuij', bt, wino_tiles(np.abs(x), m), bt)
+    n, c, th, tw, a, _ = v.shape
+    prod = np.einsum('ijoc,ijcq->ijoq', u.transpose(2, 3, 0, 1), v.transpose(4, 5, 1, 0, 2, 3).reshape(a, a, c, n * th * tw))
+    prod = prod.reshape(a, a, w.shape[0], n, th, tw).transpose(3, 2, 4, 5, 0, 1)           # [n,co,th,tw,a,a]
+    s = wino_untile(np.einsum('pi,notuij,qj->notupq', at, prod, at), x.shape[2], x.shape[3])
+    if bias is not None:
+        s = s + np.abs(f64(bias)).reshape(1, -1, 1, 1)
+    if res is not None:
+        s = s + np.abs(f64(res))
+    return s
+
+
+# roundings of the transforms of one output element, beside the cin of the channel sum: a row of a transform matrix with k
+# non-zero entries costs at most k - 1 additions (its constants are fused or powers of two in the kernels: v_fma / v_pk_fma), the
+# filter transform is formed in fp64 and rounded once.  m = 2 (wino.hip): B^T rows have 2 entries -> 1 + 1, A^T rows 3 -> 2 + 2,
+# filters 1: 7.  m = 4 (wino43.hip): B^T rows up to 4 entries -> 3 + 3 (and one more each where 5 x is not fused: 4 + 4), A^T rows 5
+# -> 4 + 4, filters 1: 17.
+WINO_ROUNDINGS = {2: 7, 4: 17}
+
+
+def wino_ceiling(cin, m, s_w, extra=3):
+    """The derived ceiling of F(m x m, 3 x 3) in fp32: (1.01 (cin + T_m) + extra) u S_w; extra: bias, residual, store."""
+    return (1.01 * (cin + WINO_ROUNDINGS[m]) + extra) * U24 * s_w

@@ -76,8 +76,8 @@ def _pack(w, cin_pad):
     (3, 64, 128, 45, 60, 1, 2, 0, True, False, False),   # downsample 1x1
     (2, 121, 64, 45, 60, 3, 1, 1, False, False, True),   # cost-volume regressor (121 -> 124 ch)
     (5, 128, 256, 5, 7, 3, 1, 1, False, False, True),    # tiny map, M tail
-    (16, 64, 64, 90, 120, 3, 1, 1, True, True, True),    # large M -> 128-row tiles
-    (16, 128, 128, 45, 60, 3, 1, 1, True, False, True),  # 128x128 tiles
+    (16, 64, 64, 90, 120, 3, 1, 1, True, True, True),    # large M: ops.conv runs F(2x2,3x3) here; on the implicit GEMM b128m = 1350 < 2048: the 64x64 tile
+    (16, 128, 128, 45, 60, 3, 1, 1, True, False, True),  # F(2x2,3x3) too; b128 = 675 < 2048: no 64x128 tile (the large tiles: test_gpu_conv_sweeps.py)
 ])
 def test_conv2d(dev, n, cin, cout, h, w, k, s, p, bias, res, relu):
     from stabstitch2_amd import ops

@@ -262,3 +262,192 @@ def test_stability_distortion_oracle_on_sweep_inputs():
         ref = R.distortion_score(m)
         assert ref > 0.5                                   # the stretched cells are counted
         assert abs(M.distortion_score(T(m).view(1, t, 7, 9, 2)) - ref) < 5e-6
+
+
+# ------------------------------------------------------------------------------------------------ convolution
+CONV_RAGGED = [                    # (n, cin, cout, (t,) h, w, k, stride, pad)
+    (2, 5, 7, None, 9, 11, (3, 3), 2, (1, 2)), (1, 4, 3, None, 6, 5, (7, 7), 1, (3, 3)), (2, 3, 4, None, 5, 6, (2, 5), 3, (2, 3)),
+    (3, 6, 5, None, 1, 1, (3, 3), 1, (1, 1)), (1, 2, 9, None, 2, 3, (7, 7), 2, (3, 3)), (1, 7, 2, None, 8, 8, (1, 1), 2, (0, 0)),
+    (2, 3, 4, 6, 5, 7, (5, 3, 3), 1, (2, 1, 1)), (1, 4, 3, 7, 4, 5, (3, 3, 3), 1, (0, 1, 1)), (1, 2, 3, 5, 6, 6, (5, 5, 5), 2, (2, 0, 3)),
+]
+
+
+@pytest.mark.parametrize('n,cin,cout,t,h,w,k,stride,pad', CONV_RAGGED)
+def test_conv_statement_against_torch_fp64(n, cin, cout, t, h, w, k, stride, pad):
+    """ref64.conv (value), its S (the same convolution of absolute values) and conv_terms (a convolution of ones) against
+    F.conv2d / F.conv3d in float64, with bias, residual and ReLU; pool_max against F.max_pool2d."""
+    rs = np.random.RandomState(n + 10 * cin + 100 * h + w)
+    x = rs.normal(0, 1, (n, cin, h, w) if t is None else (n, cin, t, h, w))
+    wt = rs.normal(0, 1, (cout, cin) + k)
+    b = rs.normal(0, 1, cout)
+    if t is None:
+        f = lambda a, c, bb: F.conv2d(T(a), T(c), None if bb is None else T(bb), stride=stride, padding=pad)
+    else:
+        f = lambda a, c, bb: F.conv3d(T(a), T(c), None if bb is None else T(bb), stride=(1, stride, stride), padding=pad)
+    pre = f(x, wt, b).numpy()
+    r = rs.normal(0, 1, pre.shape)
+    val, s = R.conv(x, wt, b, r, stride, pad, relu=True)
+    assert maxerr(val, np.maximum(pre + r, 0), 'conv') < 1e-12
+    assert maxerr(s, f(np.abs(x), np.abs(wt), np.abs(b)).numpy() + np.abs(r), 'S') < 1e-12
+    ones = f(np.ones((1,) + x.shape[1:]), np.ones((1,) + wt.shape[1:]), None).numpy()[0, 0]
+    assert (R.conv_terms(x.shape, wt.shape, stride, pad) == np.rint(ones)).all()
+    v2, bd = R.conv_bound(x, wt, b, r, stride, pad, relu=True)
+    assert (v2 == val).all() and (bd == R.dot_bound(np.rint(ones) + 2, s)).all()
+    if t is None:
+        for (pk, ps, pp) in ((2, 2, 0), (3, 2, 1)):
+            if val.shape[2] + 2 * pp >= pk and val.shape[3] + 2 * pp >= pk:
+                assert (R.pool_max(val, pk, ps, pp) == F.max_pool2d(T(val), pk, ps, pp).numpy()).all()
+
+
+def _fold_bn(conv, bn):
+    sc = (bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps))
+    return (conv.weight.double() * sc.view(-1, 1, 1, 1)).numpy(), (bn.bias.double() - bn.running_mean.double() * sc).numpy()
+
+
+def test_conv_statement_against_the_oracle_layers():
+    """ref64 against the fp32 oracle layers that the goldens pin (oracle/nets.py under the synthetic checkpoint, on G8's frames):
+    the stem (conv 7x7/2, BatchNorm folded here in fp64, ReLU, max-pool 3/2/1), the first residual block's conv + BN + ReLU, a
+    regressor conv + ReLU + conv + ReLU + MaxPool2d(2, 2), and SmoothNet's first Conv3d.  The oracle is fp32: 1e-5 relative to the
+    largest value."""
+    from stabstitch2_amd import synth
+    sp, sm = N.SpatialNet().eval(), N.SmoothNet().eval()
+    for m in (sp, sm):
+        m.load_state_dict(synth.synthetic_state_dict(m), strict=True)
+    _, lr = synth.make_clip(2, 360, 480, seed=0)
+    x = torch.cat([lr[0][0], lr[1][1]])[:, :, 100:193, 200:321].contiguous()                 # 2 frames, a 93 x 121 window
+    s1 = sp.feature_extractor_stage1
+    w0, b0 = _fold_bn(s1[0], s1[1])
+    want = s1[3](s1[2](s1[1](s1[0](x))))
+    got, bound = R.stem_pool(x.numpy(), w0, b0)
+    assert maxerr(got, want, 'stem + pool') <= 1e-5 * float(want.abs().max())
+    blk = s1[4][0]
+    w1, b1 = _fold_bn(blk.conv1, blk.bn1)
+    want1 = blk.relu(blk.bn1(blk.conv1(want)))
+    got1, _ = R.conv(want.numpy(), w1, b1, None, 1, 1, relu=True)
+    assert maxerr(got1, want1, 'layer1 conv1') <= 1e-5 * float(want1.abs().max())
+    reg = sp.regressNet1_part1
+    z = T(G.conv_inputs(2, 2, 2, 45, 60)[0])
+    wantp = reg[4](reg[3](reg[2](reg[1](reg[0](z)))))
+    mid, _ = R.conv(z.numpy(), reg[0].weight.numpy(), None, None, 1, 1, relu=True)
+    gotp, _ = R.conv_pool2(mid, reg[2].weight.numpy(), None, 1, 1, relu=True)
+    assert gotp.shape == tuple(wantp.shape) and maxerr(gotp, wantp, 'regressor conv, conv, pool') <= 1e-5 * float(wantp.abs().max())
+    c3 = sm.MotionPre.MotionConv3D[0]
+    h = T(G.conv_inputs(1, 128, 128, 7, 9, (5, 3, 3), t=7)[0])
+    want3 = F.relu(c3(h))
+    got3, _ = R.conv(h.numpy(), c3.weight.numpy(), c3.bias.numpy(), None, 1, (2, 1, 1), relu=True)
+    assert maxerr(got3, want3, 'conv3d') <= 1e-5 * float(want3.abs().max())
+
+
+def _ig_operands(c):
+    """x, w, bias, res of an implicit-GEMM case in torch's layouts (real channels only), and the conv arguments."""
+    to, ho, wo, M, K = G.ig_geometry(c)
+    out_hw = (ho, wo) if c['t'] is None else (to, ho, wo)
+    return G.conv_inputs(c['n'], c['c_real'], c['cout'], c['h'], c['w'], c['k'], t=c['t'], out_hw=out_hw, bias=c['bias'], res=c['res'])
+
+
+@pytest.mark.parametrize('c', G.IGEMM_CASES, ids=lambda c: c['name'])
+def test_torch_fp32_conv_inside_the_direct_gate(c):
+    """fp32 F.conv2d / conv3d (another fp32 sum, in torch's order) meets the direct-convolution gate dot_bound(K_real + 2, S) on every
+    sweep input with a factor 2 to spare: the gate is usable, and torch's own error is where the derivation says."""
+    x, wt, b, r = _ig_operands(c)
+    pad = c['p'] if c['t'] is not None else c['p'][1:]
+    ref, bound = R.conv_bound(x, wt, b, r, c['s'], pad, c['relu'])
+    if c['t'] is None:
+        o = F.conv2d(T(x), T(wt), None if b is None else T(b), stride=c['s'], padding=pad)
+    else:
+        o = F.conv3d(T(x), T(wt), None if b is None else T(b), stride=(1, c['s'], c['s']), padding=pad)
+    if r is not None:
+        o = o + T(r)
+    o = F.relu(o) if c['relu'] else o
+    ratio = float((np.abs(o.numpy() - ref) / bound).max())
+    assert ratio <= 0.5, ratio                   # observed <= 0.16
+
+
+@pytest.mark.parametrize('h,w', G.STEM_SIZES, ids=lambda v: str(v))
+def test_torch_fp32_stem_inside_the_direct_gate(h, w):
+    """the same for the stem's inputs: conv 7x7/2 + ReLU and the 3/2/1 max-pool of it (bound pooled by max), two filter banks"""
+    x, wt, b = G.stem_inputs(5, h, w, 2)
+    o = F.relu(F.conv2d(T(x), T(wt), T(b), stride=2, padding=3))
+    ref, bound = R.stem(x, wt, b)
+    assert float((np.abs(o.numpy() - ref) / bound).max()) <= 0.5
+    pref, pbound = R.stem_pool(x, wt, b)
+    assert float((np.abs(F.max_pool2d(o, 3, 2, 1).numpy() - pref) / pbound).max()) <= 0.5
+
+
+def test_implicit_gemm_claims_follow_the_dispatch_rules():
+    """Every implicit-GEMM case's claimed path (tile, address mode, TAIL, splits) is what conv.hip's rules, restated in
+    sweep_inputs.igemm_plan, give for its shape; and the restated split-K plan is the library's own (ss_conv_workspace_need is
+    host code: it answers without a GPU)."""
+    from stabstitch2_amd import _hip as H
+    for c in G.IGEMM_CASES:
+        plan = G.ig_plan(c)
+        assert G.ig_claim(plan) == c['claim'], (c['name'], c['claim'], G.ig_claim(plan), plan)
+        kt, kh, kw = c['k']
+        pt, ph, pw = c['p']
+        to, ho, wo, M, K = G.ig_geometry(c)
+        need = int(H.lib().ss_conv_workspace_need(c['n'], c['t'] or 1, c['h'], c['w'], c['cin'], c['cout'], kt, kh, kw, c['s'], pt, ph, pw,
+                                                  c['groups']))
+        sp = G.conv_splits(M, c['cout'], c['groups'], G.cdiv(K, 32))
+        assert need == (c['groups'] * sp * M * c['cout'] if sp > 1 else 0), (c['name'], need, sp)
+        assert (sp == plan['splits']) == c['ws'] or sp == 1, c['name']
+    for case in G.POOL_REDUCE_CASES:
+        n, h, w, cin, cout, groups, _ = case
+        assert G.conv_splits(n * h * w, cout, groups, G.cdiv(9 * cin, 32)) > 1, case
+    for (h, w, cin) in ((7, 16, 64), (16, 7, 64), (45, 60, 128), (23, 30, 256), (11, 15, 128), (5, 7, 128)):          # wino_blocks == the library's rule
+        tbh, tbw = G.wino_blocks(h, w)
+        wgs = lambda images: images * G.cdiv((h + 1) // 2, tbh) * G.cdiv((w + 1) // 2, tbw)
+        eff = h * w / (4.0 * G.cdiv((h + 1) // 2, tbh) * tbh * G.cdiv((w + 1) // 2, tbw) * tbw)
+        for images in (1, 95, 96, 191, 192):
+            want = (wgs(images) >= 96) if eff >= 0.70 else (eff >= 0.60 and wgs(images) >= 192)
+            assert bool(H.lib().ss_conv_uses_winograd(1, 3, 3, 1, cin, 64, h, w, images)) == want, (h, w, images)
+
+
+def test_reach_table_names_every_conv_kernel_of_the_library():
+    """The reach table of the convolution sweep against the gfx950 code objects of the built library: every instantiation of
+    conv_igemm_kernel, splitk_reduce_kernel, conv_wino_kernel, conv_wino43* and stem_pool* that the library carries is either named
+    by the table (with the cases claimed to launch it) or listed as unreachable from the C ABI with the reason, and the table names
+    nothing the library lacks."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))
+    import kernel_resources as KR
+    from stabstitch2_amd import _hip as H
+    have = {G.kernel_key(k) for k in KR.kernels(H.LIB_PATH)}
+    have = {k for k in have if k.startswith(G.CONV_ENGINE_KERNELS)}
+    assert len(have) >= 30, sorted(have)
+    table = G.reach_table()
+    assert not set(table) & set(G.UNREACHABLE)
+    missing = sorted(have - set(table) - set(G.UNREACHABLE))
+    assert not missing, 'instantiations in the library that no sweep case claims: %s' % missing
+    stale = sorted((set(table) | set(G.UNREACHABLE)) - have)
+    assert not stale, 'the table names kernels the library does not carry: %s' % stale
+    assert all(table[k] for k in table)
+
+
+W2_CPU = G.WINO2_CASES
+W43_CPU = G.WINO43_CASES[:-1]       # (the 11-image case repeats the 46 x 120 geometry of its neighbours: the emulation is the same)
+
+
+@pytest.mark.parametrize('m,case', [(2, c) for c in W2_CPU] + [(4, c) for c in W43_CPU], ids=lambda v: '-'.join(map(str, v)) if isinstance(v, tuple) else 'F%d' % v)
+def test_winograd_emulation_inside_the_derived_ceiling(m, case):
+    """The fp32 emulation of F(m x m, 3 x 3) (sweep_inputs.wino_emul32) against ref64 on every Winograd sweep input: inside the derived
+    ceiling (1.01 (cin + T_m) + extra) u S_w with a factor 2 to spare, with bias + residual + ReLU and bare.  In exact arithmetic the
+    Winograd form IS the convolution (checked in fp64); rho, the emulation's error in units of u S_w, is what the GPU gate uses."""
+    n, h, w, cin, cout = case
+    x, wt, b, r = G.conv_inputs(n, cin, cout, h, w, out_hw=(h, w), res=True)
+    k = R.WINO[m]
+    d = R.wino_tiles(x.astype(np.float64), m)
+    u = np.einsum('ia,ocab,jb->ocij', k['G'], wt.astype(np.float64), k['G'])
+    v = np.einsum('ia,nctuab,jb->nctuij', k['BT'], d, k['BT'])
+    y = R.wino_untile(np.einsum('pi,notuij,qj->notupq', k['AT'], np.einsum('ocij,nctuij->notuij', u, v), k['AT']), h, w)
+    exact, s_direct = R.conv(x, wt, None, None, 1, 1)
+    assert maxerr(y, exact, 'fp64 Winograd form') <= 1e-11 * float(s_direct.max())
+    for (bb, rr, relu) in ((b, r, True), (None, None, False)):
+        ref, bound, rho, s_w = G.wino_gate(x, wt, m, bb, rr, relu)
+        assert (s_w >= s_direct - 1e-9).all()                       # the transforms only grow the scale
+        ceiling = R.wino_ceiling(cin, m, s_w)
+        e = np.abs(G.wino_emul32(x, wt, m, bb, rr, relu).astype(np.float64) - ref)
+        ratio = float((e / ceiling).max())
+        if os.environ.get('SS_VERBOSE'):
+            print('  [ref64] F(%d) %s rho %.3f, emulation / ceiling %.3f' % (m, case, rho, ratio))
+        assert ratio <= 0.5, (ratio, rho)
+        assert 0 < rho and (e <= bound).all()
