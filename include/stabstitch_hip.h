@@ -346,6 +346,22 @@ SS_API int ss_render_linear_clip(const float* const* views_base, const float* so
 SS_API int ss_render_linear_clip_u8(const unsigned char* const* views_base, const float* source, const float* T,
                              unsigned char* out, float* mask1_out, int frames, int views, int h, int w, int hc, int wc,
                              int mode, float* ws, void* stream);
+/* LINEAR fusion of frames that each have their OWN canvas -- one iteration of the frame loop of get_stable_sqe with fusion_mode ==
+ * 'LINEAR' (test_online_tra.py:127-152 around linear_blender :34-58; three views test_online_tra_threeview.py:489-502) for each of
+ * `frames` frames (the current frames of up to 32 live streams, or one streaming push: frames = 1) in the clip entry's three launches
+ * (four with three views), whatever `frames` is and however the sizes differ.  views_base, source, T as in the clip entry (frame f of
+ * view k at views_base[k] + f * 3 h w); hc, wc, out: HOST arrays of `frames` entries, consumed during the call; out[f] = device
+ * pointer to [3][hc[f]][wc[f]] fp32 (the _u8 form: [hc[f]][wc[f]][3] uint8).  1 <= frames <= 32, each hc[f], wc[f] in 11..65535.
+ * ws: ss_linear_frames_workspace_floats(frames, views, hc, wc) floats (0 for arguments the render refuses; equal to the clip
+ * entry's at equal sizes).  Bit-identical, frame by frame, to the clip entry called with that one frame on that canvas;
+ * ss_linear_clip_set_rows(r > 0) sets the strip height here too (r < 0: the default height). */
+SS_API long long ss_linear_frames_workspace_floats(int frames, int views, const int* hc, const int* wc);
+SS_API int ss_render_linear_frames(const float* const* views_base, const float* source, const float* T, float* const* out,
+                            int frames, int views, int h, int w, const int* hc, const int* wc, int mode, float* ws,
+                            void* stream);
+SS_API int ss_render_linear_frames_u8(const unsigned char* const* views_base, const float* source, const float* T,
+                               unsigned char* const* out, int frames, int views, int h, int w, const int* hc,
+                               const int* wc, int mode, float* ws, void* stream);
 
 /* ---- K14: canvas bounding box and mesh normalisation (test_online_tra.py:103-136) ------------
  * mesh: n_points (x,y) pairs at LR scale (480x360); each is scaled to the HR frame as the reference

@@ -89,6 +89,11 @@ SIGNATURES = {
     'ss_linear_clip_set_rows': (c_i, [c_i]),
     'ss_render_linear_clip': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_fp] + [c_i] * 7 + [c_fp, c_st]),
     'ss_render_linear_clip_u8': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_fp] + [c_i] * 7 + [c_fp, c_st]),
+    'ss_linear_frames_workspace_floats': (c_ll, [c_i, c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i)]),
+    'ss_render_linear_frames': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, ctypes.POINTER(c_fp)] + [c_i] * 4 +
+                                [ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_i, c_fp, c_st]),
+    'ss_render_linear_frames_u8': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, ctypes.POINTER(c_fp)] + [c_i] * 4 +
+                                   [ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_i, c_fp, c_st]),
     'ss_mesh_bbox': (c_i, [c_fp, c_i, c_f, c_f, c_fp, c_i, c_st]),
     'ss_mesh_normalize': (c_i, [c_fp, c_fp, c_fp, c_i, c_f, c_f, c_st]),
     'ss_canvas_watch': (c_i, [c_fp, c_i, c_i, c_f, c_fp, c_fp, c_st]),

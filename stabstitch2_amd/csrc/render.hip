@@ -868,24 +868,17 @@ __device__ __forceinline__ unsigned lane_index_sum(unsigned long long m) {
            16u * (unsigned)__popcll(m & 0xFFFF0000FFFF0000ull) + 32u * (unsigned)__popcll(m & 0xFFFFFFFF00000000ull);
 }
 
+// one 64 x 8 tile of ONE frame: rv / source / T / W are that frame's, tile_part its partials of this tile [4 waves][P][LBC_PW]
 template <int VIEWS, bool U8>
-__global__ __launch_bounds__(256) void lb_clip_warp_kernel(RenderViews rv, const float* __restrict__ source,
-                                                           const float* __restrict__ T, float* __restrict__ W,
-                                                           unsigned* __restrict__ partials, int h, int w, int hc, int wc,
-                                                           int mode, long long img_fs) {
+__device__ __forceinline__ void lb_warp_tile(RenderViews rv, const float* __restrict__ source,
+                                             const float* __restrict__ T, float* __restrict__ W,
+                                             unsigned* __restrict__ tile_part, unsigned tile, int h, int w, int hc, int wc, int mode) {
     constexpr int P = VIEWS - 1;
-    const long long frame = blockIdx.y;
     const long long hw = (long long)h * w, ohw = (long long)hc * wc;
-    source += frame * (VIEWS * SS_NV * 2);
-    T += frame * (VIEWS * 2 * SS_NT);
-    W += frame * (VIEWS * 4) * ohw;
-#pragma unroll
-    for (int k = 0; k < VIEWS; ++k)
-        rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + frame * img_fs);
     const int lx = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nbx = (wc + 63) / 64;
-    const int tby = blockIdx.x / nbx, tbx = blockIdx.x - tby * nbx;
-    unsigned* part = partials + ((frame * gridDim.x + blockIdx.x) * 4 + wv) * (P * LBC_PW);
+    const int tby = tile / nbx, tbx = tile - tby * nbx;      // (unsigned division: tile is a block index)
+    unsigned* part = tile_part + wv * (P * LBC_PW);
     const int x = tbx * 64 + lx;
     const int ya = tby * 8 + wv, yb = ya + 4;
     if (ya >= hc) {                                  // a wave below the canvas: its partials are read all the same
@@ -967,14 +960,24 @@ __global__ __launch_bounds__(256) void lb_clip_warp_kernel(RenderViews rv, const
     }
 }
 
-// one workgroup per (frame, pass): wave partials -> scalars block
-__global__ __launch_bounds__(256) void lb_clip_reduce_kernel(const unsigned* __restrict__ partials, unsigned long long* __restrict__ scalars,
-                                                             int tiles, int nbx, int passes) {
-    const int frame = blockIdx.x / passes, p = blockIdx.x - frame * passes;
-    const unsigned* q0 = partials + ((long long)frame * tiles * 4) * (passes * LBC_PW) + p * LBC_PW;
-    const long long stride = (long long)passes * LBC_PW;
-    const int nw = tiles * 4;                        // wave partials of this frame
-    unsigned long long* s = scalars + (long long)blockIdx.x * 16;
+template <int VIEWS, bool U8>
+__global__ __launch_bounds__(256) void lb_clip_warp_kernel(RenderViews rv, const float* __restrict__ source,
+                                                           const float* __restrict__ T, float* __restrict__ W,
+                                                           unsigned* __restrict__ partials, int h, int w, int hc, int wc,
+                                                           int mode, long long img_fs) {
+    constexpr int P = VIEWS - 1;
+    const long long frame = blockIdx.y;
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k)
+        rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + frame * img_fs);
+    lb_warp_tile<VIEWS, U8>(rv, source + frame * (VIEWS * SS_NV * 2), T + frame * (VIEWS * 2 * SS_NT),
+                            W + frame * (VIEWS * 4) * ((long long)hc * wc),
+                            partials + ((frame * gridDim.x + blockIdx.x) * 4) * (P * LBC_PW), blockIdx.x, h, w, hc, wc, mode);
+}
+
+// one (frame, pass): the frame's nw wave partials of this pass (q0, `stride` words apart) -> its scalars block s
+__device__ __forceinline__ void lb_reduce_pass(const unsigned* __restrict__ q0, long long stride, int nw, int nbx,
+                                               unsigned long long* __restrict__ s) {
     __shared__ unsigned long long red[6];
     __shared__ LbCenters Ls;
     __shared__ float smn[4], smx[4];
@@ -1027,6 +1030,14 @@ __global__ __launch_bounds__(256) void lb_clip_reduce_kernel(const unsigned* __r
         u[12] = mn != INFINITY ? f2key(mn) : 0xffffffffu;         // (the values lb_init_kernel + atomicMin / atomicMax leave)
         u[13] = mx != -INFINITY ? f2key(mx) : 0u;
     }
+}
+
+// one workgroup per (frame, pass): wave partials -> scalars block
+__global__ __launch_bounds__(256) void lb_clip_reduce_kernel(const unsigned* __restrict__ partials, unsigned long long* __restrict__ scalars,
+                                                             int tiles, int nbx, int passes) {
+    const int frame = blockIdx.x / passes, p = blockIdx.x - frame * passes;
+    lb_reduce_pass(partials + ((long long)frame * tiles * 4) * (passes * LBC_PW) + p * LBC_PW, (long long)passes * LBC_PW,
+                   tiles * 4, nbx, scalars + (long long)blockIdx.x * 16);
 }
 
 struct LbClipArgs {
@@ -1124,20 +1135,28 @@ __global__ __launch_bounds__(256) void lb_clip_blend_kernel(LbClipArgs a, int hc
 // loads of the next row are issued before the current row's arithmetic.  Same fmaf chains as the tile kernel and as
 // lb_blur_kernel: bit-identical output.  The tile kernel moved 2.2 GB per 32-frame clip at 2.7 TB/s (three phases between
 // barriers, 50 KB of LDS -> 3 workgroups per CU: its loads came in bursts); this one streams.
+// one blend pass of ONE frame: its planes, this pass's scalars block, its output ([3][hc][wc] fp32 or [hc][wc][3] uint8)
+struct LbPass {
+    const float *ref, *tgt, *m1a, *m1b, *m2;          // m1b (UNION): ref mask = m1a + m1b - m1a m1b
+    float* mk_out;                                    // nullable [hc][wc]
+    const unsigned long long* s;
+    void* out;
+};
+
+// strip (bx, by) of 64 columns x rs rows of that frame, one wave
 template <bool UNION, bool U8OUT>
-__global__ __launch_bounds__(64) void lb_clip_blend_rows_kernel(LbClipArgs a, int hc, int wc, int rs, Gauss21 g) {
+__device__ __forceinline__ void lb_blend_strip(const LbPass& a, int hc, int wc, int rs, int bx, int by, const Gauss21& g) {
     __shared__ float XL[96];
     __shared__ LbCenters Ls;
     __shared__ float prange[2];
-    const long long frame = blockIdx.z;
     const long long ohw = (long long)hc * wc;
-    const float* __restrict__ m1a = a.m1a + frame * a.m_fs;
-    const float* __restrict__ m1b = UNION ? a.m1b + frame * a.m_fs : nullptr;
-    const float* __restrict__ m2 = a.m2 + frame * a.m_fs;
-    const float* __restrict__ ref = a.ref + frame * a.ref_fs;
-    const float* __restrict__ tgt = a.tgt + frame * a.tgt_fs;
-    float* mk_out = a.mask1_out ? a.mask1_out + frame * a.mask1_fs : nullptr;
-    const unsigned long long* s = a.scalars + frame * a.sc_fs;
+    const float* __restrict__ m1a = a.m1a;
+    const float* __restrict__ m1b = UNION ? a.m1b : nullptr;
+    const float* __restrict__ m2 = a.m2;
+    const float* __restrict__ ref = a.ref;
+    const float* __restrict__ tgt = a.tgt;
+    float* mk_out = a.mk_out;
+    const unsigned long long* s = a.s;
     const int lane = threadIdx.x;
     if (lane == 0) {
         Ls = lb_centers(s);
@@ -1149,7 +1168,7 @@ __global__ __launch_bounds__(64) void lb_clip_blend_rows_kernel(LbClipArgs a, in
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const LbCenters L = Ls;
     const float pmin = prange[0], pden = __fadd_rn(__fsub_rn(prange[1], prange[0]), 1e-3f);
-    const int c0 = blockIdx.x * 64, s0 = blockIdx.y * rs, s1 = min(s0 + rs, hc);
+    const int c0 = bx * 64, s0 = by * rs, s1 = min(s0 + rs, hc);
     const int c = c0 + lane;
     const bool cin = c < wc, second = lane < 20;
     const int ca = min(max(reflect_idx(c0 - 10 + lane, wc), 0), wc - 1);
@@ -1221,11 +1240,28 @@ __global__ __launch_bounds__(64) void lb_clip_blend_rows_kernel(LbClipArgs a, in
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
                 const float v = __fadd_rn(__fmul_rn(orf[ch], mk), __fmul_rn(otg[ch], mk2));
-                if (U8OUT) reinterpret_cast<unsigned char*>(a.out)[(frame * ohw + io) * 3 + ch] = render_to_u8(v);
-                else a.out[(frame * 3 + ch) * ohw + io] = v;
+                if (U8OUT) static_cast<unsigned char*>(a.out)[io * 3 + ch] = render_to_u8(v);
+                else static_cast<float*>(a.out)[ch * ohw + io] = v;
             }
         }
     }
+}
+
+template <bool UNION, bool U8OUT>
+__global__ __launch_bounds__(64) void lb_clip_blend_rows_kernel(LbClipArgs a, int hc, int wc, int rs, Gauss21 g) {
+    const long long frame = blockIdx.z;
+    const long long ohw = (long long)hc * wc;
+    LbPass p;
+    p.ref = a.ref + frame * a.ref_fs;
+    p.tgt = a.tgt + frame * a.tgt_fs;
+    p.m1a = a.m1a + frame * a.m_fs;
+    p.m1b = UNION ? a.m1b + frame * a.m_fs : nullptr;
+    p.m2 = a.m2 + frame * a.m_fs;
+    p.mk_out = a.mask1_out ? a.mask1_out + frame * a.mask1_fs : nullptr;
+    p.s = a.scalars + frame * a.sc_fs;
+    p.out = U8OUT ? static_cast<void*>(reinterpret_cast<unsigned char*>(a.out) + frame * ohw * 3)
+                  : static_cast<void*>(a.out + frame * 3 * ohw);
+    lb_blend_strip<UNION, U8OUT>(p, hc, wc, rs, blockIdx.x, blockIdx.y, g);
 }
 
 static Gauss21 lb_gauss() {
@@ -1337,4 +1373,182 @@ extern "C" int ss_render_linear_clip_u8(const unsigned char* const* views_base, 
                                         int wc, int mode, float* ws, void* stream) {
     return render_linear_clip_launch(reinterpret_cast<const void* const*>(views_base), source, T, out, mask1_out, frames, views,
                                      h, w, hc, wc, mode, ws, stream, true);
+}
+
+// ------------------------------------------------------------------------------------------------
+// LINEAR fusion of up to 32 frames that each have their OWN canvas (the current frames of S live streams, or one streaming push:
+// frames = 1): the clip render above with ragged sizes, still three launches (four with three views) whatever `frames` is.  The
+// grids are flattened lists -- all frames' 64 x 8 warp tiles, all frames' 64 x rs blend strips -- and a workgroup finds its frame
+// in a table of per-frame descriptors passed BY VALUE in the kernel arguments (1.4 KB of the 4 KB segment): the arrays are consumed
+// during the call, nothing to copy to the device and nothing whose lifetime a later launch depends on.  The lookup is a binary
+// search over <= 33 prefix sums on the scalar unit (blockIdx is uniform).  Per pixel the device functions of the clip kernels.
+//   ws: W of frame 0, 1, .. [V][4][hc_i][wc_i] | F of frame 0, 1, .. [3][hc_i][wc_i] (V = 3 only) | scalars [n][P][16] u64 |
+//       partials of frame 0, 1, .. [tiles_i][4 waves][P][8] u32          (the clip's layout where the sizes are equal)
+#define LBF_MAX 32
+struct LbFrameTab {
+    int n;
+    unsigned tile0[LBF_MAX + 1];                      // prefix sums of the frames' warp tiles (64 x 8)
+    unsigned strip0[LBF_MAX + 1];                     // prefix sums of the frames' blend strips (64 x rs)
+    unsigned short hc[LBF_MAX], wc[LBF_MAX];
+    long long w_off[LBF_MAX], f_off[LBF_MAX];         // the frame's W / F, floats from ws
+    long long part_off[LBF_MAX];                      // the frame's partials, words from the partials block
+    void* out[LBF_MAX];
+};
+
+// the frame whose range of the flattened grid holds block b: pre[f] <= b < pre[f + 1] (uniform: scalar loads of the table)
+__device__ __forceinline__ int lb_frame_of(const unsigned* pre, int n, unsigned b) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int m = (lo + hi) >> 1;
+        if (b >= pre[m]) lo = m; else hi = m;
+    }
+    return lo;
+}
+
+extern "C" long long ss_linear_frames_workspace_floats(int frames, int views, const int* hc, const int* wc) {
+    if (frames <= 0 || frames > LBF_MAX || (views != 2 && views != 3) || !hc || !wc) return 0;
+    const long long p = views - 1;
+    long long total = 1;                              // (+ 1: as ss_linear_clip_workspace_floats)
+    for (int f = 0; f < frames; ++f) {
+        if (hc[f] < 11 || wc[f] < 11 || hc[f] > 65535 || wc[f] > 65535) return 0;
+        const long long ohw = (long long)hc[f] * wc[f];
+        const long long tiles = (long long)ss_cdiv(wc[f], 64) * ss_cdiv(hc[f], 8);
+        total += views * 4 * ohw + (views == 3 ? 3 * ohw : 0) + p * 32 + tiles * 4 * p * LBC_PW;
+    }
+    return total;
+}
+
+template <int VIEWS, bool U8>
+__global__ __launch_bounds__(256) void lb_frames_warp_kernel(RenderViews rv, const float* __restrict__ source,
+                                                             const float* __restrict__ T, float* __restrict__ ws,
+                                                             unsigned* __restrict__ partials, int h, int w, int mode,
+                                                             long long img_fs, LbFrameTab t) {
+    constexpr int P = VIEWS - 1;
+    const int f = lb_frame_of(t.tile0, t.n, blockIdx.x);
+    const unsigned tile = blockIdx.x - t.tile0[f];
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k)
+        rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + (long long)f * img_fs);
+    lb_warp_tile<VIEWS, U8>(rv, source + (long long)f * (VIEWS * SS_NV * 2), T + (long long)f * (VIEWS * 2 * SS_NT),
+                            ws + t.w_off[f], partials + t.part_off[f] + ((long long)tile * 4) * (P * LBC_PW), tile, h, w,
+                            (int)t.hc[f], (int)t.wc[f], mode);
+}
+
+// one workgroup per (frame, pass)
+__global__ __launch_bounds__(256) void lb_frames_reduce_kernel(const unsigned* __restrict__ partials,
+                                                               unsigned long long* __restrict__ scalars, int passes, LbFrameTab t) {
+    const int f = blockIdx.x / passes, p = blockIdx.x - f * passes;
+    const int tiles = (int)(t.tile0[f + 1] - t.tile0[f]);
+    lb_reduce_pass(partials + t.part_off[f] + p * LBC_PW, (long long)passes * LBC_PW, tiles * 4, ((int)t.wc[f] + 63) / 64,
+                   scalars + (long long)blockIdx.x * 16);
+}
+
+// blend pass 1 (UNION = false; into the frame's output, or into F when a second pass follows) / pass 2 (UNION = true) of every frame
+template <bool UNION, bool U8OUT>
+__global__ __launch_bounds__(64) void lb_frames_blend_rows_kernel(float* __restrict__ ws, const unsigned long long* __restrict__ scalars,
+                                                                  int views, int rs, Gauss21 g, LbFrameTab t) {
+    const int f = lb_frame_of(t.strip0, t.n, blockIdx.x);
+    const int strip = (int)(blockIdx.x - t.strip0[f]);
+    const int hc = t.hc[f], wc = t.wc[f];
+    const int nbx = (wc + 63) / 64;
+    const int by = strip / nbx, bx = strip - by * nbx;
+    const long long ohw = (long long)hc * wc;
+    float* W = ws + t.w_off[f];
+    float* F = ws + t.f_off[f];
+    LbPass a;
+    a.m1a = W + 3 * ohw;
+    a.mk_out = nullptr;
+    if (!UNION) {
+        a.ref = W; a.tgt = W + 4 * ohw;
+        a.m1b = nullptr; a.m2 = W + 7 * ohw;
+        a.s = scalars + (long long)f * (views - 1) * 16;
+        a.out = views == 2 ? t.out[f] : static_cast<void*>(F);
+    } else {
+        a.ref = F; a.tgt = W + 8 * ohw;
+        a.m1b = W + 7 * ohw; a.m2 = W + 11 * ohw;
+        a.s = scalars + ((long long)f * 2 + 1) * 16;
+        a.out = t.out[f];
+    }
+    lb_blend_strip<UNION, U8OUT>(a, hc, wc, rs, bx, by, g);
+}
+
+static int render_linear_frames_launch(const void* const* views_base, const float* source, const float* T, void* const* out,
+                                       int frames, int views, int h, int w, const int* hc, const int* wc, int mode, float* ws,
+                                       void* stream, bool u8) {
+    if (!views_base || !source || !T || !out || !hc || !wc || !ws || frames <= 0 || frames > LBF_MAX || (views != 2 && views != 3) ||
+        h <= 1 || w <= 1 || (mode != SS_WARP_NORMAL && mode != SS_WARP_FAST))
+        return SS_ERR_ARG;
+    if (reinterpret_cast<unsigned long long>(ws) & 7ull) return SS_ERR_ARG;
+    RenderViews rv;
+    for (int i = 0; i < 3; ++i) rv.img[i] = i < views ? static_cast<const float*>(views_base[i]) : nullptr;
+    for (int i = 0; i < views; ++i)
+        if (!rv.img[i]) return SS_ERR_ARG;
+    const int P = views - 1;
+    // rolling blend only (the 64 x 64-tile form of ss_linear_clip_set_rows(r < 0) does not exist here: default strip height)
+    const int rs = g_lb_rows > 0 ? g_lb_rows : 96;
+    LbFrameTab t = {};
+    t.n = frames;
+    long long w_total = 0, f_total = 0, part_total = 0;
+    for (int f = 0; f < frames; ++f) {
+        if (!out[f] || hc[f] < 11 || wc[f] < 11 || hc[f] > 65535 || wc[f] > 65535) return SS_ERR_ARG;
+        const long long ohw = (long long)hc[f] * wc[f];
+        const long long tiles = (long long)ss_cdiv(wc[f], 64) * ss_cdiv(hc[f], 8);
+        const long long strips = (long long)ss_cdiv(wc[f], 64) * ss_cdiv(hc[f], rs);
+        t.hc[f] = (unsigned short)hc[f];
+        t.wc[f] = (unsigned short)wc[f];
+        t.tile0[f + 1] = t.tile0[f] + (unsigned)tiles;
+        t.strip0[f + 1] = t.strip0[f] + (unsigned)strips;
+        t.w_off[f] = w_total;
+        t.f_off[f] = f_total;                         // (relative to the F block; made absolute below)
+        t.part_off[f] = part_total;
+        t.out[f] = out[f];
+        w_total += views * 4 * ohw;
+        f_total += views == 3 ? 3 * ohw : 0;
+        part_total += tiles * 4 * P * LBC_PW;
+    }
+    for (int f = 0; f < frames; ++f) t.f_off[f] += w_total;
+    long long sc_off = w_total + f_total;
+    sc_off += sc_off & 1;                             // 8-byte alignment of the u64 block, as in the clip entry
+    unsigned long long* scalars = reinterpret_cast<unsigned long long*>(ws + sc_off);
+    unsigned* partials = reinterpret_cast<unsigned*>(scalars + (long long)frames * P * 16);
+    hipStream_t st = (hipStream_t)stream;
+    const long long img_fs = u8 ? 3ll * h * w : 12ll * h * w;
+    const dim3 ga(t.tile0[frames]), gr(t.strip0[frames]);
+    if (views == 2) {
+        if (u8) hipLaunchKernelGGL((lb_frames_warp_kernel<2, true>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
+        else hipLaunchKernelGGL((lb_frames_warp_kernel<2, false>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
+    } else {
+        if (u8) hipLaunchKernelGGL((lb_frames_warp_kernel<3, true>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
+        else hipLaunchKernelGGL((lb_frames_warp_kernel<3, false>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
+    }
+    hipLaunchKernelGGL(lb_frames_reduce_kernel, dim3(frames * P), dim3(256), 0, st, (const unsigned*)partials, scalars, P, t);
+    const Gauss21 g = lb_gauss();
+    const unsigned long long* sc = scalars;
+    if (views == 2) {
+        if (u8) hipLaunchKernelGGL((lb_frames_blend_rows_kernel<false, true>), gr, dim3(64), 0, st, ws, sc, views, rs, g, t);
+        else hipLaunchKernelGGL((lb_frames_blend_rows_kernel<false, false>), gr, dim3(64), 0, st, ws, sc, views, rs, g, t);
+    } else {
+        hipLaunchKernelGGL((lb_frames_blend_rows_kernel<false, false>), gr, dim3(64), 0, st, ws, sc, views, rs, g, t);
+        if (u8) hipLaunchKernelGGL((lb_frames_blend_rows_kernel<true, true>), gr, dim3(64), 0, st, ws, sc, views, rs, g, t);
+        else hipLaunchKernelGGL((lb_frames_blend_rows_kernel<true, false>), gr, dim3(64), 0, st, ws, sc, views, rs, g, t);
+    }
+    return ss_launch_status();
+}
+
+// `frames` frames with their own canvases, LINEAR fusion: view k's frame f at views_base[k] + f * 3 h w floats (planar fp32
+// [n,3,h,w]) -> out[f] = [3][hc[f]][wc[f]]; hc / wc / out: host arrays of `frames` entries, consumed during the call;
+// ws: ss_linear_frames_workspace_floats(...) floats
+extern "C" int ss_render_linear_frames(const float* const* views_base, const float* source, const float* T, float* const* out,
+                                       int frames, int views, int h, int w, const int* hc, const int* wc, int mode, float* ws,
+                                       void* stream) {
+    return render_linear_frames_launch(reinterpret_cast<const void* const*>(views_base), source, T,
+                                       reinterpret_cast<void* const*>(out), frames, views, h, w, hc, wc, mode, ws, stream, false);
+}
+
+// the same from decoded uint8 frames [n,h,w,3] per view to uint8 video frames out[f] = [hc[f]][wc[f]][3]
+extern "C" int ss_render_linear_frames_u8(const unsigned char* const* views_base, const float* source, const float* T,
+                                          unsigned char* const* out, int frames, int views, int h, int w, const int* hc,
+                                          const int* wc, int mode, float* ws, void* stream) {
+    return render_linear_frames_launch(reinterpret_cast<const void* const*>(views_base), source, T,
+                                       reinterpret_cast<void* const*>(out), frames, views, h, w, hc, wc, mode, ws, stream, true);
 }

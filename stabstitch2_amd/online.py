@@ -303,6 +303,7 @@ class _Stitcher:
     now from the caller's frames with the direct render, else copies of the graph's output).  A subclass provides _load, _step_static
     and the window-fill push; one with S canvases also _regrown / _render_direct / overflow_report."""
     _U8_STEADY = True        # push_u8 in the steady state: the resize writes the graph's LR inputs, the render samples the uint8 frames
+    _LINEAR_DIRECT = True    # may LINEAR fusion take the direct render (DIRECT_LINEAR)?  Not with two pushes in flight (_TwoInFlight)
 
     def __init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only=False, canvases=1):
         if grow not in ('never', 'recapture'):
@@ -316,7 +317,9 @@ class _Stitcher:
         self.warp_mode, self.fusion_mode = warp_mode, fusion_mode
         self.use_graph = use_graph
         self.meshes_only = bool(meshes_only)
-        self._direct_render = bool(DIRECT_RENDER and use_graph and fusion_mode == 'AVERAGE' and not self.meshes_only)
+        direct = fusion_mode == 'AVERAGE' or (fusion_mode == 'LINEAR' and DIRECT_LINEAR and self._LINEAR_DIRECT)
+        self._direct_render = bool(DIRECT_RENDER and use_graph and direct and not self.meshes_only)
+        self._lin_ws = {}                # direct LINEAR render: chunk -> ((canvas sizes, views), workspace), re-made when a canvas changes
         self.watch = _CanvasWatch(canvases, margin, self.dev)      # overflow of the fixed canvas(es); meshes_only: never started
         self.static = None               # steady-state buffers (inputs, rings, output) once the window is full
         self.graph = None
@@ -386,8 +389,8 @@ class _Stitcher:
             B['graph'] = None
 
     def _direct(self):
-        """Does the steady-state push launch its AVERAGE render itself, outside the graph, on the caller's frames (DIRECT_RENDER)?
-        Decided when the stitcher is built."""
+        """Does the steady-state push launch its render itself, outside the graph, on the caller's frames (DIRECT_RENDER; LINEAR
+        fusion: DIRECT_LINEAR too, plain stitchers only)?  Decided when the stitcher is built."""
         return self._direct_render
 
     def _u8_steady(self):
@@ -423,7 +426,7 @@ class _Stitcher:
         return self._take(self._deferred_splines(), self.static['out'], u8 or frames[:len(frames) // 2], u8 is not None)
 
     def _deferred_splines(self):
-        """Direct render: the splines and footprints (src, T, footprint) the step left for the push's render."""
+        """Direct render: the splines and footprints (src, T, footprint; LINEAR: None) the step left for the push's render."""
         return getattr(self, '_deferred', None)
 
     def _take(self, deferred, out, imgs, u8):
@@ -448,6 +451,9 @@ class _Stitcher:
                 self._deferred = (src, T, fp)
                 return None
             return ops.render_average(imgs, src, T, self.hc, self.wc, self.warp_mode, out=out, footprint=fp)
+        if out is _DEFER:                    # LINEAR: the graph ends with the splines and the watcher
+            self._deferred = (src, T, None)
+            return None
         w = ops.tps_warp_views(imgs, src, T, self.hc, self.wc, self.warp_mode)        # [V,4,Hc,Wc]
         res = ops.linear_blend(w[0, 0:3], w[1, 0:3], w[0, 3], w[1, 3])
         if len(imgs) == 3:
@@ -463,10 +469,25 @@ class _Stitcher:
     def _render_direct(self, deferred, imgs, u8):
         """One canvas, two or three views."""
         src, T, fp = deferred
+        if self.fusion_mode == 'LINEAR':     # the fused three / four launches at n = 1, uint8 frames in -> the uint8 video frame out
+            shp = (1, self.h, self.w, 3) if u8 else (1, 3, self.h, self.w)
+            return self._render_linear([f.reshape(shp) for f in imgs], src[None], T[None], [(self.hc, self.wc)])
         if u8:                           # uint8 frames in, the uint8 video frame out: no fp32 frame planes, no fp32 canvas
             return [ops.render_average_u8(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp)]
         shp = (1, 3, self.h, self.w)
         return [ops.render_average([f.reshape(shp) for f in imgs], src, T, self.hc, self.wc, self.warp_mode, footprint=fp)]
+
+    def _render_linear(self, views, src, T, sizes):
+        """Direct LINEAR render of n frames on their own canvases `sizes` (ops.render_linear_frames, <= 32 frames per call) with
+        the workspaces this stitcher holds; they are re-made when a canvas is set or regrown (the sizes are their key)."""
+        res = []
+        for c in range(0, len(sizes), 32):
+            key = (tuple(sizes[c:c + 32]), len(views))
+            if self._lin_ws.get(c, (None, None))[0] != key:
+                self._lin_ws[c] = (key, ops.linear_frames_workspace(key[0], key[1], self.dev))
+            res += ops.render_linear_frames([f[c:c + 32].contiguous() for f in views], src[c:c + 32], T[c:c + 32], key[0],
+                                            self.warp_mode, ws=self._lin_ws[c][1])
+        return res
 
     # ------------------------------------------------------------------ k frames of every view per call (one canvas)
     # A subclass provides _push (one plain push), push_u8, _batch_buffers (the per-k work buffers, 'lr' [V,k,3,360,480] among
@@ -688,7 +709,7 @@ class OnlineStitcher(_Stitcher):
         """One DECODED frame pair: img* uint8 [H,W,3] device tensors in cv2.imread's layout and channel order (the reference's frame
         loop, test_online_tra.py:252-278) -> list of stitched VIDEO frames uint8 [Hc,Wc,3] (`.astype(np.uint8)` of the fused values,
         :413), empty for the first 6 pushes, 7 frames on the 7th, then one per push.  Byte for byte ops.ingest_u8 -> push ->
-        ops.canvas_to_u8; in the steady state (DIRECT_RENDER, fusion AVERAGE) the cv2-exact resize writes the graph's LR inputs and
+        ops.canvas_to_u8; in the steady state (direct render: AVERAGE, or LINEAR with DIRECT_LINEAR) the cv2-exact resize writes the graph's LR inputs and
         the render samples the uint8 frames and writes the uint8 frame itself: no fp32 frame planes, no fp32 canvas.
         PipelinedOnlineStitcher: the frames of the PREVIOUS push come back, `flush_u8()` for the last; a stream is fed through
         push_u8 or through push, not both."""
@@ -834,6 +855,11 @@ BATCH_GRAPHS = 4                       # batch sizes whose steady-state graphs (
 # views: 66 + 50 MB of HBM traffic, ~35 us of a 1.1 ms push).  Same kernel, same operands: frames bit-identical.  Read when a stitcher
 # is constructed.
 DIRECT_RENDER = os.environ.get('SS_DIRECT_RENDER', '1') != '0'
+# LINEAR fusion joins it (OnlineStitcher, MultiOnlineStitcher, ThreeViewOnlineStitcher): the graph ends with the splines and the
+# watcher, the push renders through ops.render_linear_frames -- three launches (four with three views) for all S streams of a
+# MultiOnlineStitcher, whatever their canvas sizes, instead of the per-frame chain warp + 7 blender launches + copy per stream; under
+# push_u8 from the uint8 frames to the uint8 video frame.  Bit-identical frames.  Read when a stitcher is constructed.
+DIRECT_LINEAR = os.environ.get('SS_DIRECT_LINEAR', '1') != '0'
 _DEFER = object()                      # `out=_DEFER`: compute splines and footprints, leave the render launch to the push
 FUSED_SPLINES = os.environ.get('SS_FUSED_SPLINES', '1') != '0'   # ThreeViewOnlineStitcher: composition + splines in one launch
 PIPE_STREAM_CANDIDATES = 5        # streams tried pairwise by _TwoInFlight._pick_streams
@@ -850,7 +876,10 @@ class _TwoInFlight:
     HIP graph per buffer parity; hand-over buffers are double-buffered, events order the halves.  Per frame the launches and their
     operands are the plain stitcher's: results are bit-identical.  What changes is WHEN a result is handed out: `push` returns the
     frames of the PREVIOUS push (valid on the caller's stream), `flush()` the last ones.
+    LINEAR fusion stays inside the graphs here (_LINEAR_DIRECT = False): with two pushes in flight the direct LINEAR render would
+    need a workspace per buffer parity.
     A subclass provides _pipe_alloc / _pipe_load / _run_a / _run_b (and _pipe_empty for S streams)."""
+    _LINEAR_DIRECT = False
 
     def _pipe_init(self):
         if not L.QUAD:
@@ -1012,7 +1041,7 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
         for pair in stream: for frame in st.push(*pair): ...
         for frame in st.flush(): ...
     0.64 ms per push = 1559 frames/s at 720p against 0.85 ms / 1171.  The canvas is fixed after the first window (grow='never';
-    overflow is counted as in OnlineStitcher)."""
+    overflow is counted as in OnlineStitcher).  LINEAR fusion renders inside the graphs (no direct LINEAR render: _TwoInFlight)."""
 
     def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE', deterministic=False):
         OnlineStitcher.__init__(self, nets, height, width, canvas, margin, warp_mode, fusion_mode, use_graph=True, grow='never',
@@ -1148,9 +1177,13 @@ class MultiOnlineStitcher(_Stitcher):
     def _alloc_outputs(self):
         st, S, d = self.static, self.S, self.dev
         st['out_all'] = None
+        linear_direct = self._direct() and self.fusion_mode == 'LINEAR'      # the push renders all streams into fresh tensors
         if len({(s.hc, s.wc) for s in self.single}) == 1:       # equal canvas sizes: one render launch for all streams
-            st['out_all'] = torch.empty((S, 3, self.single[0].hc, self.single[0].wc), device=d)
-            st['out'] = [st['out_all'][s] for s in range(S)]
+            # (out_all is also the mark of that case: where nothing is rendered into it, its shape alone, without memory)
+            st['out_all'] = torch.empty((S, 3, self.single[0].hc, self.single[0].wc), device='meta' if linear_direct else d)
+            st['out'] = None if linear_direct else [st['out_all'][s] for s in range(S)]
+        elif linear_direct:
+            st['out'] = None
         else:
             st['out'] = [torch.empty((3, s.hc, s.wc), device=d) for s in self.single]
 
@@ -1240,6 +1273,9 @@ class MultiOnlineStitcher(_Stitcher):
             watch = self.watch.args()
         else:
             ops.canvas_watch(src, self.watch.wi, self.watch.wf, self.watch.guard)
+        if defer and self.fusion_mode == 'LINEAR':        # equal or different canvas sizes: one ragged render, launched by the push
+            self._deferred = (src, T, None)
+            return
         if out_all is not None:
             # all streams render onto canvases of ONE size (e.g. the caller fixed them): the S current frames are a clip
             hc, wc = self.single[0].hc, self.single[0].wc
@@ -1257,15 +1293,18 @@ class MultiOnlineStitcher(_Stitcher):
                                watch=None if watch is None else self.watch.args(s))
 
     def _deferred_splines(self):
-        if self.static['out_all'] is not None:
+        if self.static['out_all'] is not None or self.fusion_mode == 'LINEAR':
             return getattr(self, '_deferred', None)
         return [getattr(one, '_deferred', None) for one in self.single]
 
     def _render_direct(self, deferred, imgs, u8):
-        """S canvases, two views: one clip-style launch when the canvases share a size, else one launch per stream."""
+        """S canvases, two views.  AVERAGE: one clip-style launch when the canvases share a size, else one launch per stream."""
         S = self.S
         if not u8:
             imgs = [f.reshape(S, 3, self.h, self.w) for f in imgs]
+        if self.fusion_mode == 'LINEAR':     # ONE ragged render over the S streams' own canvases (chunks of 32 streams)
+            src, T, _ = deferred
+            return [[f] for f in self._render_linear(list(imgs), src, T, self.canvas_sizes)]
         if self.static['out_all'] is not None:
             src, T, fp = deferred
             one = self.single[0]
@@ -1330,7 +1369,8 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
         st = PipelinedMultiOnlineStitcher(nets, H, W, streams=8)
         for batch in source: per_stream = st.push(*batch)        # S lists: [] x 6, 7 frames, [] (one push of lag), then 1 frame each
         per_stream = st.flush()
-    Canvases are fixed after the first window (grow='never')."""
+    Canvases are fixed after the first window (grow='never').  LINEAR fusion renders inside the graphs, stream by stream (no direct
+    LINEAR render: _TwoInFlight)."""
     _U8_STEADY = False       # push_u8: ingest_u8 -> push -> canvas_to_u8
 
     def __init__(self, nets, height, width, streams, canvases=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
@@ -1607,7 +1647,8 @@ class ThreeViewOnlineStitcher(_Stitcher):
 class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
     """ThreeViewOnlineStitcher with TWO pushes in flight (round 6; opt-in; see _TwoInFlight): the three views' trunks and the two
     pairs' stage-1 heads of triple t + 1 run beside triple t's regressor heads, smoothing, composition and three-image render.  Frames
-    bit-identical to ThreeViewOnlineStitcher's, handed out one push late (`flush()` for the last); boxes fixed after the first window."""
+    bit-identical to ThreeViewOnlineStitcher's, handed out one push late (`flush()` for the last); boxes fixed after the first window.
+    LINEAR fusion renders inside the graphs (no direct LINEAR render: _TwoInFlight)."""
     _U8_STEADY = False       # push_u8: ingest_u8 -> push -> canvas_to_u8
 
     def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE'):

@@ -1011,6 +1011,48 @@ def render_linear_clip(views, source, T, hc, wc, mode='NORMAL', out=None, want_m
     return (out, mk) if want_masks else out
 
 
+def linear_frames_workspace(sizes, views, device):
+    """Workspace of render_linear_frames for these canvases [(hc, wc)] (a stitcher holds it across pushes)."""
+    n = len(sizes)
+    hcs = (ctypes.c_int * n)(*[int(s[0]) for s in sizes])
+    wcs = (ctypes.c_int * n)(*[int(s[1]) for s in sizes])
+    need = int(H.lib().ss_linear_frames_workspace_floats(n, views, hcs, wcs))
+    if need <= 0:
+        raise ValueError('render_linear_frames: 1..32 frames of 2|3 views on canvases of 11..65535 pixels a side, got %d x %d views on %s'
+                         % (n, views, list(sizes)))
+    return torch.empty(need, device=device, dtype=torch.float32)
+
+
+def render_linear_frames(views, source, T, sizes, mode='NORMAL', outs=None, ws=None):
+    """LINEAR fusion of n frames that each have their OWN canvas in three launches (four with three views) whatever n is: views =
+    list of 2|3 contiguous device tensors [n,3,h,w] fp32 -> list of n frames [3,hc_i,wc_i]; or [n,h,w,3] uint8 -> the uint8 video
+    frames [hc_i,wc_i,3].  source [n,V,63,2]; T [n,V,2,66]; sizes = n pairs (hc, wc); 1 <= n <= 32.  outs: n tensors to write;
+    ws: linear_frames_workspace(sizes, V, device).  Bit-identical, frame by frame, to render_linear_clip called with that one
+    frame on that canvas."""
+    v = len(views)
+    u8 = views[0].dtype == torch.uint8
+    if u8:
+        n, h, w, _ = views[0].shape
+        assert all(tuple(t.shape) == (n, h, w, 3) for t in views)
+    else:
+        n, _, h, w = views[0].shape
+        assert all(tuple(t.shape) == (n, 3, h, w) for t in views)
+    assert source.shape[0] == n and T.shape[0] == n and len(sizes) == n
+    dev, dt = views[0].device, views[0].dtype
+    sizes = [(int(a), int(b)) for a, b in sizes]
+    shapes = [(hc, wc, 3) if u8 else (3, hc, wc) for hc, wc in sizes]
+    if outs is None:
+        outs = [torch.empty(shp, device=dev, dtype=dt) for shp in shapes]
+    assert len(outs) == n and all(tuple(o.shape) == shp and o.dtype == dt for o, shp in zip(outs, shapes))
+    if ws is None:
+        ws = linear_frames_workspace(sizes, v, dev)
+    hcs = (ctypes.c_int * n)(*[s[0] for s in sizes])
+    wcs = (ctypes.c_int * n)(*[s[1] for s in sizes])
+    H.call('ss_render_linear_frames_u8' if u8 else 'ss_render_linear_frames', H.ptr_array(views, dtype=dt), H.dptr(_f(source)),
+           H.dptr(T), H.ptr_array(outs, dtype=dt), n, v, h, w, hcs, wcs, MODES[mode], H.dptr(ws), H.stream())
+    return list(outs)
+
+
 def mesh_bbox(meshes, img_h, img_w, bbox=None):
     """meshes: list of LR-scale tensors [...,2] -> device tensor [4] = wmin, wmax, hmin, hmax (HR px).
     bbox: an existing box to fold these meshes into (in place)."""
