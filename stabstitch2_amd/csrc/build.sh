@@ -2,7 +2,9 @@
 # Build libstabstitch_hip.so for gfx950 (MI355X) in-tree.
 #   stabstitch2_amd/csrc/build.sh           -> stabstitch2_amd/libstabstitch_hip.so         (the product)
 #   stabstitch2_amd/csrc/build.sh tuning    -> tools/libstabstitch_hip_tuning.so            (-DSS_TUNING: adds the
-#       ss_debug_set / ss_debug_ptr knobs and the per-workgroup s_memtime stamps used by tools/ab_*.py, diag_phases.py)
+#       ss_debug_set / ss_debug_ptr knobs, the per-workgroup s_memtime stamps of tools/diag_*.py and the comparison kernels
+#       that tests and tools/ab_*.py measure the product against; concluded experiments are not kept in it: LAB_NOTES.md,
+#       "Retired experiment code")
 # -ffp-contract=off: the samplers reproduce the reference's separate mul/add sequence (its out-of-range taps cancel
 # exactly only without fma contraction); every intended fma is an explicit fmaf()/MFMA in the sources.
 set -e

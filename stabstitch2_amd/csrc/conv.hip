@@ -507,9 +507,7 @@ static int g_ablate = 0;            // key 1: ablation mask
 static int g_split_target = 512;    // key 2: workgroups a split-K launch aims for
 unsigned long long* ss_tuning_dbg = nullptr;
 extern int g_wino_nb1_max_cin, g_wino_ablate, g_wino_variant;
-extern int g_wino_knob[4];
-extern int g_wino_lds_pad;
-extern int g_w43_ablate;
+extern int g_stem_kernel;
 #define g_dbg ss_tuning_dbg
 extern "C" SS_API void ss_debug_ptr(void* ptr) { g_dbg = (unsigned long long*)ptr; }
 extern "C" SS_API void ss_debug_set(int key, int value) {
@@ -518,12 +516,11 @@ extern "C" SS_API void ss_debug_set(int key, int value) {
     if (key == 2) g_split_target = value;
     if (key == 3) g_amode_off = value;
     if (key == 4) g_lds_pad = value;
-    if (key == 6) g_wino_ablate = value;           // Winograd ablations (wrong results): 1 no filter loads, 2 no transform, 4 no epilogue
-    if (key == 7) g_wino_variant = value;          // Winograd kernel: 0 auto, 1 one tile block per workgroup, 2 pair kernel
     if (key == 5) g_wino_nb1_max_cin = value;      // Winograd: 32-channel blocks (3 workgroups / CU) up to this cin
-    if (key == 20) g_wino_lds_pad = value;
-    if (key == 21) g_w43_ablate = value;           // F(4x4,3x3) K-loop ablations (timing only)
-    if (key >= 16 && key < 20) g_wino_knob[key - 16] = value;      // Winograd round-3 experiments (see WinoP::knob)
+    if (key == 6) g_wino_ablate = value;           // Winograd ablations (wrong results): 1 no filter loads, 2 no raw loads / LDS /
+                                                   // transform (both: alternating schedule only), 4 no epilogue
+    if (key == 7) g_wino_variant = value;          // Winograd schedule: 0 stream (dispatched), 1 phase-alternating
+    if (key == 18) g_stem_kernel = value;          // stem: 2 = the two-halves-per-workgroup kernel
 }
 #else
 constexpr int g_lds_pad = 0, g_amode_off = 0, g_force_tile = 0;

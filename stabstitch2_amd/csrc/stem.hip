@@ -60,13 +60,11 @@ struct StemP {
     unsigned in_bytes, pk_bytes;
 #ifdef SS_TUNING
     unsigned long long* dbg;     // per-workgroup phase stamps (tools/diag_stem.py)
-    int stagger;
 #endif
 };
 
 #ifdef SS_TUNING
-extern int g_wino_lds_pad;
-extern int g_wino_knob[4];
+int g_stem_kernel = 0;           // ss_debug_set key 18: 2 = the two-halves-per-workgroup kernel (tools/ab_stem_split.py)
 #define SP_STAMP(i) do { if (p.dbg) ts[i] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define SP_STAMP(i) do { } while (0)
@@ -100,14 +98,6 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(StemP p) {
     // prologue and epilogue are VALU / LDS work that shares its SIMD with the OTHER resident workgroup's dense MFMA stream: at
     // equal priority each of their instructions waits for an MFMA boundary (64 clocks).  Raised priority lets them through.
     __builtin_amdgcn_s_setprio(3);
-#ifdef SS_TUNING
-    // experiment (ss_debug_set key 16, units of 1024 clocks): the second resident workgroup of a CU (LDS base != 0) sleeps in the
-    // FIRST round so that the two run in anti-phase (all workgroups have the same length: left alone they stay in lock-step)
-    if (p.stagger > 0 && blockIdx.x < 512u && (__builtin_amdgcn_s_getreg((31 << 11) | 6) & 0x1FFu) != 0u) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        while (__builtin_amdgcn_s_memtime() - t0 < (unsigned long long)p.stagger * 1024ull) __builtin_amdgcn_s_sleep(32);
-    }
-#endif
 
     // consecutive workgroups = the filter banks of one tile (they read the same patch), then the next tile of the image
     const unsigned lin = blockIdx.x;
@@ -523,13 +513,7 @@ extern "C" int ss_stem_pool(const float* in_padded, const float* packed, const f
     p.pk_bytes = (unsigned)(ss_stem_pool_packed_floats(groups) * 4);
 #ifdef SS_TUNING
     p.dbg = ss_tuning_dbg;
-    p.stagger = g_wino_knob[0];
-    const unsigned dyn = (unsigned)g_wino_lds_pad;          // ss_debug_set key 20: extra LDS -> one workgroup per CU (experiments)
-#else
-    const unsigned dyn = 0u;
-#endif
-#ifdef SS_TUNING
-    const bool split = g_wino_knob[2] != 2;                  // ss_debug_set(18, 2): the two-halves-per-workgroup kernel
+    const bool split = g_stem_kernel != 2;
 #else
     const bool split = SP_SPLIT_DEFAULT;
 #endif
@@ -540,7 +524,7 @@ extern "C" int ss_stem_pool(const float* in_padded, const float* packed, const f
         p.ntiles = (unsigned)tiles;
         hipLaunchKernelGGL(stem_pool_kernel_half, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
     } else {
-        hipLaunchKernelGGL(stem_pool_kernel, dim3((unsigned)wgs), dim3(256), dyn, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(stem_pool_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, p);
     }
     return ss_launch_status();
 }

@@ -517,7 +517,7 @@ def wino_blocks(h, w):
 def wino2_kernel(h, w, res=False, pool=False, sliced=False):
     tbh, tbw = wino_blocks(h, w)
     if pool:
-        return 'conv_wino_kernel<%d,%d,2,0,1,0,8>' % (tbh, tbw)
+        return 'conv_wino_kernel<%d,%d,2,0,1,0,1>' % (tbh, tbw)
     return 'conv_wino_kernel<%d,%d,2,%d,%d,%d,0>' % (tbh, tbw, int(res), int(not sliced), int(sliced))
 
 

@@ -54,36 +54,39 @@ def test_cabi_exports_exactly_the_declared_symbols(built_lib):
 
 
 def test_no_matrix_kernel_spills_or_uses_scratch(built_lib):
-    """Every gfx950 code object of the built library, read back from its metadata notes (tools/kernel_resources.py): a kernel that
-    issues MFMA instructions must have .vgpr_spill_count = 0 and no private segment, and at most 8 spilled SGPRs (those go to VGPR
-    lanes, not to memory: see the comment at the assertion).  Twice a VGPR spill shipped
-    unnoticed (round 4: 47 registers of conv_wino43_kernel, 114 KB of scratch stores per workgroup; round 5: 7 of
+    """Every gfx950 code object of the product library AND of the tuning library (tools/libstabstitch_hip_tuning.so, built the way
+    tools/_tuning.py builds it if it is missing: three GPU tests load it), read back from its metadata notes
+    (tools/kernel_resources.py): a kernel that issues MFMA instructions must have .vgpr_spill_count = 0 and no private segment, and
+    at most 8 spilled SGPRs (those go to VGPR lanes, not to memory: see the comment at the assertion).  Twice a VGPR spill shipped
+    unnoticed (round 4: 47 registers of the first F(4x4,3x3) kernel, 114 KB of scratch stores per workgroup; round 5: 7 of
     stem_pool_kernel_half with a scratch_load inside its MFMA stream)."""
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     try:
         import kernel_resources
+        import _tuning
     finally:
         sys.path.pop(0)
     from stabstitch2_amd import _hip
     if not os.path.exists(os.path.join(kernel_resources.LLVM, 'llvm-readelf')):
         pytest.skip('no llvm-readelf in this image')
-    ks = kernel_resources.kernels(_hip.LIB_PATH)
-    mfma = {k: v for k, v in ks.items() if v['mfma_instructions'] > 0}
-    assert len(ks) >= 60 and len(mfma) >= 30, (len(ks), len(mfma))
-    for want in ('conv_igemm_kernel', 'conv_wino_kernel', 'conv_wino43p_kernel', 'stem_pool_kernel_half'):
-        assert any(want in k for k in mfma), want
-    # (SGPR spills go to VGPR lanes -- v_writelane / v_readlane, no memory: the persistent F(4x4,3x3) kernel parks up to six
-    # block-loop scalars that way outside its K loop; what must never ship is a VGPR spilled to scratch memory)
-    bad = {k: (v.get('.vgpr_spill_count', 0), v.get('.private_segment_fixed_size', 0))
-           for k, v in mfma.items() if v.get('.vgpr_spill_count', 0) or v.get('.private_segment_fixed_size', 0)}
-    assert not bad, 'MFMA kernels with VGPR spills / scratch (vgpr spills, scratch bytes): %s' % bad
-    assert max(v.get('.sgpr_spill_count', 0) for v in mfma.values()) <= 8
-    # the register budgets the occupancy arguments of DESIGN.md rest on
-    half = next(v for k, v in ks.items() if 'stem_pool_kernel_half' in k)
-    assert half['.vgpr_count'] + half.get('.agpr_count', 0) <= 128          # four workgroups of 256 threads per CU
-    for k, v in ks.items():
-        if 'conv_wino43' in k:               # (both the persistent and the one-block-per-workgroup kernel)
-            assert v['.vgpr_count'] <= 256 and v.get('.vgpr_spill_count', 0) == 0, k
+    for lib_path in (_hip.LIB_PATH, _tuning.ensure_built()):
+        ks = kernel_resources.kernels(lib_path)
+        mfma = {k: v for k, v in ks.items() if v['mfma_instructions'] > 0}
+        assert len(ks) >= 60 and len(mfma) >= 30, (lib_path, len(ks), len(mfma))
+        for want in ('conv_igemm_kernel', 'conv_wino_kernel', 'conv_wino43p_kernel', 'stem_pool_kernel_half'):
+            assert any(want in k for k in mfma), (lib_path, want)
+        # (SGPR spills go to VGPR lanes -- v_writelane / v_readlane, no memory: the persistent F(4x4,3x3) kernel parks up to six
+        # block-loop scalars that way outside its K loop; what must never ship is a VGPR spilled to scratch memory)
+        bad = {k: (v.get('.vgpr_spill_count', 0), v.get('.private_segment_fixed_size', 0))
+               for k, v in mfma.items() if v.get('.vgpr_spill_count', 0) or v.get('.private_segment_fixed_size', 0)}
+        assert not bad, '%s: MFMA kernels with VGPR spills / scratch (vgpr spills, scratch bytes): %s' % (lib_path, bad)
+        assert max(v.get('.sgpr_spill_count', 0) for v in mfma.values()) <= 8, lib_path
+        # the register budgets the occupancy arguments of DESIGN.md rest on
+        half = next(v for k, v in ks.items() if 'stem_pool_kernel_half' in k)
+        assert half['.vgpr_count'] + half.get('.agpr_count', 0) <= 128, lib_path      # four workgroups of 256 threads per CU
+        for k, v in ks.items():
+            if 'conv_wino43' in k:
+                assert v['.vgpr_count'] <= 256 and v.get('.vgpr_spill_count', 0) == 0, (lib_path, k)
 
 
 def test_product_never_imports_oracle_and_fails_without_gpu():

@@ -10,11 +10,16 @@ sys.path.insert(0, ROOT)
 PATH = os.path.join(ROOT, 'tools', 'libstabstitch_hip_tuning.so')
 
 
-def lib():
-    from stabstitch2_amd import _hip
+def ensure_built():
+    """-> path of the tuning library, built first if it is missing."""
     if not os.path.exists(PATH):
         subprocess.run(['bash', os.path.join(ROOT, 'stabstitch2_amd', 'csrc', 'build.sh'), 'tuning'], check=True)
-    h = ctypes.CDLL(PATH)
+    return PATH
+
+
+def lib():
+    from stabstitch2_amd import _hip
+    h = ctypes.CDLL(ensure_built())
     for name, (res, args) in _hip.SIGNATURES.items():
         fn = getattr(h, name)
         fn.restype = res

@@ -4,7 +4,15 @@
 The .so carries one clang offload bundle per translation unit in its .hip_fatbin section; each bundle's gfx950 entry is an ELF
 whose NT_AMDGPU_METADATA note lists, per kernel, .vgpr_count / .agpr_count / .sgpr_count / .vgpr_spill_count / .sgpr_spill_count /
 .private_segment_fixed_size (scratch bytes per lane) / .group_segment_fixed_size (static LDS).  tests/test_host_logic.py holds the
-MFMA kernels to zero spills and zero scratch with `kernels()` below."""
+MFMA kernels to zero spills and zero scratch with `kernels()` below.
+
+    python tools/kernel_resources.py --digest [lib]            per kernel: sha256 of its instruction stream, demangled name
+    python tools/kernel_resources.py --digest-masked [lib]     the same with the offsets of the kernel-argument loads masked
+The check for a source-only edit of the kernels (dead code removed, a template parameter renamed): build the library before and
+after with the same compiler and compare the lists -- equal digests are equal machine code.  An edit that moves fields of a
+kernel's argument struct shifts the offsets of its argument loads and nothing else: compare the masked lists (and the register /
+LDS budgets of the table above)."""
+import hashlib
 import os
 import re
 import struct
@@ -84,20 +92,76 @@ def kernels(lib_path):
                 name = e.get('.name', base)
                 e['mfma_instructions'] = mfma.get(base, 0)
                 res[name] = e
-    names = list(res)
-    try:
-        dem = subprocess.run([os.path.join(LLVM, 'llvm-cxxfilt')] + names, check=True, capture_output=True, text=True).stdout.splitlines()
-        if len(dem) == len(names):
-            res = {d_: res[n] for d_, n in zip(dem, names)}
-    except Exception:
-        pass
-    return res
+    return _demangled(res)
+
+
+def _demangled(by_symbol):
+    names = list(by_symbol)
+    for tool in (os.path.join(LLVM, 'llvm-cxxfilt'), 'c++filt'):      # (not every ROCm install carries llvm-cxxfilt)
+        try:
+            dem = subprocess.run([tool] + names, check=True, capture_output=True, text=True).stdout.splitlines()
+            if len(dem) == len(names):
+                return {d_: by_symbol[n] for d_, n in zip(dem, names)}
+        except Exception:
+            pass
+    return by_symbol
+
+
+def digests(lib_path, mask_kernarg_offsets=False):
+    """-> {demangled kernel name: sha256 hex digest of its instruction stream}: mnemonics and operands in order, without addresses,
+    encodings and comments (branch operands are relative, so a kernel's digest does not depend on where it lies).
+    mask_kernarg_offsets: the immediate offset of every scalar load whose base is the kernel-argument pointer (the user SGPR pair
+    the kernel descriptor assigns to it) reads `KARG`."""
+    res = {}
+    with tempfile.TemporaryDirectory() as d:
+        for i, elf in enumerate(code_objects(lib_path)):
+            f = os.path.join(d, 'co%d.elf' % i)
+            open(f, 'wb').write(elf)
+            # kernel descriptors: which kernels there are, and the SGPR pair that holds the kernel-argument pointer at entry
+            # (user SGPRs in the order private segment buffer (4), dispatch pointer (2), queue pointer (2), kernel arguments (2))
+            kd = subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '-D', '-j', '.rodata', f], check=True, capture_output=True, text=True).stdout
+            karg = {}
+            sym = None
+            for line in kd.splitlines():
+                m = re.match(r'^\.amdhsa_kernel (\S+)', line)
+                if m:
+                    sym = m.group(1)
+                    karg[sym] = 0
+                    continue
+                m = re.match(r'^\s*\.amdhsa_user_sgpr_(private_segment_buffer|dispatch_ptr|queue_ptr) (\d+)', line)
+                if m and sym is not None and int(m.group(2)):
+                    karg[sym] += 4 if m.group(1) == 'private_segment_buffer' else 2
+            dis = subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '-d', '--no-show-raw-insn', f], check=True, capture_output=True, text=True).stdout
+            sym = None
+            for line in dis.splitlines():
+                m = re.match(r'^[0-9a-f]+ <([^>]+)>:', line)
+                if m:
+                    sym = m.group(1) if m.group(1) in karg else None
+                    if sym is not None:
+                        res[sym] = hashlib.sha256()
+                        base = 's[%d:%d]' % (karg[sym], karg[sym] + 1)
+                    continue
+                ins = ' '.join(line.split('//')[0].split())
+                if sym is None or not ins:
+                    continue
+                if mask_kernarg_offsets:
+                    m = re.match(r'^(s_load_dword\w* \S+ ' + re.escape(base) + r',) \S+(.*)$', ins)
+                    if m:
+                        ins = m.group(1) + ' KARG' + m.group(2)
+                res[sym].update((ins + '\n').encode())
+    return _demangled({k: v.hexdigest() for k, v in res.items()})
 
 
 def main():
-    lib = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith('-') else os.path.join(
-        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'stabstitch2_amd', 'libstabstitch_hip.so')
-    pat = sys.argv[2] if len(sys.argv) > 2 else ''
+    args = sys.argv[1:]
+    default_lib = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'stabstitch2_amd', 'libstabstitch_hip.so')
+    if args and args[0] in ('--digest', '--digest-masked'):
+        ds = digests(args[1] if len(args) > 1 else default_lib, mask_kernarg_offsets=args[0] == '--digest-masked')
+        for name in sorted(ds):
+            print('%s  %s' % (ds[name], name))
+        return
+    lib = args[0] if args and not args[0].startswith('-') else default_lib
+    pat = args[1] if len(args) > 1 else ''
     ks = kernels(lib)
     print('%-100s %5s %5s %5s %6s %8s %7s %5s' % ('kernel', 'vgpr', 'agpr', 'sgpr', 'spill', 'scratch', 'lds', 'mfma'))
     for name in sorted(ks):
