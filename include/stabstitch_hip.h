@@ -323,7 +323,7 @@ SS_API int ss_render_footprints(const float* source, const float* T, float* fp, 
 SS_API int ss_render_footprints_watch(const float* source, const float* T, float* fp, int frames, int views, int h, int w,
                                       int hc, int wc, float guard, int* watch_i, float* watch_f, void* stream);
 /* LINEAR fusion (linear_blender): ref, tgt [3][hc][wc]; ref_m, tgt_m [hc][wc]; out [3][hc][wc];
- * mask1_out optional [hc][wc]; ws: ss_linear_blend_workspace_floats(hc, wc) floats. */
+ * mask1_out optional [hc][wc]; ws: ss_linear_blend_workspace_floats(hc, wc) floats, 8-byte aligned (SS_ERR_ARG otherwise). */
 SS_API long long ss_linear_blend_workspace_floats(int hc, int wc);
 SS_API int ss_linear_blend(const float* ref, const float* tgt, const float* ref_m, const float* tgt_m, float* out,
                     float* mask1_out, int hc, int wc, float* ws, void* stream);

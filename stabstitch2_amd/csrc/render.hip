@@ -803,6 +803,7 @@ extern "C" int ss_linear_blend(const float* ref, const float* tgt, const float* 
                                float* mask1_out, int hc, int wc, float* ws, void* stream) {
     if (!ref_m || !tgt_m || !ws || (!out && !mask1_out) || (out && (!ref || !tgt)) || hc < 11 || wc < 11)
         return SS_ERR_ARG;
+    if (reinterpret_cast<unsigned long long>(ws) & 7ull) return SS_ERR_ARG;      // the scalar block is 64-bit words (as the clip entry)
     // 1-D kernel exp(-0.5 (t/sigma)^2) on linspace(-10,10,21), normalised, fp32 like torchvision
     Gauss21 g;
     {

@@ -489,3 +489,368 @@ WINO_ROUNDINGS = {2: 7, 4: 17}
 def wino_ceiling(cin, m, s_w, extra=3):
     """The derived ceiling of F(m x m, 3 x 3) in fp32: (1.01 (cin + T_m) + extra) u S_w; extra: bias, residual, store."""
     return (1.01 * (cin + WINO_ROUNDINGS[m]) + extra) * U24 * s_w
+
+
+# ------------------------------------------------------------------------------------------------ LINEAR fusion
+def gauss21():
+    """The 21 weights of GaussianBlur((21, 21), sigma 20): exp(-0.5 (t / 20)^2) on t = -10 .. 10, normalised, in float64."""
+    t = np.arange(-10, 11, dtype=np.float64)
+    k = np.exp(-0.5 * (t / 20.0) ** 2)
+    return k / k.sum()
+
+
+def blur21(x, k=None, border='reflect'):
+    """x [h,w] (h, w >= 11) -> the separable 21-tap Gaussian of x with a reflect border (the border pixel is not repeated)."""
+    k = gauss21() if k is None else k
+    h, w = x.shape
+    xp = np.pad(x, ((0, 0), (10, 10)), mode=border)
+    y = sum(k[i] * xp[:, i:i + w] for i in range(21))
+    yp = np.pad(y, ((10, 10), (0, 0)), mode=border)
+    return sum(k[i] * yp[i:i + h, :] for i in range(21))
+
+
+def linear_blender(ref, tgt, ref_m, tgt_m, parts=False, blur=blur21, eps=1e-3):
+    """The reference's linear_blender (test_online_tra.py:34-58): ref, tgt [3,h,w] | None, ref_m, tgt_m [h,w] -> (mask1 [h,w],
+    planes [3,h,w] | None).
+
+      cen_k   the centroid (row, column) of the non-zero pixels of mask k; vec = cen2 - cen1
+      ovl     round(ref_m tgt_m) (half to even), ref_only = ref_m - ovl
+      proj    (r - cen1_r) vec_r + (c - cen1_c) vec_c on the overlap; ovl_mask = (proj - min) / (max - min + 1e-3) there, 0 elsewhere
+      mask1   clamp(blur21(ref_only + (1 - ovl_mask) ref_m) ref_m + ref_only, 0, 1)
+      planes  ref mask1 + tgt (1 - mask1) tgt_m
+
+    Two places are stated, not inherited.  The reference DEFINES the centroids as fp32 numbers (`.float().mean()`) and vec cancels,
+    so they are the exact mean (integer sums, one division) rounded through f32, and float64 from there on.  On an empty overlap
+    the reference raises (`proj.min()` of nothing); the library defines ovl_mask = 0 there, and that extension is what is stated
+    here -- it also covers an empty target mask, whose centroid (0 / 0) is then never used.
+    parts: also return dict(om, X, P, den, overlap) for the derived bound (linear_blend_bound): P = the largest |a| + |b| of
+    proj = a + b over the overlap, den = max - min + 1e-3."""
+    m1, m2 = f64(ref_m), f64(tgt_m)
+    h, w = m1.shape
+    assert h >= 11 and w >= 11, (h, w)
+    r1, c1 = np.nonzero(m1)
+    assert r1.size, 'the reference mask is empty'
+    cen1 = (float(F32(r1.sum() / r1.size)), float(F32(c1.sum() / r1.size)))
+    ovl = np.round(m1 * m2)
+    ref_only = m1 - ovl
+    om = np.zeros_like(m1)
+    r, c = np.nonzero(ovl)
+    P, den = 0.0, eps
+    if r.size:
+        r2, c2 = np.nonzero(m2)
+        cen2 = (float(F32(r2.sum() / r2.size)), float(F32(c2.sum() / r2.size)))
+        vec = (cen2[0] - cen1[0], cen2[1] - cen1[1])
+        a, b = (r - cen1[0]) * vec[0], (c - cen1[1]) * vec[1]
+        proj = a + b
+        den = proj.max() - proj.min() + eps
+        om[r, c] = (proj - proj.min()) / den
+        P = float((np.abs(a) + np.abs(b)).max())
+    X = ref_only + (1.0 - om) * m1
+    mask1 = np.clip(blur(X) * m1 + ref_only, 0.0, 1.0)
+    planes = None
+    if ref is not None:
+        planes = f64(ref) * mask1[None] + f64(tgt) * ((1.0 - mask1) * m2)[None]
+    if parts:
+        return mask1, planes, dict(om=om, X=X, P=P, den=float(den), overlap=int(r.size))
+    return mask1, planes
+
+
+LB_WEIGHT_U = 32            # relative error of one fp32 blur weight in units of u: the argument (i - 10) / 20, its square and the
+                            # halving 3 u of an argument <= 0.125 (0.4 u of the value), expf 2 ulp = 4 u, the 21-term sum of positive
+                            # numbers 21 u, the division 1 u: 27 u, rounded up
+
+
+def linear_blend_bound(ref, tgt, ref_m, tgt_m):
+    """-> (mask1, planes | None, bound_mask1 [h,w], bound_planes [3,h,w] | None): linear_blender and the derived bound of an fp32
+    evaluation of it in which every operation is one correctly rounded IEEE operation or a fused multiply-add (u = 2^-24), for
+    masks on which round(ref_m tgt_m) is decided exactly (sweep_inputs.lb_case asserts it) and centroids defined as above:
+
+      proj    vec = cen2 - cen1, r - cen1, the product, the sum:    d_p   = 1.01 * 4 u P
+      om      numerator 2 d_p + u n, denominator 2 d_p + 2 u den + u 1e-3 (the constant in fp32), the division u, om <= 1:
+                                                                   d_om  = 1.01 (4 d_p / den + 4 u)
+              (0 on an overlap of one pixel: proj - min is x - x there in every precision, and on none)
+      X       1 - om, the product with ref_m, the sum (X <= 2):     d_X   = ref_m d_om + 4.04 u
+      blur    per pass a 21-term fp32 accumulation (dot_bound's gamma_21) with weights of relative error LB_WEIGHT_U u, on
+              X >= 0 -- so the scale of both is the blur itself; the input's error passes through (the weights sum to 1):
+                                                                   d_B   = blur21(d_X) + 2 (1.01 * 21 + LB_WEIGHT_U) u 1.01 blur21(X)
+      mask1   blur * ref_m, + ref_only, the clamp contracts:        d_M   = ref_m d_B + 2.02 u (blur21(X) ref_m + ref_only)
+      planes  ref mask1 + tgt ((1 - mask1) tgt_m): the inputs' d_M, 2 roundings on the first product and sum, 4 on the second:
+                                                                   d_out = (|ref| + |tgt| tgt_m) d_M + 1.01 u (2 |ref| mask1 + 4 |tgt| mask2)"""
+    mask1, planes, p = linear_blender(ref, tgt, ref_m, tgt_m, parts=True)
+    m1, m2 = f64(ref_m), f64(tgt_m)
+    d_p = 1.01 * 4 * U24 * p['P']
+    d_om = 1.01 * (4 * d_p / p['den'] + 4 * U24) if p['overlap'] > 1 else 0.0
+    d_x = m1 * d_om * (np.round(m1 * m2) != 0) + 4.04 * U24
+    bl = blur21(p['X'])
+    d_b = blur21(d_x) + 2 * (1.01 * 21 + LB_WEIGHT_U) * U24 * 1.01 * bl
+    d_m = m1 * d_b + 2.02 * U24 * (bl * m1 + (m1 - np.round(m1 * m2)))
+    d_out = None
+    if planes is not None:
+        a, b = np.abs(f64(ref)), np.abs(f64(tgt))
+        d_out = (a + b * m2[None]) * d_m[None] + 1.01 * U24 * (2 * a * mask1[None] + 4 * b * ((1.0 - mask1) * m2)[None])
+    return mask1, planes, d_m, d_out
+
+
+# ------------------------------------------------------------------------------------------------ mesh geometry
+def dlt4(src, dst):
+    """utils/torch_DLT.py: the homography src -> dst from four correspondences, src, dst [n,4,2] -> H [n,3,3] with H[2,2] = 1;
+    rows per corner (x, y) -> (u, v): [x y 1 0 0 0 -ux -uy] h = u, [0 0 0 x y 1 -vx -vy] h = v, solved in float64."""
+    d = f64(dst)
+    n = d.shape[0]
+    s = np.broadcast_to(f64(src), d.shape)
+    x, y, u, v = s[..., 0], s[..., 1], d[..., 0], d[..., 1]
+    one, zero = np.ones_like(x), np.zeros_like(x)
+    A = np.stack((np.stack((x, y, one, zero, zero, zero, -u * x, -u * y), -1),
+                  np.stack((zero, zero, zero, x, y, one, -v * x, -v * y), -1)), 2).reshape(n, 8, 8)
+    h = np.linalg.solve(A, d.reshape(n, 8, 1)).reshape(n, 8)
+    return np.concatenate((h, np.ones((n, 1))), 1).reshape(n, 3, 3)
+
+
+def decompose(offset8, img_h, img_w, scale=1.0):
+    """spatial_network.py:72-93 / 291-300: offset8 [n,8] -> (H, H_tgt, H_ref) [n,3,3]: H = DLT(c, c + m), H_tgt = DLT(c, c + m / 2),
+    H_ref = H^-1 H_tgt, every corner point divided by `scale`.  The corner points are the fp32 numbers the reference forms (c + m
+    and c + m / 2 are one fp32 addition each; / 2 and / scale are exact for the powers of two in use); float64 from there."""
+    m = f32(offset8).reshape(-1, 4, 2)
+    c = np.array([[0.0, 0.0], [img_w, 0.0], [0.0, img_h], [img_w, img_h]], F32)[None]
+    sc = F32(scale)
+    H = dlt4(c / sc, (c + m) / sc)
+    Ht = dlt4(c / sc, (c + m / F32(2.0)) / sc)
+    return H, Ht, np.linalg.inv(H) @ Ht
+
+
+def spatial_thetas(offset8, img_h, img_w):
+    """spatial_network.py:291-300 -> (theta_ref, theta_tgt) [n,3,3]: M^-1 H M of the decomposition at 1/8 scale, M = [[w/2, 0, w/2],
+    [0, h/2, h/2], [0, 0, 1]] at the feature size (w, h) = (img_w / 8, img_h / 8)."""
+    _, Ht, Hr = decompose(offset8, img_h, img_w, 8.0)
+    fw, fh = img_w / 8.0 / 2.0, img_h / 8.0 / 2.0
+    M = np.array([[fw, 0, fw], [0, fh, fh], [0, 0, 1.0]])
+    Mi = np.linalg.inv(M)
+    return Mi @ Hr @ M, Mi @ Ht @ M
+
+
+def h2mesh(H, mesh):
+    """spatial_network.py:20-36: H [n,3,3], mesh [n,...,2] -> persp_divide(H^-1 [x y 1]^T), the shape of mesh."""
+    m = f64(mesh)
+    p = m.reshape(m.shape[0], -1, 2)
+    t = np.linalg.inv(f64(H)) @ np.concatenate((p, np.ones(p.shape[:2] + (1,))), 2).transpose(0, 2, 1)
+    return np.stack((t[:, 0] / t[:, 2], t[:, 1] / t[:, 2]), 2).reshape(m.shape)
+
+
+def rigid_mesh(img_h, img_w):
+    """[7,9,2] (x, y): torch.linspace(0, size, 9 | 7) as fp32 VALUES, promoted"""
+    import torch
+    xs = torch.linspace(0.0, float(img_w), 9).numpy().astype(np.float64)
+    ys = torch.linspace(0.0, float(img_h), 7).numpy().astype(np.float64)
+    return np.stack(np.broadcast_arrays(xs[None, :], ys[:, None]), axis=2)
+
+
+def spatial_meshes(offset8, off_ref, off_tgt, img_h, img_w):
+    """build_SpatialNet's tail: (motion1, motion2) [n,7,9,2] = H2Mesh(H_ref | H_tgt, rigid) + off_ref | off_tgt - rigid, the
+    decomposition at full scale."""
+    _, Ht, Hr = decompose(offset8, img_h, img_w, 1.0)
+    n = Hr.shape[0]
+    rigid = np.repeat(rigid_mesh(img_h, img_w)[None], n, 0)
+    return (h2mesh(Hr, rigid) + f64(off_ref).reshape(n, 7, 9, 2) - rigid, h2mesh(Ht, rigid) + f64(off_tgt).reshape(n, 7, 9, 2) - rigid)
+
+
+# ------------------------------------------------------------------------------------------------ SmoothNet glue
+# One statement, three readings.  dt = float64: the statement.  dt = float32: every operation below is one numpy fp32 operation, in
+# the reference's order -- the sequential fp32 program the kernels must reproduce bit for bit.  absum=True (float64, inputs taken
+# by absolute value, every subtraction an addition): S, the scale of the derived bound smooth_bound, as conv's S is to dot_bound.
+def _prep(x, dt, absum):
+    x = np.asarray(f64(x) if dt == np.float64 else f32(x), dt)
+    return np.abs(x) if absum else x
+
+
+def _sub(a, b, absum):
+    return a + b if absum else a - b
+
+
+def window_flows(ts, nw, t, wstride, zero_first, dt=np.float64, absum=False):
+    """smooth_network.py:139-144 per sliding window: ts [n,63,2] -> tsflow [nw,t,63,2], window wi covers frames wi wstride + [0, t);
+    tsflow[0] = ts[first] (0 with zero_first: test_online_tra.py:362-366), tsflow[s] = tsflow[s - 1] + ts[first + s]."""
+    ts = _prep(ts, dt, absum)
+    out = np.empty((nw, t) + ts.shape[1:], dt)
+    for wi in range(nw):
+        b = wi * wstride
+        acc = np.zeros_like(ts[b]) if zero_first else ts[b].copy()
+        out[wi, 0] = acc
+        for s in range(1, t):
+            acc = acc + ts[b + s]
+            out[wi, s] = acc
+    return out
+
+
+def window_meshes(sm, nw, t, wstride, dt=np.float64, absum=False):
+    sm = _prep(sm, dt, absum)
+    return np.stack([sm[wi * wstride:wi * wstride + t] for wi in range(nw)])
+
+
+def smooth_embed(sm1, sm2, ts1, ts2, e1w, e1b, e3w, e3b, nw, t, wstride, zero_first, dt=np.float64, absum=False):
+    """smooth_network.py:29-34, 66-72: hidden [nw,t,63,128] = cat(ReLU(Linear_1(smesh1)), ReLU(Linear_3(tsflow1)), ReLU(Linear_1(smesh2)),
+    ReLU(Linear_3(tsflow2))), Linear(2 -> 32): (x w[c,0] + y w[c,1]) + b[c]."""
+    def lin(p, w, b):
+        w, b = _prep(w, dt, absum), _prep(b, dt, absum)
+        o = (p[..., 0:1] * w[:, 0] + p[..., 1:2] * w[:, 1]) + b
+        return o if absum else np.maximum(o, dt(0))
+    return np.concatenate((lin(window_meshes(sm1, nw, t, wstride, dt, absum), e1w, e1b),
+                           lin(window_flows(ts1, nw, t, wstride, zero_first, dt, absum), e3w, e3b),
+                           lin(window_meshes(sm2, nw, t, wstride, dt, absum), e1w, e1b),
+                           lin(window_flows(ts2, nw, t, wstride, zero_first, dt, absum), e3w, e3b)), axis=-1)
+
+
+def smooth_finalize(sm1, sm2, ts1, ts2, delta, nw, t, wstride, zero_first, dt=np.float64, absum=False):
+    """smooth_network.py:145-157 per window: delta [nw,t,63,4] -> the eight outputs [nw,t,63,2]: ori_mesh = smesh, ori_path = tsflow,
+    smooth_mesh = ori_mesh - delta, smooth_path = ori_path + delta (delta[..., 0:2] for view 1, [..., 2:4] for view 2)."""
+    d = _prep(delta, dt, absum).reshape(nw, t, -1, 4)
+    out = {}
+    for k, (sm, ts, dd) in enumerate(((sm1, ts1, d[..., 0:2]), (sm2, ts2, d[..., 2:4])), 1):
+        om, op = window_meshes(sm, nw, t, wstride, dt, absum), window_flows(ts, nw, t, wstride, zero_first, dt, absum)
+        out.update({'ori_mesh%d' % k: om, 'ori_path%d' % k: op, 'smooth_mesh%d' % k: _sub(om, dd, absum), 'smooth_path%d' % k: op + dd})
+    return out
+
+
+def smooth_stitch(sm1, sm2, ts1, ts2, delta, nw, t, dt=np.float64, absum=False):
+    """The reference's frame loop over the sliding windows (test_online_tra.py:377-392, test_metric_ssd.py:415-436), n = nw + t - 1
+    frames, stride 1, the first tsmotion of every window zeroed: window 0 gives its t frames, window k >= 1 its last one;
+        ori_path[f]    = ori_path[f - 1] + (op_w[t - 1] - op_w[t - 2])
+        smooth_path[f] = ori_path[f]     + (sp_w[t - 1] - op_w[t - 1])         (f >= t, w = f - t + 1)
+    -> dict(ori_mesh1/2, smooth_mesh1/2, ori_path2, smooth_path2) [n,63,2]."""
+    o = smooth_finalize(sm1, sm2, ts1, ts2, delta, nw, t, 1, 1, dt, absum)
+    out = {}
+    for k in ('ori_mesh1', 'ori_mesh2', 'smooth_mesh1', 'smooth_mesh2'):
+        out[k] = np.concatenate((o[k][0], o[k][1:, -1]), 0)
+    ori, sm = list(o['ori_path2'][0]), list(o['smooth_path2'][0])
+    for w in range(1, nw):
+        ori.append(ori[-1] + _sub(o['ori_path2'][w, -1], o['ori_path2'][w, -2], absum))
+        sm.append(ori[-1] + _sub(o['smooth_path2'][w, -1], o['ori_path2'][w, -1], absum))
+    out['ori_path2'], out['smooth_path2'] = np.stack(ori), np.stack(sm)
+    return out
+
+
+def smooth_bound(roundings, s):
+    """The gate of a sequential fp32 evaluation with at most `roundings` rounded operations between an input and the output, s = the
+    same evaluation on absolute values with every subtraction an addition: 2 x 1.01 roundings u s.  The rigorous forward bound is
+    half of it (each operation multiplies what it has by (1 + d), |d| <= u, and what it has never exceeds s); a correct fp32 program
+    comes close to that half where an output is two operations from its inputs (0.93 of it on 75600 such outputs of the sweep),
+    so the gate carries the factor 2 that every derived gate is shown to leave the fp32 reading (tests/test_ref64.py).  A wrong
+    order or a dropped term moves an output by its own size, 1e6 gates away; the bits are held separately."""
+    assert np.all(np.asarray(roundings) * U24 < 0.01)
+    return 2 * 1.01 * roundings * U24 * s
+
+
+def window_shift(ring, rows):
+    """The streaming windows' documented shift (include/stabstitch_hip.h, ss_window_push / ss_window_advance): ring [W,E] and the k new
+    rows [k,E] -> (work [W-1+k,E] = ring rows 1 .. W-1 then the new rows, the new ring = the last W rows of work); a copy."""
+    work = np.concatenate((ring[1:], rows), 0)
+    return work, work[-ring.shape[0]:]
+
+
+# ------------------------------------------------------------------------------------------------ canvas normalisation, watcher
+def scale_to_hr(mesh, img_h, img_w, dt=np.float64):
+    """test_online_tra.py:103-104: LR mesh [...,2] -> HR pixels, x * img_w / 480, y * img_h / 360 (the product, then the division);
+    img_h = img_w = 0: the mesh is HR already."""
+    m = np.asarray(mesh, dt)
+    if img_w <= 0 and img_h <= 0:
+        return m.copy()
+    return np.stack(((m[..., 0] * dt(img_w)) / dt(480.0), (m[..., 1] * dt(img_h)) / dt(360.0)), -1)
+
+
+def canvas_normalize(mesh_hr, bbox, dt=np.float64):
+    """test_online_tra.py:129-136: HR mesh [...,2] on the canvas bbox = (wmin, wmax, hmin, hmax) -> [-1, 1]:
+    ((x - wmin) * 2) / (wmax - wmin) - 1, the same in y; bbox broadcasts against the mesh's leading axes."""
+    m, b = np.asarray(mesh_hr, dt), np.asarray(bbox, dt)
+    ow, oh = b[..., 1] - b[..., 0], b[..., 3] - b[..., 2]
+    return np.stack((((m[..., 0] - b[..., 0]) * dt(2.0)) / ow - dt(1.0), ((m[..., 1] - b[..., 2]) * dt(2.0)) / oh - dt(1.0)), -1)
+
+
+def canvas_recover(nmesh, bbox, dt=np.float64):
+    """test_online_tra.py:85-91 on the canvas: [-1, 1] -> canvas pixels, ((v + 1) * extent) / 2."""
+    m, b = np.asarray(nmesh, dt), np.asarray(bbox, dt)
+    return np.stack((((m[..., 0] + dt(1.0)) * (b[..., 1] - b[..., 0])) / dt(2.0), ((m[..., 1] + dt(1.0)) * (b[..., 3] - b[..., 2])) / dt(2.0)), -1)
+
+
+def three_view_align(w12_m1, w12_m2, w23_m1, w23_m2, img_h, img_w, dt=np.float64):
+    """test_online_tra_threeview.py:345-380: four LR meshes [n,63,2] -> (a1, a2, b1, b2, mid) in HR pixels: the pair (2, 3) is shifted
+    by the per-frame mean over the 63 vertices of (w12_m2 - w23_m1); mid = (a2 + b1) / 2.  -> also `absdiff`, the mean of
+    |w12_m2 - w23_m1|: the scale of the bound of an fp32 mean taken in any order."""
+    a1, a2, b1, b2 = (scale_to_hr(m, img_h, img_w, dt) for m in (w12_m1, w12_m2, w23_m1, w23_m2))
+    off = (a2 - b1).mean(axis=1, keepdims=True, dtype=dt)
+    absdiff = np.abs(a2 - b1).mean(axis=1, keepdims=True, dtype=dt)
+    b1, b2 = b1 + off, b2 + off
+    return a1, a2, b1, b2, (a2 + b1) / dt(2.0), absdiff
+
+
+WATCH_SLACK = F32(2.5e-4)
+
+
+def canvas_watch(src, guard, watch_i, watch_f):
+    """The overflow watcher of a streaming canvas as include/stabstitch_hip.h documents it: src [streams,P,2] canvas-normalised control
+    points of one push ([-1, 1] = inside), watch_i [streams,4] = {frames seen, frames with a point outside, index of the first such
+    frame (-1), frames with a point within `guard` of an edge or outside}, watch_f [streams,4] = running {xmin, xmax, ymin, ymax};
+    updated in place.  Outside: a NaN point, or a coordinate beyond +-(1 + 2.5e-4) (the rounding slack); a guard not above the slack
+    makes `near` coincide with `outside`.  All comparisons are strict and between fp32 numbers."""
+    src = f32(src)
+    one, g = F32(1.0), F32(guard)
+    g = g if g > WATCH_SLACK else -WATCH_SLACK
+    for s in range(src.shape[0]):
+        x, y = src[s, :, 0], src[s, :, 1]
+        bad = bool(np.isnan(src[s]).any())
+        xmin, xmax, ymin, ymax = np.fmin.reduce(x), np.fmax.reduce(x), np.fmin.reduce(y), np.fmax.reduce(y)       # a NaN operand is dropped
+        lo, hi = min(xmin, ymin), max(xmax, ymax)
+        out = bad or lo < -one - WATCH_SLACK or hi > one + WATCH_SLACK
+        near = out or lo < -one + g or hi > one - g
+        seen = int(watch_i[s, 0])
+        if out:
+            watch_i[s, 1] += 1
+            if watch_i[s, 2] < 0:
+                watch_i[s, 2] = seen
+        if near:
+            watch_i[s, 3] += 1
+        watch_i[s, 0] = seen + 1
+        watch_f[s] = (np.fmin(watch_f[s, 0], xmin), np.fmax(watch_f[s, 1], xmax), np.fmin(watch_f[s, 2], ymin), np.fmax(watch_f[s, 3], ymax))
+
+
+def ulp_bound(roundings, value, scale):
+    """|fp32 sequence - float64| for `roundings` single rounded operations on numbers whose size, in the output's unit, is at most
+    max(|value|, scale): 1.01 roundings u max(|value|, scale)."""
+    return 1.01 * roundings * U24 * np.maximum(np.abs(value), scale)
+
+
+def canvas_normalize_bound(mesh_hr, bbox):
+    """-> (canvas_normalize in float64, its gate): the fp32 sequence is x * img_w, / 480, - wmin, * 2, / extent, - 1 -- six roundings
+    (two fewer without the scaling) of numbers no larger than M = the largest coordinate or box entry, which in the output's unit
+    is 2 M / extent of that axis."""
+    m, b = f64(mesh_hr), f64(bbox)
+    big = max(float(np.abs(m).max()), float(np.abs(b).max()))
+    scale = np.stack((2 * big / (b[..., 1] - b[..., 0]), 2 * big / (b[..., 3] - b[..., 2])), -1)
+    ref = canvas_normalize(m, b)
+    return ref, ulp_bound(6, ref, np.broadcast_to(scale, ref.shape))
+
+
+def canvas_recover_bound(nmesh, bbox):
+    """-> (canvas_recover in float64, its gate): v + 1, * extent, / 2 -- three roundings of numbers up to (|v| + 1) extent."""
+    n, b = f64(nmesh), f64(bbox)
+    ext = np.stack((b[..., 1] - b[..., 0], b[..., 3] - b[..., 2]), -1)
+    ref = canvas_recover(n, b)
+    return ref, ulp_bound(3, ref, np.broadcast_to((np.abs(n) + 1) * ext, ref.shape))
+
+
+def three_view_align_bound(w12_m1, w12_m2, w23_m1, w23_m2, img_h, img_w):
+    """-> (a1, a2, b1, b2, mid in float64, the gates of b1, b2, mid): the two roundings of the scaling on every coordinate (`scaled`),
+    the 63-point fp32 mean of the differences in ANY order (dot_bound on the mean of their absolute values, + their inputs' 2 x
+    scaled), then b + off (one rounding) and (a2 + b1) / 2 (two)."""
+    a1, a2, b1, b2, mid, absdiff = three_view_align(*[f64(m) for m in (w12_m1, w12_m2, w23_m1, w23_m2)], img_h, img_w)
+    big = max(float(np.abs(x).max()) for x in (a1, a2, b1, b2))
+    scaled = 1.01 * 2 * U24 * big
+    mean_b = dot_bound(63, absdiff, extra=2) + 2 * scaled
+    return (a1, a2, b1, b2, mid), (mean_b + scaled + U24 * np.abs(b1), mean_b + scaled + U24 * np.abs(b2),
+                                   0.5 * mean_b + scaled + 2 * U24 * np.abs(mid))
+
+
+def canvas_shift_bound(mesh_hr, origin):
+    """-> (mesh - origin in float64, its gate): ONE rounding of a number up to |mesh| + |origin|.  A single rounding can reach its
+    bound u |value| exactly, so the gate counts two: the factor 2 every derived gate leaves the fp32 reading."""
+    m, o = f64(mesh_hr), f64(origin)
+    ref = m - o
+    return ref, ulp_bound(2, ref, 0.0)

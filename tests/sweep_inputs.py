@@ -1,11 +1,56 @@
 """Seeded inputs and gate constructions of the kernel sweeps, shared by tests/test_ref64.py (CPU: the fp32 oracle against
-tests/ref64.py on these very inputs, under these very gates) and tests/test_gpu_kernel_sweeps.py / tests/test_gpu_conv_sweeps.py
-(the kernels).  The float64 statements themselves are in tests/ref64.py and do not depend on anything here.  The second half
-holds the convolution sweep: its cases, the dispatch rules of the convolution engine restated (which kernel a shape takes), an fp32
-emulation of both Winograd forms, and the reach table from kernel instantiation to the cases claimed to launch it."""
+tests/ref64.py on these very inputs, under these very gates) and tests/test_gpu_kernel_sweeps.py / tests/test_gpu_conv_sweeps.py /
+tests/test_gpu_rest_sweeps.py (the kernels), with the comparison helpers the three sweep files share (within, refused, host).
+The float64 statements themselves are in tests/ref64.py and do not depend on anything here.  The middle holds the convolution
+sweep: its cases, the dispatch rules of the convolution engine restated (which kernel a shape takes), an fp32 emulation of both
+Winograd forms, and the reach table from kernel instantiation to the cases claimed to launch it; then the inputs of the LINEAR and
+mesh-geometry sweeps and library_reach, the coverage table of every kernel of the library."""
+import os
+
 import numpy as np
 
-from ref64 import F32, f64, dot_bound, linspace, bilinear_clamped, grid_sample_zeros, homography_coords
+from ref64 import F32, WATCH_SLACK, f64, dot_bound, linspace, bilinear_clamped, grid_sample_zeros, homography_coords
+
+VERBOSE = bool(os.environ.get('SS_VERBOSE'))
+
+
+# ------------------------------------------------------------------------------------------------ comparison helpers
+def host(t):
+    return t.detach().cpu().numpy().astype(np.float64) if hasattr(t, 'detach') else np.asarray(t, dtype=np.float64)
+
+
+def within(got, ref, bound, what):
+    """every element: |got - ref| <= bound (array or scalar); prints the worst |diff| / bound under SS_VERBOSE"""
+    got, ref = host(got), host(ref)
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    assert np.isfinite(got).all(), what + ' has non-finite values'
+    d = np.abs(got - ref)
+    bound = np.broadcast_to(np.asarray(bound, dtype=np.float64), d.shape)
+    excess = d - bound
+    if VERBOSE:
+        ratio = float((d / np.maximum(bound, 1e-300))[bound > 0].max()) if (bound > 0).any() else 0.0
+        print('  [sweep] %-58s max|diff| %.3e  worst |diff|/bound %.3f' % (what, float(d.max()) if d.size else 0.0, ratio))
+    i = np.unravel_index(int(np.argmax(excess)), excess.shape) if d.size else ()
+    assert (excess <= 0).all(), '%s: |diff| %.3e > bound %.3e at %s (%d of %d elements out)' % (
+        what, d[i], bound[i], i, int((excess > 0).sum()), d.size)
+
+
+def refused(code, fn, *args):
+    import pytest
+    from stabstitch2_amd import _hip as H
+    with pytest.raises(H.HipError) as ei:
+        fn(*args)
+    assert ei.value.code == code, (ei.value.code, code)
+
+
+def astype_u8(x):
+    """`.astype(np.uint8)` as include/stabstitch_hip.h documents it: truncation toward zero through int32, the low byte kept; a
+    value int32 cannot hold (|v| >= 2^31, +-inf, NaN) gives 0."""
+    x = np.asarray(x, F32)
+    ok = np.abs(x) < 2147483648.0                               # False for NaN
+    t = np.trunc(np.where(ok, x, 0)).astype(np.int64)
+    return np.where(ok, t & 0xFF, 0).astype(np.uint8)
+
 
 RAMP = 1.0 / 64.0           # ramp channels of the homography inputs hold index * RAMP (exact in fp32, same magnitude as the texture)
 
@@ -588,3 +633,310 @@ def reach_table():
         for res in (False, True):
             add(wino43_kernel(w, cin, res), 'wino43[%d-%d-%d-%d-%d]' % (n, h, w, cin, cout))
     return table
+
+
+# ================================================================================================ LINEAR fusion sweep
+# Shared by tests/test_ref64.py (CPU) and tests/test_gpu_rest_sweeps.py (the kernels).
+LB_CANVASES = [(11, 11), (11, 64), (12, 65), (21, 21), (20, 130), (64, 64), (65, 63), (97, 129), (200, 300)]       # (hc, wc)
+LB_PATTERNS = ['rects', 'inside', 'disjoint', 'one_pixel', 'symmetric', 'ones', 'half', 'last']
+LB_VEC_ZERO = ('symmetric', 'ones')            # the centroids coincide on purpose: vec == 0 exactly, proj == 0
+LB_NO_OVERLAP = ('disjoint',)
+
+
+def _cover(n, a, b):
+    """How much of pixel x (the interval x +- 0.5) lies in [a, b], x = 0 .. n - 1; a, b multiples of 1/64 -> multiples of 1/64."""
+    x = np.arange(n, dtype=np.float64)
+    return np.clip(np.minimum(x + 0.5, b) - np.maximum(x - 0.5, a), 0.0, 1.0)
+
+
+def _rect(h, w, r0, r1, c0, c1):
+    """A soft-edged rectangle: min of the row and the column coverage (a product would leave the 1/64 lattice)."""
+    return np.minimum(_cover(h, r0, r1)[:, None], _cover(w, c0, c1)[None, :])
+
+
+def _q(v):
+    return np.floor(v) + 19.0 / 64.0            # a fractional border on the 1/64 lattice
+
+
+def lb_masks(pattern, h, w):
+    """-> (m1, m2) [h,w] float64 on the 1/64 lattice, see LB_PATTERNS / the issue's list."""
+    one = np.ones((h, w))
+    if pattern == 'rects':                      # two soft-edged rectangles with fractional borders that overlap
+        return _rect(h, w, _q(0.08 * h), _q(0.86 * h), -1.0, _q(0.62 * w)), _rect(h, w, _q(0.2 * h), h + 1.0, _q(0.33 * w), _q(0.9 * w))
+    if pattern == 'inside':                     # the target inside the reference, off its centre
+        return _rect(h, w, -1.0, h + 1.0, -1.0, w + 1.0), _rect(h, w, _q(0.55 * h), _q(0.9 * h), _q(0.5 * w), _q(0.85 * w))
+    if pattern == 'disjoint':                   # no overlap: the range keys are never written, om is never used
+        return _rect(h, w, -1.0, _q(0.7 * h), -1.0, _q(0.35 * w)), _rect(h, w, _q(0.2 * h), h + 1.0, np.floor(0.35 * w) + 2.0, w + 1.0)
+    if pattern == 'one_pixel':                  # binary rectangles that share one pixel: pmax == pmin, the denominator is the 1e-3
+        r0, c0 = h // 2, w // 2
+        m1, m2 = np.zeros((h, w)), np.zeros((h, w))
+        m1[:r0 + 1, :c0 + 1] = 1.0
+        m2[r0:, c0:] = 1.0
+        return m1, m2
+    if pattern == 'symmetric':                  # both symmetric about the canvas centre: vec == 0 exactly
+        a, b = _q(0.1 * h) , _q(0.1 * w)
+        c, d = _q(0.3 * h), _q(0.3 * w)
+        return _rect(h, w, a, h - 1 - a, b, w - 1 - b), _rect(h, w, c, h - 1 - c, d, w - 1 - d)
+    if pattern == 'ones':                       # the overlap touches all four borders, the reflect halo feeds every edge pixel
+        return one, one.copy()
+    if pattern == 'half':                       # m1 = 1, m2 = 0.5 around a block of ones: the product 0.5 rounds to 0 (half to even).
+        m2 = np.full((h, w), 0.5)               # m2 = 0 on the left quarter moves its centroid right, so proj grows with the column and
+        m2[h // 3:, w // 2 + 1:] = 1.0          # the 0.5 pixels left of the block lie BELOW the overlap's projection range: counted as
+        m2[:, :w // 4] = 0.0                    # overlap (half rounded away from zero) they would stretch the range
+        return one, m2
+    if pattern == 'last':                       # the target's non-zero pixels are only in the last column and the last row
+        m2 = np.zeros((h, w))
+        m2[h - 1, :] = 1.0
+        m2[:, w - 1] = 47.0 / 64.0
+        m2[h - 1, w - 1] = 1.0
+        return _rect(h, w, _q(0.15 * h), h + 1.0, _q(0.1 * w), w + 1.0), m2
+    raise KeyError(pattern)
+
+
+def lb_case(pattern, hc, wc, seed=0):
+    """One LINEAR blender input -> (ref [3,hc,wc], tgt [3,hc,wc], m1 [hc,wc], m2 [hc,wc]) fp32: images uniform 0..255, masks from
+    lb_masks.  Asserted here, for every case: the masks are multiples of 1/64 in [0, 1], so that m1 m2 (a multiple of 1/4096) and the
+    union m1 + m2 - m1 m2 are exact in fp32 and round() takes the same branch in every precision; the index sums behind the
+    centroids stay below 2^24, so that an fp32 `.float().mean()` IS the exact mean rounded once; |vec| >= 1 px unless the pattern
+    makes it vanish, so that the cancellation in vec stays bounded; the overlap is what the pattern says."""
+    rs = np.random.RandomState(13000 + seed + 131 * hc + 17 * wc + LB_PATTERNS.index(pattern))
+    m1, m2 = lb_masks(pattern, hc, wc)
+    for m in (m1, m2):
+        assert m.shape == (hc, wc) and (m >= 0).all() and (m <= 1).all() and (m * 64 == np.round(m * 64)).all(), pattern
+    assert np.array_equal((m1.astype(F32) * m2.astype(F32)).astype(np.float64), m1 * m2)
+    un32 = m1.astype(F32) + m2.astype(F32) - m1.astype(F32) * m2.astype(F32)
+    assert np.array_equal(un32.astype(np.float64), m1 + m2 - m1 * m2)
+    for m in (m1, m2):
+        assert max(np.nonzero(m)[0].sum(), np.nonzero(m)[1].sum()) < 2 ** 24
+    ovl = np.round(m1 * m2)
+    assert (ovl.sum() == 0) == (pattern in LB_NO_OVERLAP), (pattern, ovl.sum())
+    if pattern == 'one_pixel':
+        assert ovl.sum() == 1
+    if pattern == 'half':
+        assert ((m1 * m2) == 0.5).any() and (ovl[(m1 * m2) == 0.5] == 0).all()
+    cen = [np.array([np.nonzero(m)[0].mean(), np.nonzero(m)[1].mean()]) for m in (m1, m2)]
+    vec = cen[1].astype(F32).astype(np.float64) - cen[0].astype(F32).astype(np.float64)
+    if pattern in LB_VEC_ZERO:
+        assert (vec == 0).all(), (pattern, vec)
+    else:
+        assert np.hypot(*vec) >= 1.0, (pattern, hc, wc, vec)
+    ref = rs.uniform(0, 255, (3, hc, wc)).astype(F32)
+    tgt = rs.uniform(0, 255, (3, hc, wc)).astype(F32)
+    return ref, tgt, m1.astype(F32), m2.astype(F32)
+
+
+def lb_third(hc, wc, seed=0):
+    """The third view of a chain: (w3 [3,hc,wc], m3 [hc,wc]) fp32, a soft rectangle over the lower right of the canvas (it overlaps
+    the union of every pattern's pair) on the 1/64 lattice: the union of the first two is on the 1/4096 lattice and its product with
+    m3 on the 2^-18 one, still exact in fp32."""
+    rs = np.random.RandomState(14000 + seed + 131 * hc + 17 * wc)
+    m3 = _rect(hc, wc, _q(0.35 * hc), hc + 1.0, _q(0.45 * wc), wc + 1.0)
+    return rs.uniform(0, 255, (3, hc, wc)).astype(F32), m3.astype(F32)
+
+
+LB_RENDER_CANVASES = [(40, 50), (11, 70), (97, 65), (80, 129)]      # hc < 64 and wc < 64; hc == 11; one row past the 96-row strip and
+                                                                    # one column past a 64-column strip; one column past two strips
+LB_RENDER_FRAME = (72, 96)
+
+
+def lb_render_case(frames, views, hc, wc, off_canvas=None, seed=0):
+    """Inputs of the fused LINEAR renderers: `frames` frames of `views` views of 72 x 96 (warp_case's textures, rounded to whole
+    numbers so that the uint8 frames hold the same values) and hand-built splines -> (U [frames,views,3,72,96] fp32, source
+    [frames,views,63,2] canvas-normalised, target [63,2]).  View v's frame is mapped onto a box of 0.62 x 0.7 of the canvas whose
+    corner moves right and down with v (so that neighbouring views overlap in part, and the masks have fractional borders), with
+    2 % jitter per control point and frame.  off_canvas: that view's box starts two canvas widths to the right -- nothing of it
+    overlaps the others; its warped mask is all zero under FAST and holds the clamped sampler's rounding residue (blend_residue, a
+    few 1e-5 at a few pixels) under NORMAL."""
+    h, w = LB_RENDER_FRAME
+    U, _, tgt = warp_case(frames * views, h, w, hc, wc, seed=20 + seed)
+    rs = np.random.RandomState(15000 + seed + 131 * hc + 17 * wc + views)
+    r = rigid_px(h, w)[0]                                                    # [7,9,2]
+    src = np.empty((frames, views, 7, 9, 2), F32)
+    for f in range(frames):
+        for v in range(views):
+            ox = (0.02, 0.33, 0.38)[v] * wc + (2.0 * wc if v == off_canvas else 0.0)
+            oy = (0.05, 0.25, 0.28)[v] * hc
+            src[f, v, ..., 0] = ox + r[..., 0] * (0.62 * wc / w) + rs.normal(0, 0.02 * wc, (7, 9))
+            src[f, v, ..., 1] = oy + r[..., 1] * (0.70 * hc / h) + rs.normal(0, 0.02 * hc, (7, 9))
+    U3 = np.rint(U[:, :3]).clip(0, 255).astype(F32).reshape(frames, views, 3, h, w)
+    return U3, norm_px(src.reshape(frames * views, 7, 9, 2), hc, wc).reshape(frames, views, 63, 2), tgt[0]
+
+
+# ================================================================================================ mesh geometry sweep
+GEOM_BATCHES = [1, 63, 64, 65, 300]            # one item per thread in 64-thread blocks, or one block per item
+GEOM_SIZES = [(360, 480), (720, 1280)]
+
+
+def geom_offsets(n, kind, img_h, img_w, seed=0):
+    """offset8 [n,8] fp32: 'zero' (the identity), 'mild' (up to 8 % of the frame, the size the regressor produces), 'large' (every
+    corner pulled 40 % of the way to the centre and jittered by 5 %: a quad of about a quarter of the area, near collapse for a
+    DLT but still convex)."""
+    rs = np.random.RandomState(21000 + seed + n + img_h + {'zero': 0, 'mild': 1, 'large': 2}[kind])
+    size = np.array([img_w, img_h], np.float64)
+    if kind == 'zero':
+        return np.zeros((n, 8), F32)
+    if kind == 'mild':
+        return (rs.uniform(-0.08, 0.08, (n, 4, 2)) * size).reshape(n, 8).astype(F32)
+    c = np.array([[0.0, 0.0], [img_w, 0.0], [0.0, img_h], [img_w, img_h]])
+    m = 0.4 * (size / 2 - c)[None] + rs.uniform(-0.05, 0.05, (n, 4, 2)) * size
+    q = c[None] + m                                                          # still convex: the corners keep their cyclic order
+    for a, b, d in ((0, 1, 3), (1, 3, 2), (3, 2, 0), (2, 0, 1)):
+        e1, e2 = q[:, b] - q[:, a], q[:, d] - q[:, b]
+        assert (e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0] > 0).all()
+    return m.reshape(n, 8).astype(F32)
+
+
+def geom_residuals(n, seed=0):
+    """(off_ref, off_tgt) [n,126] fp32: the second stage's per-vertex residuals, N(0, 3 px)"""
+    rs = np.random.RandomState(22000 + seed + n)
+    return rs.normal(0, 3.0, (n, 126)).astype(F32), rs.normal(0, 3.0, (n, 126)).astype(F32)
+
+
+# ================================================================================================ SmoothNet glue, windows, canvas normalisation, watcher
+# Shared by tests/test_ref64.py (CPU: the fp32 reading of each statement inside half of its gate on these very cases) and
+# tests/test_gpu_rest_sweeps.py (the kernels).
+def corner_points(n, img_h, img_w):
+    return np.repeat(np.array([[0.0, 0.0], [img_w, 0.0], [0.0, img_h], [img_w, img_h]], F32)[None], n, 0)
+
+
+
+
+def smooth_case(nw, t, wstride, seed=0):
+    """smesh1/2, tsmotion1/2 [n,63,2] of pipeline-like size (LR meshes around the rigid grid, ~2 px motions), delta [nw,t,63,4],
+    the two embeddings' weights [32,2] and biases [32]; n = (nw - 1) wstride + t frames"""
+    n = (nw - 1) * wstride + t
+    rs = np.random.RandomState(24000 + seed + 7 * nw + 131 * t + wstride)
+    rigid = rigid_px(360, 480).reshape(1, 63, 2)
+    sm = [(rigid + rs.normal(0, 4.0, (n, 63, 2))).astype(F32) for _ in range(2)]
+    ts = [rs.normal(0, 2.0, (n, 63, 2)).astype(F32) for _ in range(2)]
+    delta = rs.normal(0, 1.5, (nw, t, 63, 4)).astype(F32)
+    emb = [rs.normal(0, 0.5, s).astype(F32) for s in ((32, 2), (32,), (32, 2), (32,))]
+    return sm, ts, delta, emb
+
+
+SMOOTH_SHAPES = [(nw, t, ws) for t in (2, 7) for nw in (1, 2, 30, 300) for ws in (1, t)]
+
+
+
+
+def ring_case(rings, w, e, k, seed=0):
+    rs = np.random.RandomState(25000 + seed + rings + 7 * w + 131 * e + k)
+    return rs.normal(0, 1, (rings, w, e)).astype(F32), rs.normal(0, 1, (rings, k, e)).astype(F32)
+
+
+WINDOW_SHAPES = [(2, 2048), (2049, 1), (7, 126), (7, 255), (7, 256), (7, 257), (2, 1), (5, 512), (8, 292)]      # (W, E): (W - 1) E <= 2048
+
+
+
+
+def norm_case(frames, views, seed=0):
+    """LR meshes [views][frames,63,2] around the rigid 360 x 480 grid, shifted per view, and canvas boxes in HR pixels of a 720 x 1280
+    frame: one box, and one per frame"""
+    rs = np.random.RandomState(26000 + seed + frames + 7 * views)
+    rigid = rigid_px(360, 480).reshape(1, 63, 2)
+    meshes = [(rigid + rs.normal(0, 9.0, (frames, 63, 2)) + [110.0 * v, 7.0 * v]).astype(F32) for v in range(views)]
+    box = np.array([-31.7, 1893.2, -44.1, 801.6], F32)
+    boxes = (box[None] + rs.uniform(-20, 20, (frames, 4))).astype(F32)
+    return meshes, box, boxes
+
+
+def watch_frames():
+    """Seven frames [7,2,63,2] of two views inside the canvas, each with one point moved: exactly on +-1; exactly on -(1 + slack) and on +(1 + slack)
+    (inside) and one fp32 step beyond (outside); exactly on the guard distance 1 - 0.02 (not near) and one step beyond (near); a NaN in
+    lane 37 of the second view.  Frames 0 .. 2 are inside: the first clipped frame is frame 3."""
+    rs = np.random.RandomState(27000)
+    f = rs.uniform(-0.9, 0.9, (7, 2, 63, 2)).astype(F32)
+    one, slack, g = F32(1.0), WATCH_SLACK, F32(0.02)
+    edge = one + slack
+    near = one - g
+    f[0, 0, 5] = [1.0, -1.0]
+    f[1, 1, 62] = [-edge, 0.0]
+    f[1, 0, 10] = [edge, 0.0]
+    f[2, 0, 17, 1] = near
+    f[3, 1, 40, 0] = np.nextafter(edge, F32(2.0))
+    f[4, 0, 63 - 1, 1] = np.nextafter(near, F32(2.0))
+    f[5, 1, 37, 1] = np.nan
+    f[6, 0, 0, 1] = -np.nextafter(edge, F32(2.0))
+    return f
+
+
+def three_view_case(frames):
+    """The four LR meshes of a three-view alignment [4][frames,63,2] (w12_m1, w12_m2, w23_m1, w23_m2: the pair (2, 3)'s first mesh is
+    the pair (1, 2)'s second moved by 3.3 px) and the first canvas' box"""
+    meshes, box, _ = norm_case(frames, 3, seed=3)
+    return [meshes[0], meshes[1], (meshes[1] + F32(3.3)).astype(F32), meshes[2]], box
+
+
+NORM_FRAMES = [1, 7, 300]
+NORM_SIZES = [(720, 1280), (0, 0)]             # scaled from LR, and HR already (img_h = img_w = 0)
+STITCH_SHAPES = [(1, 2), (1, 7), (2, 2), (2, 7), (30, 2), (30, 7), (300, 2), (300, 7)]       # (nw, t)
+
+
+# ================================================================================================ the coverage table of the library
+KS, CS, RS_ = 'test_gpu_kernel_sweeps', 'test_gpu_conv_sweeps', 'test_gpu_rest_sweeps'
+LB_CHAIN = ('lb_init_kernel', 'lb_centroid_kernel', 'lb_range_kernel', 'lb_premask_kernel', 'lb_blur_kernel', 'lb_final_kernel')
+
+
+def library_reach():
+    """Every kernel of the built library by its base name (all instantiations of a template share an entry; the convolution engine's
+    instantiations are told apart by reach_table above) -> (kind, tests, held_to):
+      'fp64'      the sweep tests that compare it with a statement of tests/ref64.py
+      'identity'  the test that holds it bit for bit to the kernels `held_to`, every one of them 'fp64' or 'identity' in turn
+      'exact'     copy, permute, byte and min / max kernels: the test that holds them bit for bit to numpy
+    Kernels that no call of the C ABI launches are in UNREACHABLE.  tests/test_ref64.py holds the table to the code objects of the
+    built library (nothing missing, nothing stale), follows every identity chain to an 'fp64' end and checks that the cited tests
+    exist."""
+    t = {}
+
+    def add(kind, names, tests, held_to=()):
+        for n in names.split():
+            assert n not in t, n
+            t[n] = (kind, tuple(tests), tuple(held_to))
+    # ---- the two earlier sweeps
+    add('fp64', 'cost_volume_kernel', [KS + '::test_cost_volume_against_fp64', KS + '::test_cost_volume_shifted_and_chain_against_fp64'])
+    add('fp64', 'ccl_softmax_kernel', [KS + '::test_ccl_against_fp64'])
+    add('fp64', 'l2norm_kernel', [KS + '::test_l2norm_against_fp64', KS + '::test_ccl_against_fp64'])
+    add('fp64', 'homo_warp_kernel', [KS + '::test_homography_against_fp64'])
+    add('fp64', 'tps_solve_kernel tps_inverse_kernel', [KS + '::test_tps_solve_by_its_action'])
+    add('fp64', 'tps_points_kernel', [KS + '::test_tps_points_against_fp64'])
+    add('fp64', 'tsm_prepare_kernel tsm_finish_kernel tsm_fused_kernel', [KS + '::test_tsmotion_against_fp64'])
+    add('fp64', 'tps_warp_kernel', [KS + '::test_tps_dense_warp_against_fp64'])
+    add('fp64', 'tps_warp_views_kernel', [KS + '::test_tps_warp_views_against_fp64'])
+    add('identity', 'render_average_kernel', [KS + '::test_fused_render_equals_formula_on_per_view_warps'], ['tps_warp_kernel', 'canvas_u8x1_kernel', 'canvas_u8x4_kernel'])
+    add('identity', 'render_lattice_kernel render_order_kernel', ['test_gpu_parity::test_render_footprint_skipping'], ['render_average_kernel'])
+    add('fp64', 'psnr_ssim_kernel psnr_ssim_finish_kernel', [KS + '::test_psnr_ssim_against_fp64'])
+    add('fp64', 'stability_kernel distortion_kernel max_reduce_kernel', [KS + '::test_metric_scores_against_fp64_and_refusals'])
+    add('fp64', 'linear_kernel linear_grouped_kernel', [KS + '::test_linear_against_fp64'])
+    add('exact', 'maxpool_kernel', [KS + '::test_maxpool_split_bit_exact'])
+    add('fp64', 'conv_igemm_kernel splitk_reduce_kernel', [CS + '::test_implicit_gemm_against_fp64', CS + '::test_conv_pool_in_reduce_against_fp64'])
+    add('fp64', 'stem_pool_kernel_half stem_pool_pack_kernel nchw_to_nhwc3_padded_kernel', [CS + '::test_stem_against_fp64'])
+    add('fp64', 'conv_wino_kernel wino_pack_kernel wino_pack3_kernel', [CS + '::test_winograd_f2_against_fp64'])
+    add('fp64', 'conv_wino43p_kernel wino43_pack_kernel', [CS + '::test_winograd_f4_against_fp64'])
+    # ---- LINEAR fusion
+    add('fp64', ' '.join(LB_CHAIN), [RS_ + '::test_linear_blend_against_fp64', RS_ + '::test_linear_blend_three_view_chain_against_fp64'])
+    add('identity', 'lb_clip_warp_kernel lb_clip_reduce_kernel lb_clip_blend_kernel lb_clip_blend_rows_kernel lb_frames_warp_kernel '
+        'lb_frames_reduce_kernel lb_frames_blend_rows_kernel', [RS_ + '::test_linear_renderers_equal_per_frame_chain'],
+        LB_CHAIN + ('tps_warp_views_kernel', 'mask_union_kernel', 'canvas_u8x1_kernel', 'canvas_u8x4_kernel'))
+    # ---- mesh geometry
+    add('fp64', 'tensor_dlt_kernel spatial_decompose_kernel spatial_meshes_kernel', [RS_ + '::test_dlt_decompose_meshes_against_fp64'])
+    add('fp64', 'h2mesh_kernel', [RS_ + '::test_h2mesh_against_fp64'])
+    add('exact', 'mesh_bbox_kernel', [RS_ + '::test_mesh_bbox_bit_exact'])
+    add('fp64', 'mesh_normalize_kernel mesh_normalize_views_kernel stream_normalize_watch_kernel', [RS_ + '::test_canvas_normalize_kernels_bit_exact'])
+    add('fp64', 'three_view_align_kernel three_view_normalize_kernel three_view_finish_kernel', [RS_ + '::test_three_view_glue_kernels'])
+    add('exact', 'canvas_watch_kernel canvas_watch_frames_kernel', [RS_ + '::test_canvas_watchers_against_the_documented_update'])
+    add('identity', 'three_view_splines_kernel', ['test_gpu_round6::test_three_view_splines_equal_the_seven_launches'],
+        ['three_view_align_kernel', 'three_view_normalize_kernel', 'tps_solve_kernel', 'tps_points_kernel', 'three_view_finish_kernel',
+         'stream_normalize_watch_kernel'])
+    add('identity', 'stream_splines_kernel', ['test_gpu_round6::test_stream_splines_equal_normalise_plus_solve'],
+        ['stream_normalize_watch_kernel', 'mesh_normalize_views_kernel', 'tps_solve_kernel'])
+    # ---- SmoothNet glue, streaming windows
+    add('fp64', 'smooth_embed_kernel smooth_finalize_kernel', [RS_ + '::test_smooth_embed_and_finalize'])
+    add('fp64', 'smooth_stitch_kernel smooth_path_chain_kernel', [RS_ + '::test_smooth_stitch_against_frame_loop'])
+    add('exact', 'window_push_kernel', [RS_ + '::test_window_push_bit_exact'])
+    add('exact', 'window_advance_kernel', [RS_ + '::test_window_advance_bit_exact'])
+    # ---- byte and layout kernels
+    add('exact', 'ingest_hr4_kernel ingest_hr1_kernel ingest_lr_kernel', [RS_ + '::test_ingest_u8_paths_bit_exact'])
+    add('exact', 'canvas_u8x4_kernel canvas_u8x1_kernel', [RS_ + '::test_canvas_to_u8_paths_and_edge_values'])
+    add('exact', 'nchw_to_nhwc_kernel nchw_to_nhwc4_kernel nhwc_to_nchw_kernel', [RS_ + '::test_layout_kernels_bit_exact'])
+    add('exact', 'affine_kernel mask_union_kernel fill_kernel', [RS_ + '::test_elementwise_helpers_bit_exact'])
+    return t

@@ -21,7 +21,6 @@ Gates (tests/test_ref64.py shows on the CPU that the fp32 oracle meets each fixe
 
     python -m pytest tests/test_gpu_kernel_sweeps.py -m gpu          (SS_VERBOSE=1 prints every observed maximum beside its gate)"""
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -30,38 +29,18 @@ import torch.nn.functional as F
 
 import ref64 as R
 import sweep_inputs as G
+from sweep_inputs import host, within, refused, VERBOSE          # noqa: F401  (the sweeps' shared helpers)
 from oracle import nets as N
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 T = torch.from_numpy
-VERBOSE = bool(os.environ.get('SS_VERBOSE'))
 
 
 @pytest.fixture(scope='module')
 def dev():
     assert torch.cuda.is_available(), 'gpu tests need a GPU'
     return torch.device('cuda:0')
-
-
-def host(t):
-    return t.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(t) else np.asarray(t, dtype=np.float64)
-
-
-def within(got, ref, bound, what):
-    """every element: |got - ref| <= bound (array or scalar); prints the worst |diff| / bound under SS_VERBOSE"""
-    got, ref = host(got), host(ref)
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert np.isfinite(got).all(), what + ' has non-finite values'
-    d = np.abs(got - ref)
-    bound = np.broadcast_to(np.asarray(bound, dtype=np.float64), d.shape)
-    excess = d - bound
-    if VERBOSE:
-        ratio = float((d / np.maximum(bound, 1e-300))[bound > 0].max()) if (bound > 0).any() else 0.0
-        print('  [sweep] %-58s max|diff| %.3e  worst |diff|/bound %.3f' % (what, float(d.max()) if d.size else 0.0, ratio))
-    i = np.unravel_index(int(np.argmax(excess)), excess.shape) if d.size else ()
-    assert (excess <= 0).all(), '%s: |diff| %.3e > bound %.3e at %s (%d of %d elements out)' % (
-        what, d[i], bound[i], i, int((excess > 0).sum()), d.size)
 
 
 def nhwc(x, dev):
@@ -72,13 +51,6 @@ def nhwc(x, dev):
 def nchw_of(t, c=None):
     t = t if c is None else t[..., :c]
     return t.permute(0, 3, 1, 2)
-
-
-def refused(code, fn, *args):
-    from stabstitch2_amd import _hip as H
-    with pytest.raises(H.HipError) as ei:
-        fn(*args)
-    assert ei.value.code == code, (ei.value.code, code)
 
 
 # ================================================================================================ cost volume
