@@ -322,6 +322,11 @@ SS_API int ss_render_footprints(const float* source, const float* T, float* fp, 
  * (ss_three_view_splines).  One graph node less on a batch-1 push. */
 SS_API int ss_render_footprints_watch(const float* source, const float* T, float* fp, int frames, int views, int h, int w,
                                       int hc, int wc, float guard, int* watch_i, float* watch_f, void* stream);
+/* ss_render_footprints_watch + ss_canvas_watch_fit's refit of box / epoch / ext0 [frames] behind the watcher (frame = stream), in
+ * the same wave of the same launch; the viewport is the canvas size hc x wc (each in 11..65535). */
+SS_API int ss_render_footprints_watch_fit(const float* source, const float* T, float* fp, int frames, int views, int h, int w,
+                                          int hc, int wc, float guard, int* watch_i, float* watch_f, float* box, int* epoch,
+                                          const float* ext0, float margin, float zoom_limit, void* stream);
 /* LINEAR fusion (linear_blender): ref, tgt [3][hc][wc]; ref_m, tgt_m [hc][wc]; out [3][hc][wc];
  * mask1_out optional [hc][wc]; ws: ss_linear_blend_workspace_floats(hc, wc) floats, 8-byte aligned (SS_ERR_ARG otherwise). */
 SS_API long long ss_linear_blend_workspace_floats(int hc, int wc);
@@ -426,6 +431,30 @@ SS_API int ss_canvas_watch(const float* src, int streams, int views, float guard
  * seen + frames, clipped and near frames counted one by one, the first clipped index = frames seen before + the index within the
  * batch, extents folded, a NaN point outside. */
 SS_API int ss_canvas_watch_frames(const float* src, int frames, int views, float guard, int* watch_i, float* watch_f, void* stream);
+/* Fixed-size streaming output (online.py: viewport=, grow='refit'): the watcher launches above + a device-side REFIT of each
+ * stream's canvas box, by the wave that ran the watcher.  The render takes the canvas' pixel count (the viewport hout x wout, each in
+ * 11..65535) and its box separately, and every launch reads the box on the device, so zooming out is a rewrite of four floats: no
+ * new shape, no new buffer, nothing to capture again.  State per stream, beside the watcher rows:
+ *   box [streams][4] fp32 = (wmin, wmax, hmin, hmax) in HR pixels;  epoch [streams] int32 = growths so far;
+ *   ext0 [streams][2] fp32 = the box' (width, height) when the canvas was set (ss_box_fit_aspect writes it).
+ * One sequential fp32 reading (csrc/common.h: canvas_fit_update; restated in numpy by tests/test_canvas_fit_abi.py), per stream:
+ *   1 trigger: with g = guard > 2.5e-4 ? guard : -2.5e-4, continue only if min(wf0, wf2) < -1 + g or max(wf1, wf3) > 1 - g;
+ *   2 needed box: x0 = min(wmin, wmin + ((min(wf0, -1) + 1) * ow) / 2), the other three sides likewise (the old box united with
+ *     everything seen on it);  3 each side grown by margin * its extent;  4 letterboxed about its centre to wout : hout (the taller
+ *     side of ow * hout against oh * wout decides; untouched when they are equal);
+ *   5 refused -- box, epoch and watch_f untouched, such frames stay cropped and counted -- when a new coordinate is not finite, when
+ *     an extent exceeds zoom_limit x ext0, or when no side moved by 0.5 px;
+ *   6 else the box is written, epoch += 1 and the stream's watch_f row starts again at {+inf, -inf, +inf, -inf} (its extents were
+ *     measured on the old box); watch_i goes on counting.
+ * ss_canvas_watch_frames_fit fits ONCE, behind the last frame of the batch.  SS_ERR_ARG before any launch: a null pointer,
+ * streams / frames / views <= 0, a negative or NaN guard, margin or zoom_limit, a viewport outside 11..65535. */
+SS_API int ss_canvas_watch_fit(const float* src, int streams, int views, float guard, int* watch_i, float* watch_f, float* box,
+                               int* epoch, const float* ext0, float margin, float zoom_limit, int hout, int wout, void* stream);
+SS_API int ss_canvas_watch_frames_fit(const float* src, int frames, int views, float guard, int* watch_i, float* watch_f,
+                                      float* box, int* epoch, const float* ext0, float margin, float zoom_limit, int hout,
+                                      int wout, void* stream);
+/* Step 4 alone on n boxes [n][4], in place, when a canvas is set; ext0 (NULL, or [n][2]) receives the fitted extents. */
+SS_API int ss_box_fit_aspect(float* boxes, float* ext0, int n, int hout, int wout, void* stream);
 /* One streaming push's control points of ALL views + the watcher above in ONE launch (one wave per stream; a batch-1 push is
  * bound by its launch count): meshes[v] = view v's newest LR-scale meshes, stream s at meshes[v] + s * mesh_frame_stride floats;
  * bboxes [4] (bbox_frame_stride 0: one canvas) or [streams][4] (4: a canvas per stream); out [streams][views][63][2] = what `views`

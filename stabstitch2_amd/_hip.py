@@ -83,6 +83,7 @@ SIGNATURES = {
     'ss_render_footprint_floats': (c_ll, [c_i, c_i, c_i]),
     'ss_render_footprints': (c_i, [c_fp, c_fp, c_fp] + [c_i] * 6 + [c_st]),
     'ss_render_footprints_watch': (c_i, [c_fp, c_fp, c_fp] + [c_i] * 6 + [c_f, c_fp, c_fp, c_st]),
+    'ss_render_footprints_watch_fit': (c_i, [c_fp, c_fp, c_fp] + [c_i] * 6 + [c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_f, c_f, c_st]),
     'ss_linear_blend_workspace_floats': (c_ll, [c_i, c_i]),
     'ss_linear_blend': (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_fp, c_st]),
     'ss_linear_clip_workspace_floats': (c_ll, [c_i, c_i, c_i, c_i]),
@@ -98,6 +99,9 @@ SIGNATURES = {
     'ss_mesh_normalize': (c_i, [c_fp, c_fp, c_fp, c_i, c_f, c_f, c_st]),
     'ss_canvas_watch': (c_i, [c_fp, c_i, c_i, c_f, c_fp, c_fp, c_st]),
     'ss_canvas_watch_frames': (c_i, [c_fp, c_i, c_i, c_f, c_fp, c_fp, c_st]),
+    'ss_canvas_watch_fit': (c_i, [c_fp, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_f, c_f, c_i, c_i, c_st]),
+    'ss_canvas_watch_frames_fit': (c_i, [c_fp, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_fp, c_fp, c_f, c_f, c_i, c_i, c_st]),
+    'ss_box_fit_aspect': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_st]),
     'ss_stream_normalize_watch': (c_i, [ctypes.c_void_p, c_i, c_ll, c_fp, c_i, c_fp, c_i, c_f, c_f, c_f, c_fp, c_fp, c_st]),
     'ss_mesh_normalize_views': (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_f, c_f, c_st]),
     'ss_mesh_normalize_views_boxes': (c_i, [c_fp, c_ll, c_fp, c_fp, c_i, c_i, c_i, c_f, c_f, c_st]),

@@ -86,6 +86,71 @@ __device__ __forceinline__ void canvas_watch_update(float xmin, float xmax, floa
     }
 }
 
+// Device-side refit of a streaming canvas whose OUTPUT SIZE is fixed (viewport hout x wout; online.py: grow='refit').  The render
+// kernels take the pixel count and the box separately and the box is read on the device, so zooming out is a rewrite of four
+// floats.  State per stream: box [4] (wmin, wmax, hmin, hmax in HR px), epoch (growths so far), ext0 [2] (the extents the canvas
+// was set with).  All arithmetic in __f*_rn intrinsics, one operation after the other: ONE sequential fp32 reading, restated in
+// numpy by tests/test_canvas_fit_abi.py.
+struct SsCanvasFit {
+    float* box;          // [streams][4]
+    int* epoch;          // [streams]
+    float* ext0;         // [streams][2] (width, height): written when the canvas is set, read by the fit
+    float margin, zoom_limit, wout, hout;
+};
+
+// letterbox (x0, x1, y0, y1) about its centre to the aspect wout : hout -- it only ever expands; untouched when ow * hout == oh * wout
+struct SsBox {
+    float x0, x1, y0, y1;
+};
+__device__ __forceinline__ SsBox canvas_fit_aspect(SsBox b, float wout, float hout) {
+    const float ow = __fsub_rn(b.x1, b.x0), oh = __fsub_rn(b.y1, b.y0);
+    const float pw = __fmul_rn(ow, hout), ph = __fmul_rn(oh, wout);
+    if (pw > ph) {
+        const float d = __fmul_rn(__fsub_rn(__fdiv_rn(pw, wout), oh), 0.5f);
+        b.y0 = __fsub_rn(b.y0, d); b.y1 = __fadd_rn(b.y1, d);
+    } else if (ph > pw) {
+        const float d = __fmul_rn(__fsub_rn(__fdiv_rn(ph, hout), ow), 0.5f);
+        b.x0 = __fsub_rn(b.x0, d); b.x1 = __fadd_rn(b.x1, d);
+    }
+    return b;
+}
+
+// Lane 0, right after canvas_watch_update on the same rows: when the running extents wf came within the guard of an edge, re-fix
+// the box around itself and everything seen on it (_CanvasWatch._needed_bbox's formula), grown by the margin and fitted to the
+// viewport's aspect.  Refused -- box, epoch and wf untouched, such frames stay cropped and counted as under grow='never' -- when a
+// new coordinate is not finite, when an extent would exceed zoom_limit x the initial one (a diverging mesh must not shrink the
+// picture to nothing), or when no side moves by half a pixel (_CanvasWatch._regrow's rule).  A commit resets wf: the extents were
+// measured on the old box; the counters of watch_i are stream totals and go on.
+__device__ __forceinline__ void canvas_fit_update(const SsCanvasFit& fit, int s, float guard, float* wf) {
+    const float slack = 2.5e-4f;
+    const float g = guard > slack ? guard : -slack;
+    const float lo = fminf(wf[0], wf[2]), hi = fmaxf(wf[1], wf[3]);
+    if (!(lo < __fadd_rn(-1.0f, g) || hi > __fsub_rn(1.0f, g))) return;
+    float* box = fit.box + 4 * s;
+    const float wmin = box[0], wmax = box[1], hmin = box[2], hmax = box[3];
+    const float ow = __fsub_rn(wmax, wmin), oh = __fsub_rn(hmax, hmin);
+    float x0 = __fadd_rn(wmin, __fmul_rn(__fmul_rn(__fadd_rn(fminf(wf[0], -1.0f), 1.0f), ow), 0.5f));
+    float x1 = __fadd_rn(wmin, __fmul_rn(__fmul_rn(__fadd_rn(fmaxf(wf[1], 1.0f), 1.0f), ow), 0.5f));
+    float y0 = __fadd_rn(hmin, __fmul_rn(__fmul_rn(__fadd_rn(fminf(wf[2], -1.0f), 1.0f), oh), 0.5f));
+    float y1 = __fadd_rn(hmin, __fmul_rn(__fmul_rn(__fadd_rn(fmaxf(wf[3], 1.0f), 1.0f), oh), 0.5f));
+    // (wmin + (wmax - wmin) may round an ulp short of wmax: the needed box is a union, it contains the old one)
+    x0 = fminf(x0, wmin); x1 = fmaxf(x1, wmax); y0 = fminf(y0, hmin); y1 = fmaxf(y1, hmax);
+    const float gw = __fmul_rn(fit.margin, __fsub_rn(x1, x0)), gh = __fmul_rn(fit.margin, __fsub_rn(y1, y0));
+    x0 = __fsub_rn(x0, gw); x1 = __fadd_rn(x1, gw); y0 = __fsub_rn(y0, gh); y1 = __fadd_rn(y1, gh);
+    const SsBox fb = canvas_fit_aspect(SsBox{x0, x1, y0, y1}, fit.wout, fit.hout);
+    x0 = fb.x0; x1 = fb.x1; y0 = fb.y0; y1 = fb.y1;
+    const float big = __FLT_MAX__;       // (finite: |v| <= FLT_MAX is false for an infinity and for a NaN)
+    if (!(fabsf(x0) <= big && fabsf(x1) <= big && fabsf(y0) <= big && fabsf(y1) <= big)) return;
+    if (__fsub_rn(x1, x0) > __fmul_rn(fit.zoom_limit, fit.ext0[2 * s]) ||
+        __fsub_rn(y1, y0) > __fmul_rn(fit.zoom_limit, fit.ext0[2 * s + 1]))
+        return;
+    const float moved = fmaxf(fmaxf(__fsub_rn(wmin, x0), __fsub_rn(x1, wmax)), fmaxf(__fsub_rn(hmin, y0), __fsub_rn(y1, hmax)));
+    if (moved < 0.5f) return;
+    box[0] = x0; box[1] = x1; box[2] = y0; box[3] = y1;
+    fit.epoch[s] += 1;
+    wf[0] = INFINITY; wf[1] = -INFINITY; wf[2] = INFINITY; wf[3] = -INFINITY;
+}
+
 
 #ifdef SS_TUNING
 // tools/ build only: buffer for per-workgroup s_memtime stamps (set through ss_debug_ptr, conv.hip)

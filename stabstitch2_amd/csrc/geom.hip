@@ -972,8 +972,27 @@ extern "C" int ss_mesh_normalize_views_boxes(const float* mesh, long long mesh_f
 // running {xmin, xmax, ymin, ymax} of the normalised coordinates over all frames seen -- what a grown canvas must cover.  State
 // lives on the device and is only read when somebody asks (no sync on the push path); capturable (one fixed-size launch).
 // (the wave's running extremes, NaN flag OR-ed over the lanes -> the stream's watcher state; lane 0 writes)
+// FIT (a compile-time flag: new instantiations, the watcher's own stay as they were): 1 -- lane 0 goes on with canvas_fit_update
+// (common.h) on the stream's box: the box's last reader of the push is the splines launch in front of this one, and the wave that
+// reads a stream's box is the one that writes it; 2 -- no watcher at all: block b letterboxes box b to the viewport's aspect
+// (ss_box_fit_aspect, when a canvas is set) and writes its extents to ext0.
+// (the fit's state is a parameter of the FIT instantiations only: `Fit` is SsCanvasFit there and empty for FIT = 0)
+template <int FIT, typename... Fit>
 __global__ __launch_bounds__(64) void canvas_watch_kernel(const float* __restrict__ src, int npts, float guard, int* __restrict__ watch_i,
-                                                          float* __restrict__ watch_f) {
+                                                          float* __restrict__ watch_f, Fit... fits) {
+    if constexpr (FIT == 2) {
+        const SsCanvasFit fit = (fits, ...);
+        if (threadIdx.x == 0) {
+            float* box = fit.box + 4 * blockIdx.x;
+            const SsBox b = canvas_fit_aspect(SsBox{box[0], box[1], box[2], box[3]}, fit.wout, fit.hout);
+            box[0] = b.x0; box[1] = b.x1; box[2] = b.y0; box[3] = b.y1;
+            if (fit.ext0) {
+                fit.ext0[2 * blockIdx.x] = __fsub_rn(b.x1, b.x0);
+                fit.ext0[2 * blockIdx.x + 1] = __fsub_rn(b.y1, b.y0);
+            }
+        }
+        return;
+    }
     const float* s = src + (long long)blockIdx.x * npts * 2;
     float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
     bool bad = false;
@@ -984,18 +1003,52 @@ __global__ __launch_bounds__(64) void canvas_watch_kernel(const float* __restric
         ymin = fminf(ymin, y); ymax = fmaxf(ymax, y);
     }
     canvas_watch_update(xmin, xmax, ymin, ymax, bad, guard, watch_i + blockIdx.x * 4, watch_f + blockIdx.x * 4);
+    if constexpr (FIT == 1) {
+        if (threadIdx.x == 0) canvas_fit_update((fits, ...), blockIdx.x, guard, watch_f + blockIdx.x * 4);
+    }
 }
 extern "C" int ss_canvas_watch(const float* src, int streams, int views, float guard, int* watch_i, float* watch_f, void* stream) {
     if (!src || !watch_i || !watch_f || streams <= 0 || views <= 0 || !(guard >= 0.f)) return SS_ERR_ARG;
-    hipLaunchKernelGGL(canvas_watch_kernel, dim3(streams), dim3(64), 0, (hipStream_t)stream, src, views * SS_NV, guard, watch_i, watch_f);
+    hipLaunchKernelGGL(canvas_watch_kernel<0>, dim3(streams), dim3(64), 0, (hipStream_t)stream, src, views * SS_NV, guard, watch_i, watch_f);
+    return ss_launch_status();
+}
+// the refusals the fit entries share: state pointers, margin / zoom_limit negative or NaN, a viewport outside 11..65535 (the range
+// of the LINEAR frames entry) -> false
+static bool canvas_fit_make(SsCanvasFit& fit, float* box, int* epoch, const float* ext0, float margin, float zoom_limit, int hout,
+                            int wout) {
+    if (!box || !epoch || !ext0 || !(margin >= 0.f) || !(zoom_limit >= 0.f) || hout < 11 || hout > 65535 || wout < 11 || wout > 65535)
+        return false;
+    fit.box = box; fit.epoch = epoch; fit.ext0 = const_cast<float*>(ext0);       // (read only by canvas_fit_update)
+    fit.margin = margin; fit.zoom_limit = zoom_limit; fit.wout = (float)wout; fit.hout = (float)hout;
+    return true;
+}
+extern "C" int ss_canvas_watch_fit(const float* src, int streams, int views, float guard, int* watch_i, float* watch_f, float* box,
+                                   int* epoch, const float* ext0, float margin, float zoom_limit, int hout, int wout, void* stream) {
+    SsCanvasFit fit;
+    if (!src || !watch_i || !watch_f || streams <= 0 || views <= 0 || !(guard >= 0.f) ||
+        !canvas_fit_make(fit, box, epoch, ext0, margin, zoom_limit, hout, wout))
+        return SS_ERR_ARG;
+    hipLaunchKernelGGL((canvas_watch_kernel<1, SsCanvasFit>), dim3(streams), dim3(64), 0, (hipStream_t)stream, src, views * SS_NV, guard, watch_i, watch_f,
+                       fit);
+    return ss_launch_status();
+}
+extern "C" int ss_box_fit_aspect(float* boxes, float* ext0, int n, int hout, int wout, void* stream) {
+    if (!boxes || n <= 0 || hout < 11 || hout > 65535 || wout < 11 || wout > 65535) return SS_ERR_ARG;
+    SsCanvasFit fit{};
+    fit.box = boxes; fit.ext0 = ext0;
+    fit.wout = (float)wout; fit.hout = (float)hout;
+    hipLaunchKernelGGL((canvas_watch_kernel<2, SsCanvasFit>), dim3(n), dim3(64), 0, (hipStream_t)stream, (const float*)nullptr, 0, 0.f, (int*)nullptr,
+                       (float*)nullptr, fit);
     return ss_launch_status();
 }
 
 // k consecutive frames of ONE stream (OnlineStitcher.push_many): src [frames][views][63][2] -> the stream's single watcher row, frame
 // by frame in stream order -- the row ends as `frames` launches of canvas_watch_kernel leave it (frames seen, clipped and near counted
 // one by one, the first clipped index taken from the running count, extents folded).  One wave; lane 0 owns the row.
+// FIT: ONE canvas_fit_update behind the batch's last frame (a drift inside one call can crop up to `frames` counted frames).
+template <int FIT, typename... Fit>
 __global__ __launch_bounds__(64) void canvas_watch_frames_kernel(const float* __restrict__ src, int frames, int npts, float guard,
-                                                                 int* __restrict__ watch_i, float* __restrict__ watch_f) {
+                                                                 int* __restrict__ watch_i, float* __restrict__ watch_f, Fit... fits) {
     for (int f = 0; f < frames; ++f) {
         const float* s = src + (long long)f * npts * 2;
         float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
@@ -1008,12 +1061,26 @@ __global__ __launch_bounds__(64) void canvas_watch_frames_kernel(const float* __
         }
         canvas_watch_update(xmin, xmax, ymin, ymax, bad, guard, watch_i, watch_f);
     }
+    if constexpr (FIT == 1) {
+        if (threadIdx.x == 0) canvas_fit_update((fits, ...), 0, guard, watch_f);
+    }
 }
 extern "C" int ss_canvas_watch_frames(const float* src, int frames, int views, float guard, int* watch_i, float* watch_f,
                                       void* stream) {
     if (!src || !watch_i || !watch_f || frames <= 0 || views <= 0 || !(guard >= 0.f)) return SS_ERR_ARG;
-    hipLaunchKernelGGL(canvas_watch_frames_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, src, frames, views * SS_NV, guard,
+    hipLaunchKernelGGL(canvas_watch_frames_kernel<0>, dim3(1), dim3(64), 0, (hipStream_t)stream, src, frames, views * SS_NV, guard,
                        watch_i, watch_f);
+    return ss_launch_status();
+}
+extern "C" int ss_canvas_watch_frames_fit(const float* src, int frames, int views, float guard, int* watch_i, float* watch_f,
+                                          float* box, int* epoch, const float* ext0, float margin, float zoom_limit, int hout,
+                                          int wout, void* stream) {
+    SsCanvasFit fit;
+    if (!src || !watch_i || !watch_f || frames <= 0 || views <= 0 || !(guard >= 0.f) ||
+        !canvas_fit_make(fit, box, epoch, ext0, margin, zoom_limit, hout, wout))
+        return SS_ERR_ARG;
+    hipLaunchKernelGGL((canvas_watch_frames_kernel<1, SsCanvasFit>), dim3(1), dim3(64), 0, (hipStream_t)stream, src, frames, views * SS_NV, guard,
+                       watch_i, watch_f, fit);
     return ss_launch_status();
 }
 

@@ -222,9 +222,15 @@ __device__ __forceinline__ float avg_fuse(float a, float b) {
 // near-affine warp cancel, the bound does not -- it came out at 100-140 source pixels and kept a third of the skippable
 // tiles.)  tests/test_gpu_parity.py::test_render_footprint_skipping checks on pipeline meshes that every skipped pixel is
 // outside (validity mask of the full evaluation ~ 0) and that nothing else changes.
+// FIT (a compile-time flag: a new instantiation, FIT = 0 is the kernel as it was): the wave that ran the watcher goes on with
+// canvas_fit_update (common.h) on its stream's box -- the box's last reader of the push is the splines launch in front of this one,
+// and nothing else in this launch looks at it.
+// (the fit's state is a parameter of the FIT instantiation only: `Fit` is SsCanvasFit there and empty for FIT = 0)
+template <int FIT, typename... Fit>
 __global__ void render_lattice_kernel(const float* __restrict__ source, const float* __restrict__ T,
                                       float* __restrict__ fp, long long frame_stride, int views, int hc, int wc,
-                                      int ny, int nx, float guard, int* __restrict__ watch_i, float* __restrict__ watch_f) {
+                                      int ny, int nx, float guard, int* __restrict__ watch_i, float* __restrict__ watch_f,
+                                      Fit... fits) {
     const int fv = blockIdx.y;                       // frame * views + view
     const int frame = fv / views, view = fv - frame * views;
     float* lattice = fp + frame * frame_stride + (long long)view * ny * nx * 2;
@@ -257,6 +263,9 @@ __global__ void render_lattice_kernel(const float* __restrict__ source, const fl
             ymin = fminf(ymin, y); ymax = fmaxf(ymax, y);
         }
         canvas_watch_update(xmin, xmax, ymin, ymax, bad, guard, watch_i + frame * 4, watch_f + frame * 4);
+        if constexpr (FIT == 1) {
+            if (threadIdx.x == 0) canvas_fit_update((fits, ...), frame, guard, watch_f + frame * 4);
+        }
     }
     if (idx >= ny * nx) return;
     const int i = idx / nx, j = idx - i * nx;
@@ -348,8 +357,9 @@ extern "C" long long ss_render_footprint_floats(int views, int hc, int wc) {
 }
 
 // footprints of `frames` x `views` splines in one launch: fp [frames][ lattice [views][ny][nx][2] | margin [views][2] ]
+template <int FIT>
 static int render_footprints_launch(const float* source, const float* T, float* fp, int frames, int views, int h, int w,
-                                    int hc, int wc, float guard, int* watch_i, float* watch_f, void* stream) {
+                                    int hc, int wc, float guard, int* watch_i, float* watch_f, SsCanvasFit fit, void* stream) {
     if (!source || !T || !fp || frames <= 0 || views <= 0 || views > 3 || h <= 1 || w <= 1 || hc <= 1 || wc <= 1)
         return SS_ERR_ARG;
     const int ny = ss_cdiv(hc, 8) + 1, nx = 2 * ss_cdiv(wc, 64) + 1;
@@ -360,10 +370,20 @@ static int render_footprints_launch(const float* source, const float* T, float* 
     const int fmax = 65535 / views;
     for (int f0 = 0; f0 < frames; f0 += fmax) {
         const int nf = frames - f0 < fmax ? frames - f0 : fmax;
-        hipLaunchKernelGGL(render_lattice_kernel, dim3(ss_cdiv(ny * nx, 128), nf * views), dim3(128), 0, (hipStream_t)stream,
-                           source + (long long)f0 * views * SS_NV * 2, T + (long long)f0 * views * 2 * SS_NT,
-                           fp + (long long)f0 * stride, stride, views, hc, wc, ny, nx, guard, watch_i ? watch_i + 4 * f0 : nullptr,
-                           watch_f ? watch_f + 4 * f0 : nullptr);
+        const float* src0 = source + (long long)f0 * views * SS_NV * 2;
+        const float* T0 = T + (long long)f0 * views * 2 * SS_NT;
+        int* wi0 = watch_i ? watch_i + 4 * f0 : nullptr;
+        float* wf0 = watch_f ? watch_f + 4 * f0 : nullptr;
+        if constexpr (FIT == 1) {
+            SsCanvasFit fit0 = fit;                 // (this launch's frame 0 is stream f0)
+            fit0.box += 4 * f0; fit0.epoch += f0; fit0.ext0 += 2 * f0;
+            hipLaunchKernelGGL((render_lattice_kernel<1, SsCanvasFit>), dim3(ss_cdiv(ny * nx, 128), nf * views), dim3(128), 0,
+                               (hipStream_t)stream, src0, T0, fp + (long long)f0 * stride, stride, views, hc, wc, ny, nx, guard, wi0, wf0,
+                               fit0);
+        } else {
+            hipLaunchKernelGGL(render_lattice_kernel<0>, dim3(ss_cdiv(ny * nx, 128), nf * views), dim3(128), 0, (hipStream_t)stream,
+                               src0, T0, fp + (long long)f0 * stride, stride, views, hc, wc, ny, nx, guard, wi0, wf0);
+        }
     }
     const int nt = (ny - 1) * ((nx - 1) / 2);
     for (int f0 = 0; f0 < frames; f0 += 65535) {
@@ -376,7 +396,7 @@ static int render_footprints_launch(const float* source, const float* T, float* 
 
 extern "C" int ss_render_footprints(const float* source, const float* T, float* fp, int frames, int views, int h, int w,
                                     int hc, int wc, void* stream) {
-    return render_footprints_launch(source, T, fp, frames, views, h, w, hc, wc, 0.f, nullptr, nullptr, stream);
+    return render_footprints_launch<0>(source, T, fp, frames, views, h, w, hc, wc, 0.f, nullptr, nullptr, SsCanvasFit{}, stream);
 }
 
 // the same + the streaming canvas' overflow watcher (ss_canvas_watch's update of watch_i / watch_f [frames][4], frame = stream) inside
@@ -384,7 +404,21 @@ extern "C" int ss_render_footprints(const float* source, const float* T, float* 
 extern "C" int ss_render_footprints_watch(const float* source, const float* T, float* fp, int frames, int views, int h, int w,
                                           int hc, int wc, float guard, int* watch_i, float* watch_f, void* stream) {
     if (!watch_i || !watch_f || !(guard >= 0.f)) return SS_ERR_ARG;
-    return render_footprints_launch(source, T, fp, frames, views, h, w, hc, wc, guard, watch_i, watch_f, stream);
+    return render_footprints_launch<0>(source, T, fp, frames, views, h, w, hc, wc, guard, watch_i, watch_f, SsCanvasFit{}, stream);
+}
+
+// the same + the device-side refit of the streams' boxes (canvas_fit_update: ss_canvas_watch_fit has the state's layout) behind the
+// watcher, in the same wave; the viewport is the canvas size hc x wc itself
+extern "C" int ss_render_footprints_watch_fit(const float* source, const float* T, float* fp, int frames, int views, int h, int w,
+                                              int hc, int wc, float guard, int* watch_i, float* watch_f, float* box, int* epoch,
+                                              const float* ext0, float margin, float zoom_limit, void* stream) {
+    if (!watch_i || !watch_f || !(guard >= 0.f) || !box || !epoch || !ext0 || !(margin >= 0.f) || !(zoom_limit >= 0.f) ||
+        frames <= 0 || hc < 11 || hc > 65535 || wc < 11 || wc > 65535)
+        return SS_ERR_ARG;
+    SsCanvasFit fit;
+    fit.box = box; fit.epoch = epoch; fit.ext0 = const_cast<float*>(ext0);       // (read only by canvas_fit_update)
+    fit.margin = margin; fit.zoom_limit = zoom_limit; fit.wout = (float)wc; fit.hout = (float)hc;
+    return render_footprints_launch<1>(source, T, fp, frames, views, h, w, hc, wc, guard, watch_i, watch_f, fit, stream);
 }
 
 __device__ __forceinline__ void sample3(const float* __restrict__ in, float xn, float yn, int w, int h, long long hw, int mode,

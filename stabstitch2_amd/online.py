@@ -15,6 +15,12 @@ Canvas overflow (round 5): the reference would have sized the canvas from ALL fr
 as a frame comes within half the margin of an edge -- checked through an asynchronous copy of the watcher state one push later, so
 a gradual drift grows the canvas BEFORE anything is cropped (an abrupt jump still crops the frames in between; they are counted).
 
+Fixed-size output: `viewport=(Hout, Wout)` makes every frame of a stream Hout x Wout from construction on -- the canvas box (the box
+the stitcher would have had, letterboxed to the viewport's aspect) is decoupled from the pixel count, and the render samples the
+continuous warp at the viewport's lattice.  `grow='refit'` (viewport only) then re-fixes the BOX on the device, inside the launch
+that carries the watcher (`ss_canvas_watch_fit`, `ss_render_footprints_watch_fit`), as soon as the running extents come within the
+guard of an edge: the picture zooms out, and nothing on the host changes -- no new shape, no new buffer, no capture, no sync.
+
 Once the window is full every push runs the same ~150 small kernels on buffers of fixed size, so the steady state is
 captured ONCE into a HIP graph (state lives in static tensors: the rings are shifted, not rotated) and each push is
 two input copies + one graph launch: the Python / ctypes launch overhead (~1 ms per pair, more than the kernels'
@@ -178,8 +184,10 @@ class _CanvasWatch:
     totals of the canvases each row had before, and for grow='recapture' a pinned copy of the rows one push behind and the arithmetic
     that re-fixes a canvas around everything seen on it."""
 
-    def __init__(self, n, margin, dev):
+    def __init__(self, n, margin, dev, viewport=None, refit=False, zoom_limit=2.0):
         self.n, self.margin, self.dev = n, margin, dev
+        self.viewport, self.refit, self.zoom_limit = viewport, bool(refit), float(zoom_limit)
+        self.fit = None                                # grow='refit': ops.CanvasFit -- box [N,4] / epoch [N] / ext0 [N,2] on the device
         self.wi = self.wf = None                       # device rows of the current canvases (None: no canvas yet)
         self.boxes = None                              # the current canvases (wmin, wmax, hmin, hmax in HR px), CPU fp32 [N,4]
         self.totals = [[0, 0, -1] for _ in range(n)]  # frames seen / clipped / first clipped frame on EARLIER canvases
@@ -198,6 +206,37 @@ class _CanvasWatch:
             return self.guard, self.wi, self.wf
         return self.guard, self.wi[s:s + 1], self.wf[s:s + 1]
 
+    def fit_boxes(self, dev_boxes, fit_state=None):
+        """A viewport: the canvases dev_boxes (device fp32 [N,4], the tensor the push's launches read) are letterboxed in place to its
+        aspect (ops.box_fit_aspect), or -- fit_state = (epoch [N], ext0 [N,2]) -- taken as they are with that state carried over; with
+        grow='refit' they become the device-side state of the refit.  -> the boxes, CPU fp32 [N,4] (synchronises)."""
+        hout, wout = self.viewport
+        if fit_state is None:
+            _, epoch, ext0 = ops.canvas_fit_state(self.n, self.dev)
+            ops.box_fit_aspect(dev_boxes, hout, wout, ext0)
+        else:
+            epoch, ext0 = fit_state
+        if self.refit:
+            self.fit = ops.CanvasFit(dev_boxes.view(self.n, 4), epoch, ext0, max(0.0, float(self.margin)), self.zoom_limit, hout, wout)
+        return dev_boxes.cpu().reshape(self.n, 4)
+
+    def fit_args(self, s=None):
+        """The ops.CanvasFit of all rows, or of row s, for the launches that carry the watcher (None unless grow='refit')."""
+        f = self.fit
+        if f is None or s is None:
+            return f
+        return f._replace(box=f.box[s:s + 1], epoch=f.epoch[s:s + 1], ext0=f.ext0[s:s + 1])
+
+    def fit_state(self):
+        """The refit's step-mutated tensors (box, epoch): state of the captured step beside the watcher rows."""
+        return [] if self.fit is None else [self.fit.box, self.fit.epoch]
+
+    def current(self):
+        """-> (boxes CPU fp32 [N,4], growths per canvas); grow='refit': read from the device (synchronises)."""
+        if self.fit is None:
+            return self.boxes, list(self.epoch)
+        return self.fit.box.cpu(), self.fit.epoch.cpu().tolist()
+
     def start(self, boxes, state=None):
         """Watch these canvases (CPU fp32 [N,4]) from now on: fresh rows, or state = (wi, wf) carried over."""
         self.boxes = boxes
@@ -208,14 +247,16 @@ class _CanvasWatch:
     def report(self):
         """Synchronises.  -> one dict per canvas: {'frames_seen', 'clipped_frames', 'first_clipped_frame' (stream frame index, -1 =
         none), 'near_frames' (current canvas), 'canvas_epoch', 'needed_bbox' (wmin, wmax, hmin, hmax in HR px: the current canvas
-        united with every mesh seen on it)}."""
+        united with every mesh seen on it), 'box' (the current canvas, HR px; None before it is fixed)}."""
         wi = None if self.wi is None else self.wi.cpu().tolist()
         wf = None if self.wf is None else self.wf.cpu()
+        boxes, epochs = self.current()
         reps = []
         for s in range(self.n):
             seen, clipped, first = self.totals[s]
             rep = {'frames_seen': seen, 'clipped_frames': clipped, 'first_clipped_frame': first, 'near_frames': 0,
-                   'canvas_epoch': self.epoch[s], 'needed_bbox': None}
+                   'canvas_epoch': epochs[s], 'needed_bbox': None,
+                   'box': None if boxes is None else tuple(float(x) for x in boxes[s])}
             if wi is not None:
                 w = wi[s]
                 if w[1] > 0 and first < 0:
@@ -223,13 +264,14 @@ class _CanvasWatch:
                 rep['frames_seen'] = seen + w[0]
                 rep['clipped_frames'] = clipped + w[1]
                 rep['near_frames'] = w[3]
-                rep['needed_bbox'] = tuple(float(x) for x in self._needed_bbox(s, wf[s]))
+                rep['needed_bbox'] = tuple(float(x) for x in self._needed_bbox(s, wf[s], boxes[s]))
             reps.append(rep)
         return reps
 
-    def _needed_bbox(self, s, wf):
-        """Running normalised extents [xmin, xmax, ymin, ymax] on canvas s -> union with the canvas, HR pixels."""
-        bb = self.boxes[s]
+    def _needed_bbox(self, s, wf, bb=None):
+        """Running normalised extents [xmin, xmax, ymin, ymax] on canvas s (bb: its box, read elsewhere) -> union with the canvas, HR
+        pixels."""
+        bb = self.boxes[s] if bb is None else bb
         ow, oh = float(bb[1] - bb[0]), float(bb[3] - bb[2])
         x0 = float(bb[0]) + (min(float(wf[0]), -1.0) + 1.0) * ow / 2.0
         x1 = float(bb[0]) + (max(float(wf[1]), 1.0) + 1.0) * ow / 2.0
@@ -305,10 +347,30 @@ class _Stitcher:
     _U8_STEADY = True        # push_u8 in the steady state: the resize writes the graph's LR inputs, the render samples the uint8 frames
     _LINEAR_DIRECT = True    # may LINEAR fusion take the direct render (DIRECT_LINEAR)?  Not with two pushes in flight (_TwoInFlight)
 
-    def __init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only=False, canvases=1):
-        if grow not in ('never', 'recapture'):
-            raise ValueError("grow must be 'never' or 'recapture'")
+    def __init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only=False, canvases=1,
+                 viewport=None, zoom_limit=2.0):
+        if grow not in ('never', 'recapture', 'refit'):
+            raise ValueError("grow must be 'never', 'recapture' or 'refit'")
+        if viewport is not None:
+            try:
+                viewport = (int(viewport[0]), int(viewport[1]))
+                ok = len(viewport) == 2 and all(11 <= v <= 65535 for v in viewport)
+            except (TypeError, ValueError, IndexError):
+                ok = False
+            if not ok:
+                raise ValueError('viewport must be (Hout, Wout) with each of them in 11..65535, got %r' % (viewport,))
+            if meshes_only:
+                raise ValueError('viewport sizes rendered frames: not for meshes_only stitchers')
+            if grow == 'recapture':
+                raise ValueError("grow='recapture' changes the frame size: not with a viewport (grow='refit' keeps it)")
+        elif grow == 'refit':
+            raise ValueError("grow='refit' needs a viewport: it re-fixes the canvas box under a fixed frame size")
+        if not float(zoom_limit) >= 0.0:
+            raise ValueError('zoom_limit must be >= 0, got %r' % (zoom_limit,))
         self.grow = grow
+        self.viewport, self.zoom_limit = viewport, float(zoom_limit)
+        self.hc, self.wc = viewport if viewport is not None else (None, None)
+        self._canvas_set = False         # is the canvas box fixed yet?  (with a viewport hc / wc are known before it is)
         self.nets = nets
         self.spatial, self.temporal, self.smooth = nets
         self.dev = next(self.spatial.parameters()).device
@@ -320,7 +382,8 @@ class _Stitcher:
         direct = fusion_mode == 'AVERAGE' or (fusion_mode == 'LINEAR' and DIRECT_LINEAR and self._LINEAR_DIRECT)
         self._direct_render = bool(DIRECT_RENDER and use_graph and direct and not self.meshes_only)
         self._lin_ws = {}                # direct LINEAR render: chunk -> ((canvas sizes, views), workspace), re-made when a canvas changes
-        self.watch = _CanvasWatch(canvases, margin, self.dev)      # overflow of the fixed canvas(es); meshes_only: never started
+        # overflow of the fixed canvas(es), and the device-side refit of their boxes; meshes_only: never started
+        self.watch = _CanvasWatch(canvases, margin, self.dev, viewport, grow == 'refit', zoom_limit)
         self.static = None               # steady-state buffers (inputs, rings, output) once the window is full
         self.graph = None
         self.graph_nodes = None          # nodes of the captured steady-state graph (None: not captured / not exposed)
@@ -335,7 +398,7 @@ class _Stitcher:
     def overflow_report(self):
         """Synchronises.  -> {'frames_seen', 'clipped_frames', 'first_clipped_frame' (stream frame index, -1 = none), 'near_frames'
         (current canvas), 'canvas_epoch', 'needed_bbox' (wmin, wmax, hmin, hmax in HR px: the current canvas united with every
-        mesh seen on it)}."""
+        mesh seen on it), 'box' (the current canvas, HR px; None before it is fixed)}."""
         return self.watch.report()[0]
 
     @property
@@ -344,13 +407,39 @@ class _Stitcher:
         rep = self.overflow_report()
         return [r['clipped_frames'] for r in rep] if isinstance(rep, list) else rep['clipped_frames']
 
+    def _sync_state(self):
+        """Before the device state is read: nothing here -- the reading copy waits for the caller's stream, which runs every push."""
+
     @property
     def canvas_epoch(self):
-        """Growths of the canvas (grow='recapture'; per stream for MultiOnlineStitcher)."""
-        return list(self.watch.epoch) if isinstance(self, MultiOnlineStitcher) else self.watch.epoch[0]
+        """Growths of the canvas (grow='recapture' / 'refit'; per stream for MultiOnlineStitcher).  grow='refit': the count lives on
+        the device -- synchronises."""
+        if self.watch.fit is not None:
+            self._sync_state()
+        epochs = self.watch.current()[1]
+        return epochs if isinstance(self, MultiOnlineStitcher) else epochs[0]
+
+    @property
+    def canvas_box(self):
+        """The canvas box (wmin, wmax, hmin, hmax) in HR pixels the next frame is rendered on (per stream for MultiOnlineStitcher;
+        None before the first window is complete).  grow='refit': the box lives on the device -- synchronises."""
+        if self.watch.fit is not None:
+            self._sync_state()
+        boxes = self.watch.current()[0]
+        if boxes is None:
+            return [None] * self.watch.n if isinstance(self, MultiOnlineStitcher) else None
+        boxes = [tuple(float(x) for x in b) for b in boxes]
+        return boxes if isinstance(self, MultiOnlineStitcher) else boxes[0]
 
     def _set_canvas(self):
-        """The canvas is fixed at self.bbox: its size, a fresh watcher on it."""
+        """The canvas is fixed at self.bbox: its size, a fresh watcher on it.  With a viewport the size is the viewport's, and the
+        box is letterboxed to its aspect (on the device, in place: it is the tensor every later launch reads -- and grow='refit'
+        rewrites)."""
+        self._canvas_set = True
+        if self.viewport is not None:
+            self.bbox = self.bbox.to(torch.float32).contiguous()
+            self.watch.start(self.watch.fit_boxes(self.bbox))
+            return
         bb = self.bbox.cpu()
         self.hc, self.wc = _canvas_size(bb)
         self.watch.start(bb[None])
@@ -380,7 +469,7 @@ class _Stitcher:
 
     def _state(self):
         st = self.static
-        return [st[k] for k in _STATE] + ([] if self.meshes_only else [self.watch.wi, self.watch.wf])
+        return [st[k] for k in _STATE] + ([] if self.meshes_only else [self.watch.wi, self.watch.wf] + self.watch.fit_state())
 
     def _drop_graphs(self):
         """The canvas grew or a net was reloaded: the captured steady-state graphs hold the old canvas / weights by address."""
@@ -436,17 +525,19 @@ class _Stitcher:
             return [[o.clone()] for o in out] if isinstance(out, list) else [out.clone()]
         return self._render_direct(deferred, imgs, u8)
 
-    def _render_solved(self, imgs, src, T, out=None, watch=None):
+    def _render_solved(self, imgs, src, T, out=None, watch=None, fit=None):
         """src [V,63,2] normalised control points on this canvas, T [V,2,66] their splines -> the stitched frame of the V = 2 | 3 views
         imgs [1,3,H,W] (written to `out` if given; out=_DEFER: splines and footprint left in self._deferred for the push's render).
-        watch = (guard, watch_i [1,4], watch_f [1,4]): the overflow watcher has not seen `src` yet."""
+        watch = (guard, watch_i [1,4], watch_f [1,4]): the overflow watcher has not seen `src` yet; fit (grow='refit'): the
+        ops.CanvasFit of this canvas -- the launch that carries the watcher re-fixes the box behind it."""
         if watch is not None and not (self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE):
-            ops.canvas_watch(src[None], watch[1], watch[2], watch[0])            # no footprint launch to carry it
+            ops.canvas_watch(src[None], watch[1], watch[2], watch[0], fit=fit)   # no footprint launch to carry it
             watch = None
         if self.fusion_mode == 'AVERAGE':
             fp = None
             if pipeline.SKIP_OUTSIDE:        # same footprint skipping as the offline render (pipeline.render_frames)
-                fp = ops.render_footprints(src[None], T[None], self.h, self.w, self.hc, self.wc, watch=watch)[0]
+                fp = ops.render_footprints(src[None], T[None], self.h, self.w, self.hc, self.wc, watch=watch,
+                                           fit=None if watch is None else fit)[0]
             if out is _DEFER:
                 self._deferred = (src, T, fp)
                 return None
@@ -588,20 +679,34 @@ class _Stitcher:
 
 class OnlineStitcher(_Stitcher):
     def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 use_graph=True, grow='never', meshes_only=False, deterministic=False):
+                 use_graph=True, grow='never', meshes_only=False, deterministic=False, viewport=None, zoom_limit=2.0):
         """canvas: optional (wmin, wmax, hmin, hmax) in HR pixels (e.g. the offline bbox).
+        viewport: optional (Hout, Wout), each in 11..65535 -- the size of EVERY frame this stitcher returns ([3,Hout,Wout] fp32,
+        [Hout,Wout,3] uint8 from push_u8 / push_many_u8; the first window's seven included), known from construction: `hc, wc ==
+        Hout, Wout`, so an encoder or a pinned result ring can be sized before the first push.  The canvas box is the box the
+        stitcher would have had (the first window's box grown by `margin`, or `canvas`), letterboxed about its centre to the
+        viewport's aspect (it only ever expands; untouched when ow * Hout == oh * Wout in fp32); the render samples the continuous
+        warp at the viewport's pixel lattice.  A viewport smaller than the box is POINT-SAMPLED: nothing prefilters, fine detail
+        aliases.  None (default): the size is the box' extent in whole pixels, as ever.
         deterministic: every push under the conv engine's geometry-only kernel policy (ops.deterministic): with the offline canvas the
         stream's frames equal the resident clip's (pipeline.run_two_view(..., deterministic=True)) bit for bit; ~1.6x slower pushes.
         meshes_only: no canvas, no render -- `push` returns the newly smoothed meshes (m1, m2) [k,7,9,2] (k = 7 on the 7th push,
         then 1) or None; the building block of ThreeViewOnlineStitcher, which captures the graph itself (use_graph is ignored).
         grow: 'never' -- the canvas fixed after the first window stays (frames whose mesh leaves it are cropped and COUNTED:
         `clipped_frames`); 'recapture' -- the canvas grows (and the steady-state graph is captured again) when a mesh comes within
-        half the margin of its edge; `canvas_epoch` counts the growths, `hc` / `wc` / `bbox` change with them."""
-        _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only)
+        half the margin of its edge; `canvas_epoch` counts the growths, `hc` / `wc` / `bbox` change with them; 'refit' (only with a
+        viewport; 'recapture' not with one) -- the BOX is re-fixed on the device, inside the push's own launches, as soon as the
+        watcher's running extents come within that guard: the picture zooms out (the new box contains the old one), while graphs,
+        output buffers, workspaces and `hc` / `wc` stay as they are -- nothing is captured again, nothing synchronises.  A growth is
+        refused, and such frames are cropped and counted as under 'never', when the new box is not finite, when an extent would
+        exceed `zoom_limit` x the one the canvas was set with (a diverging mesh must not shrink the picture to nothing), or when no
+        side moves by half a pixel.  `canvas_epoch`, `canvas_box` and `overflow_report()` then read the device (they synchronise).
+        push_many takes one refit per call, behind the batch's watcher: a drift inside one call can crop up to k counted frames."""
+        _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only,
+                           viewport=viewport, zoom_limit=zoom_limit)
         self.deterministic = bool(deterministic)
         self.last_meshes = None
         self.bbox = None if canvas is None else torch.tensor(canvas, dtype=torch.float32, device=self.dev)
-        self.hc = self.wc = None
         self.nrigid = get_norm_mesh(get_rigid_mesh(1, height, width, device=self.dev), height, width).contiguous()
         self.prev_feat = None            # TemporalNet stage-1 features of the previous frame, both views [2,45,60,128]
         self.prev_smotion = None         # [2,7,9,2]
@@ -614,7 +719,7 @@ class OnlineStitcher(_Stitcher):
         """mesh* [1,7,9,2] LR-scale smoothed meshes of ONE frame -> stitched frame [3,Hc,Wc] (written to `out` if given).  Control
         points + splines in one launch, the watcher inside the footprint launch."""
         src4, T4 = ops.stream_splines([mesh1, mesh2], 126, self.bbox, self.nrigid, self.h, self.w)
-        return self._render_solved([hr1, hr2], src4[0], T4[0], out, watch=self.watch.args())
+        return self._render_solved([hr1, hr2], src4[0], T4[0], out, watch=self.watch.args(), fit=self.watch.fit_args())
 
     # ------------------------------------------------------------------ steady state (window full, canvas fixed)
     def _init_static(self):
@@ -751,7 +856,7 @@ class OnlineStitcher(_Stitcher):
             self.ring_tsm[v] = (self.ring_tsm[v] + [tsm])[-WINDOW:]
         self.prev_smotion = smotion
         self.frames_in += 1
-        if self.hc is None and not self.meshes_only:
+        if not self._canvas_set and not self.meshes_only:
             self.ring_hr.append((hr1, hr2))
         if self.frames_in < WINDOW:
             return None if self.meshes_only else []
@@ -765,7 +870,7 @@ class OnlineStitcher(_Stitcher):
             self._init_static()
             self.last_meshes = (m1, m2)
             return self.last_meshes
-        if self.hc is None:                                                        # first window: fix the canvas, emit 7
+        if not self._canvas_set:                                                   # first window: fix the canvas, emit 7
             if self.bbox is None:
                 self.bbox = self._grown(ops.mesh_bbox([m1, m2], self.h, self.w))
             self._set_canvas()
@@ -839,7 +944,7 @@ class OnlineStitcher(_Stitcher):
         m1, m2 = outs['smooth_mesh1'], outs['smooth_mesh2']                      # [k,7,7,9,2]: frame j's mesh is window j's last
         src, T = ops.stream_splines([m1[0, -1], m2[0, -1]], WINDOW * e, self.bbox, self.nrigid, self.h, self.w, frames=k)
         guard, wi, wf = self.watch.args()
-        ops.canvas_watch_frames(src, wi, wf, guard)
+        ops.canvas_watch_frames(src, wi, wf, guard, fit=self.watch.fit_args())
         fp = None
         if self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE:
             fp = ops.render_footprints(src, T, self.h, self.w, self.hc, self.wc)
@@ -878,6 +983,9 @@ class _TwoInFlight:
     frames of the PREVIOUS push (valid on the caller's stream), `flush()` the last ones.
     LINEAR fusion stays inside the graphs here (_LINEAR_DIRECT = False): with two pushes in flight the direct LINEAR render would
     need a workspace per buffer parity.
+    grow='refit' (with a viewport) holds with two pushes in flight: only second halves touch the canvas box (the splines launch reads
+    it, the launch that carries the watcher rewrites it), and the second halves and direct renders of consecutive pushes all run in
+    order on the ONE stream sb -- the box push t rewrites is the box push t + 1 reads.  grow='recapture' is not offered.
     A subclass provides _pipe_alloc / _pipe_load / _run_a / _run_b (and _pipe_empty for S streams)."""
     _LINEAR_DIRECT = False
 
@@ -1021,9 +1129,18 @@ class _TwoInFlight:
         return conv(self.flush())
 
     def overflow_report(self):
+        self._sync_state()
+        return super().overflow_report()
+
+    def _sync_state(self):
+        """The pushes run on the pipe's own streams: all of them must have ended before the device state is read."""
         if getattr(self, 'pipe', None) is not None:
             torch.cuda.synchronize(self.dev)
-        return super().overflow_report()
+
+    @staticmethod
+    def _check_grow(grow):
+        if grow not in ('never', 'refit'):
+            raise ValueError("grow must be 'never' or 'refit' for a stitcher with two pushes in flight, got %r" % (grow,))
 
 
 def _tensors_of(x):
@@ -1041,11 +1158,14 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
         for pair in stream: for frame in st.push(*pair): ...
         for frame in st.flush(): ...
     0.64 ms per push = 1559 frames/s at 720p against 0.85 ms / 1171.  The canvas is fixed after the first window (grow='never';
-    overflow is counted as in OnlineStitcher).  LINEAR fusion renders inside the graphs (no direct LINEAR render: _TwoInFlight)."""
+    overflow is counted as in OnlineStitcher) or, with a viewport, re-fixed on the device (grow='refit').  LINEAR fusion renders inside the graphs (no direct LINEAR render: _TwoInFlight)."""
 
-    def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE', deterministic=False):
-        OnlineStitcher.__init__(self, nets, height, width, canvas, margin, warp_mode, fusion_mode, use_graph=True, grow='never',
-                                meshes_only=False, deterministic=deterministic)
+    def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE', deterministic=False,
+                 grow='never', viewport=None, zoom_limit=2.0):
+        """grow: 'never', or 'refit' with a viewport (see OnlineStitcher and _TwoInFlight)."""
+        self._check_grow(grow)
+        OnlineStitcher.__init__(self, nets, height, width, canvas, margin, warp_mode, fusion_mode, use_graph=True, grow=grow,
+                                meshes_only=False, deterministic=deterministic, viewport=viewport, zoom_limit=zoom_limit)
         self._pipe_init()
 
     def push_many(self, *frames):
@@ -1113,14 +1233,16 @@ class MultiOnlineStitcher(_Stitcher):
     stream's result is independent of its neighbours bit for bit (tests/test_gpu_round4.py)."""
 
     def __init__(self, nets, height, width, streams, canvases=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 use_graph=True, grow='never', meshes_only=False, deterministic=False, chain=False):
+                 use_graph=True, grow='never', meshes_only=False, deterministic=False, chain=False, viewport=None, zoom_limit=2.0):
         """grow: as OnlineStitcher -- 'never' counts the frames whose mesh left their stream's canvas (`clipped_frames`, per
-        stream), 'recapture' re-fixes the canvases of the streams that come near an edge and captures the graph again.
+        stream), 'recapture' re-fixes the canvases of the streams that come near an edge and captures the graph again, 'refit' (with
+        a viewport) re-fixes each stream's box on the device inside the push's launches.
+        viewport: (Hout, Wout), ONE for all streams: every stream's frames have that size, each on its own box (OnlineStitcher).
         meshes_only: no canvases, no render -- `push` returns the S streams' newly smoothed meshes (m1, m2) [S,k,7,9,2] (k = 7 on the
         7th push, then 1) or None; ThreeViewOnlineStitcher runs its two pair chains as such a batch of two and captures the graph
         itself (use_graph is ignored)."""
         _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only,
-                           canvases=max(1, int(streams)))
+                           canvases=max(1, int(streams)), viewport=viewport, zoom_limit=zoom_limit)
         self.deterministic = bool(deterministic)      # geometry-only kernel policy: S batched streams == S single streams, bit for bit
         # chain: the S pairs are the neighbours of a chain of S + 1 views (pair s = views s, s + 1: ThreeViewOnlineStitcher's two
         # chains).  The steady-state step then takes the S + 1 LR frames once (static['lrc'] [S+1,3,360,480]) and every inner view
@@ -1135,7 +1257,8 @@ class MultiOnlineStitcher(_Stitcher):
         if canvases is not None and len(canvases) != self.S:
             raise ValueError('one canvas per stream')
         self.single = [OnlineStitcher(nets, height, width, None if canvases is None else canvases[s], margin, warp_mode,
-                                      fusion_mode, use_graph=False, meshes_only=meshes_only, deterministic=deterministic)
+                                      fusion_mode, use_graph=False, meshes_only=meshes_only, deterministic=deterministic,
+                                      grow='refit' if grow == 'refit' else 'never', viewport=viewport, zoom_limit=zoom_limit)
                        for s in range(self.S)]                   # window fill; then the streams' canvases (watched and grown here)
 
     @property
@@ -1167,8 +1290,17 @@ class MultiOnlineStitcher(_Stitcher):
         if not self.meshes_only:
             st['bboxes'] = torch.stack([s.bbox for s in self.single], 0).contiguous()        # [S,4] the streams' fixed canvases
             # the streams' watcher rows (their first windows are counted) go on as rows of one [S,4] state (ops.canvas_watch)
-            self.watch.start(st['bboxes'].cpu(), (torch.cat([s.watch.wi for s in self.single], 0).contiguous(),
-                                                  torch.cat([s.watch.wf for s in self.single], 0).contiguous()))
+            rows = (torch.cat([s.watch.wi for s in self.single], 0).contiguous(),
+                    torch.cat([s.watch.wf for s in self.single], 0).contiguous())
+            if self.viewport is not None:         # the boxes are fitted already; grow='refit': the streams' fit states go on as rows too
+                fit = None
+                if self.grow == 'refit':
+                    fit = (torch.cat([s.watch.fit.epoch for s in self.single], 0).contiguous(),
+                           torch.cat([s.watch.fit.ext0 for s in self.single], 0).contiguous())
+                self.watch.start(self.watch.fit_boxes(st['bboxes'], fit_state=fit or (None, None)), rows)
+            else:
+                self.watch.start(st['bboxes'].cpu(), rows)
+            self._canvas_set = True
             self._alloc_outputs()
         for s in self.single:                     # the per-stream buffers and watchers are not needed any more (bbox / canvas stay)
             s.static = None
@@ -1272,7 +1404,7 @@ class MultiOnlineStitcher(_Stitcher):
         if self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE:
             watch = self.watch.args()
         else:
-            ops.canvas_watch(src, self.watch.wi, self.watch.wf, self.watch.guard)
+            ops.canvas_watch(src, self.watch.wi, self.watch.wf, self.watch.guard, fit=self.watch.fit_args())
         if defer and self.fusion_mode == 'LINEAR':        # equal or different canvas sizes: one ragged render, launched by the push
             self._deferred = (src, T, None)
             return
@@ -1280,7 +1412,8 @@ class MultiOnlineStitcher(_Stitcher):
             # all streams render onto canvases of ONE size (e.g. the caller fixed them): the S current frames are a clip
             hc, wc = self.single[0].hc, self.single[0].wc
             if self.fusion_mode == 'AVERAGE':
-                fp = ops.render_footprints(src, T, self.h, self.w, hc, wc, watch=watch) if pipeline.SKIP_OUTSIDE else None
+                fp = (ops.render_footprints(src, T, self.h, self.w, hc, wc, watch=watch, fit=self.watch.fit_args())
+                      if pipeline.SKIP_OUTSIDE else None)
                 if defer:
                     self._deferred = (src, T, fp)
                     return
@@ -1290,7 +1423,8 @@ class MultiOnlineStitcher(_Stitcher):
             return
         for s, one in enumerate(self.single):
             one._render_solved(None if defer else [hr1[s:s + 1], hr2[s:s + 1]], src[s], T[s], out=_DEFER if defer else out[s],
-                               watch=None if watch is None else self.watch.args(s))
+                               watch=None if watch is None else self.watch.args(s),
+                               fit=None if watch is None else self.watch.fit_args(s))
 
     def _deferred_splines(self):
         if self.static['out_all'] is not None or self.fusion_mode == 'LINEAR':
@@ -1369,14 +1503,17 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
         st = PipelinedMultiOnlineStitcher(nets, H, W, streams=8)
         for batch in source: per_stream = st.push(*batch)        # S lists: [] x 6, 7 frames, [] (one push of lag), then 1 frame each
         per_stream = st.flush()
-    Canvases are fixed after the first window (grow='never').  LINEAR fusion renders inside the graphs, stream by stream (no direct
-    LINEAR render: _TwoInFlight)."""
+    Canvases are fixed after the first window (grow='never') or, with a viewport, re-fixed on the device (grow='refit').  LINEAR
+    fusion renders inside the graphs, stream by stream (no direct LINEAR render: _TwoInFlight)."""
     _U8_STEADY = False       # push_u8: ingest_u8 -> push -> canvas_to_u8
 
     def __init__(self, nets, height, width, streams, canvases=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 deterministic=False):
+                 deterministic=False, grow='never', viewport=None, zoom_limit=2.0):
+        """grow: 'never', or 'refit' with a viewport (see MultiOnlineStitcher and _TwoInFlight)."""
+        self._check_grow(grow)
         MultiOnlineStitcher.__init__(self, nets, height, width, streams, canvases, margin, warp_mode, fusion_mode, use_graph=True,
-                                     grow='never', meshes_only=False, deterministic=deterministic)
+                                     grow=grow, meshes_only=False, deterministic=deterministic, viewport=viewport,
+                                     zoom_limit=zoom_limit)
         self._pipe_init()
 
     def _pipe_alloc(self):
@@ -1438,22 +1575,23 @@ class ThreeViewOnlineStitcher(_Stitcher):
         for frame in st.push(hr1, hr2, hr3, lr1, lr2, lr3): ...      # [], ..., 7 frames on the 7th push, then 1: [3,Hc,Wc] fp32
 
     Overflow of the fixed output canvas is watched as in OnlineStitcher (`clipped_frames`, `overflow_report()`); grow='recapture'
-    re-fixes the OUTPUT canvas (and captures the graph again) when a mesh comes within half the margin of its edge.
+    re-fixes the OUTPUT canvas (and captures the graph again) when a mesh comes within half the margin of its edge.  `viewport` and
+    grow='refit' as in OnlineStitcher, on the OUTPUT box only: the first canvas is a normalisation frame and stays as it is.
     `push_many` / `push_many_u8` take k consecutive triples per call (see OnlineStitcher.push_many)."""
 
     def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 use_graph=True, grow='never', deterministic=False):
+                 use_graph=True, grow='never', deterministic=False, viewport=None, zoom_limit=2.0):
         """deterministic: every push under the conv engine's geometry-only kernel policy (ops.deterministic; as OnlineStitcher's):
         push_many's frames then equal single pushes' bit for bit."""
         # the two pair chains as a batch of two streams over the CHAIN of three views: every launch serves both pairs, view 2's
         # trunk features are computed once
         self.chains = MultiOnlineStitcher(nets, height, width, streams=2, margin=margin, warp_mode=warp_mode, fusion_mode=fusion_mode,
                                           use_graph=False, meshes_only=True, deterministic=deterministic, chain=True)
-        _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow)
+        _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, viewport=viewport,
+                           zoom_limit=zoom_limit)
         self.deterministic = bool(deterministic)
         box = lambda b: None if b is None else torch.tensor(b, dtype=torch.float32, device=self.dev)
         self.bbox, self.first_canvas = box(canvas), box(first_canvas)
-        self.hc = self.wc = None
         self.nrigid = get_norm_mesh(get_rigid_mesh(1, height, width, device=self.dev), height, width).contiguous()
         self.ring_hr = []
 
@@ -1485,14 +1623,18 @@ class ThreeViewOnlineStitcher(_Stitcher):
         splines = (src [3,63,2], T [3,2,66]) from ops.three_view_splines: the steady-state push has them already, and the overflow
         watcher runs inside the footprint launch (or as a launch of its own when there is none)."""
         if splines is not None:
-            return self._render_solved(imgs, splines[0], splines[1], out, watch=self.watch.args())
+            return self._render_solved(imgs, splines[0], splines[1], out, watch=self.watch.args(), fit=self.watch.fit_args())
+        if self.watch.fit is not None:       # grow='refit': the watcher runs in a launch that carries the refit, behind the box' last reader
+            src = ops.stream_normalize_watch([m.contiguous() for m in meshes], 126, self.bbox, 0.0, 0.0)[0]
+            T = ops.tps_solve_shared(src, self.nrigid)
+            return self._render_solved(imgs, src, T, out, watch=self.watch.args(), fit=self.watch.fit_args())
         src = ops.stream_normalize_watch([m.contiguous() for m in meshes], 126, self.bbox, 0.0, 0.0,
                                          *self.watch.args())[0]                   # [3,63,2] on the output canvas, watcher updated
         return self._render_solved(imgs, src, ops.tps_solve_shared(src, self.nrigid), out)
 
     # ------------------------------------------------------------------ steady state
     def _state(self):
-        return [self.chains.static[k] for k in _STATE] + [self.watch.wi, self.watch.wf]
+        return [self.chains.static[k] for k in _STATE] + [self.watch.wi, self.watch.wf] + self.watch.fit_state()
 
     def _step_static(self):
         ch, hr = self.chains, self.static['hr']
@@ -1637,7 +1779,7 @@ class ThreeViewOnlineStitcher(_Stitcher):
                                                 self.nrigid, self.h, self.w, frames=k, frame_stride=WINDOW * e)
         self.last_composed = meshes
         guard, wi, wf = self.watch.args()
-        ops.canvas_watch_frames(src, wi, wf, guard)
+        ops.canvas_watch_frames(src, wi, wf, guard, fit=self.watch.fit_args())
         fp = None
         if self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE:
             fp = ops.render_footprints(src, T, self.h, self.w, self.hc, self.wc)
@@ -1647,13 +1789,17 @@ class ThreeViewOnlineStitcher(_Stitcher):
 class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
     """ThreeViewOnlineStitcher with TWO pushes in flight (round 6; opt-in; see _TwoInFlight): the three views' trunks and the two
     pairs' stage-1 heads of triple t + 1 run beside triple t's regressor heads, smoothing, composition and three-image render.  Frames
-    bit-identical to ThreeViewOnlineStitcher's, handed out one push late (`flush()` for the last); boxes fixed after the first window.
+    bit-identical to ThreeViewOnlineStitcher's, handed out one push late (`flush()` for the last); boxes fixed after the first window
+    (grow='never') or, with a viewport, the output box re-fixed on the device (grow='refit').
     LINEAR fusion renders inside the graphs (no direct LINEAR render: _TwoInFlight)."""
     _U8_STEADY = False       # push_u8: ingest_u8 -> push -> canvas_to_u8
 
-    def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE'):
+    def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
+                 grow='never', viewport=None, zoom_limit=2.0):
+        """grow: 'never', or 'refit' with a viewport (see ThreeViewOnlineStitcher and _TwoInFlight)."""
+        self._check_grow(grow)
         ThreeViewOnlineStitcher.__init__(self, nets, height, width, canvas, first_canvas, margin, warp_mode, fusion_mode,
-                                         use_graph=True, grow='never')
+                                         use_graph=True, grow=grow, viewport=viewport, zoom_limit=zoom_limit)
         self._pipe_init()
 
     def push_many(self, *frames):

@@ -1,6 +1,7 @@
 """Thin tensor-level wrappers over the C ABI: allocate outputs with torch, launch on the current stream of the
 device that owns the tensors, return device tensors.  These wrappers do no arithmetic of their own (the few
 mesh-sized torch expressions of the path live in pipeline.py and are named there)."""
+import collections
 import os
 import threading
 
@@ -829,16 +830,22 @@ def tps_warp(U, source, T, hc, wc, mode='NORMAL', with_mask=False):
     return out
 
 
-def render_footprints(source, T, h, w, hc, wc, watch=None):
+def render_footprints(source, T, h, w, hc, wc, watch=None, fit=None):
     """source [n,V,63,2], T [n,V,2,66], images h x w -> footprints [n, ss_render_footprint_floats] of every (frame, view) on
     the hc x wc canvas (tile-corner sampling coordinates, mesh hulls, tile order), two small launches for the whole clip.
     watch = (guard, watch_i [n,4], watch_f [n,4]): the streaming overflow watcher (ops.canvas_watch on `source`, frame = stream) inside
-    the same launches."""
+    the same launches.  fit (a CanvasFit over the same n streams, with watch; its viewport is hc x wc): the watcher's wave goes on with
+    the device-side refit of the streams' boxes (ss_render_footprints_watch_fit)."""
     n, v = source.shape[0], source.shape[1]
     per = int(H.lib().ss_render_footprint_floats(v, hc, wc))
     fp = torch.empty((n, per), device=source.device, dtype=torch.float32)
     if watch is None:
         H.call('ss_render_footprints', H.dptr(_f(source)), H.dptr(_f(T)), H.dptr(fp), n, v, h, w, hc, wc, H.stream())
+    elif fit is not None:
+        guard, wi, wf = watch
+        assert tuple(wi.shape) == (n, 4) and tuple(wf.shape) == (n, 4) and (fit.hout, fit.wout) == (hc, wc)
+        H.call('ss_render_footprints_watch_fit', H.dptr(_f(source)), H.dptr(_f(T)), H.dptr(fp), n, v, h, w, hc, wc, float(guard),
+               H.dptr(wi, dtype=torch.int32), H.dptr(wf), *_fit_state(fit, n), float(fit.margin), float(fit.zoom_limit), H.stream())
     else:
         guard, wi, wf = watch
         assert tuple(wi.shape) == (n, 4) and tuple(wf.shape) == (n, 4)
@@ -1095,18 +1102,56 @@ def canvas_watch_state(streams, device):
     return wi, wf
 
 
-def canvas_watch(src, watch_i, watch_f, guard):
-    """src [S,V,63,2] canvas-normalised control points of one push -> updates the streams' overflow state (ss_canvas_watch)."""
+CanvasFit = collections.namedtuple('CanvasFit', 'box epoch ext0 margin zoom_limit hout wout')
+CanvasFit.__doc__ = """State and policy of the device-side canvas refit (ss_canvas_watch_fit): box [S,4] fp32 (wmin, wmax, hmin, hmax in HR px),
+epoch [S] int32, ext0 [S,2] fp32 (the extents the canvases were set with) -- device tensors the launches rewrite in place -- and the
+margin, the zoom limit and the viewport (hout, wout)."""
+
+
+def canvas_fit_state(n, device):
+    """Fresh (box [n,4] fp32, epoch [n] int32, ext0 [n,2] fp32) of the device-side refit, all zero: set the boxes, then
+    box_fit_aspect(box, hout, wout, ext0)."""
+    return (torch.zeros((n, 4), dtype=torch.float32, device=device), torch.zeros((n,), dtype=torch.int32, device=device),
+            torch.zeros((n, 2), dtype=torch.float32, device=device))
+
+
+def box_fit_aspect(boxes, hout, wout, ext0=None):
+    """boxes [n,4] (or [4]) letterboxed in place about their centres to the viewport's aspect wout : hout (ss_box_fit_aspect: the
+    aspect step of the refit alone; a box only ever expands); ext0 [n,2]: receives the fitted (width, height)."""
+    n = boxes.numel() // 4
+    assert boxes.is_contiguous() and boxes.numel() == 4 * n and (ext0 is None or (ext0.is_contiguous() and ext0.numel() == 2 * n))
+    H.call('ss_box_fit_aspect', H.dptr(boxes), H.dptr(ext0, True), n, int(hout), int(wout), H.stream())
+    return boxes
+
+
+def _fit_state(fit, s):
+    """The three state pointers of a CanvasFit over s streams."""
+    assert fit.box.numel() == 4 * s and fit.epoch.numel() == s and fit.ext0.numel() == 2 * s
+    return H.dptr(fit.box), H.dptr(fit.epoch, dtype=torch.int32), H.dptr(fit.ext0)
+
+
+def canvas_watch(src, watch_i, watch_f, guard, fit=None):
+    """src [S,V,63,2] canvas-normalised control points of one push -> updates the streams' overflow state (ss_canvas_watch).
+    fit (a CanvasFit over the S streams): the same wave goes on with the device-side refit of the streams' boxes (ss_canvas_watch_fit)."""
     s, v = src.shape[0], src.shape[1]
     assert src.is_contiguous() and tuple(watch_i.shape) == (s, 4) and tuple(watch_f.shape) == (s, 4)
+    if fit is not None:
+        H.call('ss_canvas_watch_fit', H.dptr(src), s, v, float(guard), H.dptr(watch_i, dtype=torch.int32), H.dptr(watch_f),
+               *_fit_state(fit, s), float(fit.margin), float(fit.zoom_limit), int(fit.hout), int(fit.wout), H.stream())
+        return
     H.call('ss_canvas_watch', H.dptr(src), s, v, float(guard), H.dptr(watch_i, dtype=torch.int32), H.dptr(watch_f), H.stream())
 
 
-def canvas_watch_frames(src, watch_i, watch_f, guard):
+def canvas_watch_frames(src, watch_i, watch_f, guard, fit=None):
     """src [k,V,63,2] canvas-normalised control points of k consecutive frames of ONE stream -> its watcher row watch_i [1,4] /
-    watch_f [1,4] updated frame by frame (ss_canvas_watch_frames; equal to k canvas_watch calls)."""
+    watch_f [1,4] updated frame by frame (ss_canvas_watch_frames; equal to k canvas_watch calls).  fit (a CanvasFit of that one
+    stream): ONE refit of its box behind the batch's last frame (ss_canvas_watch_frames_fit)."""
     k, v = src.shape[0], src.shape[1]
     assert src.is_contiguous() and tuple(watch_i.shape) == (1, 4) and tuple(watch_f.shape) == (1, 4)
+    if fit is not None:
+        H.call('ss_canvas_watch_frames_fit', H.dptr(src), k, v, float(guard), H.dptr(watch_i, dtype=torch.int32), H.dptr(watch_f),
+               *_fit_state(fit, 1), float(fit.margin), float(fit.zoom_limit), int(fit.hout), int(fit.wout), H.stream())
+        return
     H.call('ss_canvas_watch_frames', H.dptr(src), k, v, float(guard), H.dptr(watch_i, dtype=torch.int32), H.dptr(watch_f), H.stream())
 
 

@@ -109,10 +109,11 @@ def _demangled(by_symbol):
 
 def digests(lib_path, mask_kernarg_offsets=False):
     """-> {demangled kernel name: sha256 hex digest of its instruction stream}: mnemonics and operands in order, without addresses,
-    encodings and comments (branch operands are relative, so a kernel's digest does not depend on where it lies).
+    encodings, comments and the fill behind its last instruction (branch operands are relative, so a kernel's digest does not depend
+    on where it lies, nor on whether it is a template: those get sections of their own, zero-filled instead of s_nop-filled).
     mask_kernarg_offsets: the immediate offset of every scalar load whose base is the kernel-argument pointer (the user SGPR pair
     the kernel descriptor assigns to it) reads `KARG`."""
-    res = {}
+    res, pad = {}, {}
     with tempfile.TemporaryDirectory() as d:
         for i, elf in enumerate(code_objects(lib_path)):
             f = os.path.join(d, 'co%d.elf' % i)
@@ -140,10 +141,20 @@ def digests(lib_path, mask_kernarg_offsets=False):
                     if sym is not None:
                         res[sym] = hashlib.sha256()
                         base = 's[%d:%d]' % (karg[sym], karg[sym] + 1)
+                        pad[sym] = []
                     continue
                 ins = ' '.join(line.split('//')[0].split())
                 if sym is None or not ins:
                     continue
+                # the fill between a kernel's last instruction and the next symbol (s_nop rows from the assembler, or zeros that
+                # objdump prints as `...`, whichever the kernel's section got) says where the kernel lies, not what it does: held
+                # back, and hashed only if an instruction follows
+                if ins in ('s_nop 0', '...'):
+                    pad[sym].append(ins)
+                    continue
+                for held in pad[sym]:
+                    res[sym].update((held + '\n').encode())
+                pad[sym] = []
                 if mask_kernarg_offsets:
                     m = re.match(r'^(s_load_dword\w* \S+ ' + re.escape(base) + r',) \S+(.*)$', ins)
                     if m:
