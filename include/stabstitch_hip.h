@@ -296,6 +296,16 @@ SS_API int ss_render_average(const float* const* imgs, const float* source, cons
 SS_API int ss_render_average_u8(const unsigned char* const* frames, const float* source, const float* T,
                          const float* footprint, long long footprint_floats, unsigned char* out, int views, int h, int w,
                          int hc, int wc, int mode, void* stream);
+/* ss_render_average_u8 with decoded NV12 views (the NV12 frame format below): y, uv, pitch = HOST arrays of `views` entries (Y
+ * plane, UV plane, bytes per row of both).  Every tap's B, G, R are the NV12 -> BGR statement at the tap's integer pixel, so
+ * out_format 0 writes the uint8 frame [hc][wc][3] that ss_render_average_u8 writes from the converted frames (out_uv, out_pitch
+ * unused), and out_format 1 writes that frame as NV12 -- out = Y plane, out_uv = UV plane, out_pitch bytes per row of both (even,
+ * >= wc; hc, wc even; out_uv 2-byte aligned) -- byte for byte ss_bgr_to_nv12 of it, without the BGR frame; a tile no view reaches
+ * is black (Y 16, U 128, V 128).  mode: SS_WARP_NORMAL | SS_WARP_FAST. */
+SS_API int ss_render_average_nv12(const unsigned char* const* y, const unsigned char* const* uv, const int* pitch,
+                                  const float* source, const float* T, const float* footprint, long long footprint_floats,
+                                  unsigned char* out, unsigned char* out_uv, int out_pitch, int out_format, int views, int h,
+                                  int w, int hc, int wc, int mode, void* stream);
 /* a whole clip in ONE launch (the frame loop of get_stable_sqe, test_online_tra.py:127-152): views_base = host array of
  * `views` device pointers to [frames][3][h][w] fp32; source [frames][views][63][2]; T [frames][views][2][66]; footprint
  * [frames][footprint_floats] or NULL; out [frames][3][hc][wc].  Bit-identical to `frames` calls of ss_render_average. */
@@ -367,6 +377,13 @@ SS_API int ss_render_linear_frames(const float* const* views_base, const float* 
 SS_API int ss_render_linear_frames_u8(const unsigned char* const* views_base, const float* source, const float* T,
                                unsigned char* const* out, int frames, int views, int h, int w, const int* hc,
                                const int* wc, int mode, float* ws, void* stream);
+/* ss_render_linear_frames_u8 with decoded NV12 views: y, uv, pitch, frame_stride = HOST arrays of `views` entries, frame f of view
+ * k at y[k] / uv[k] + f * frame_stride[k] bytes.  out[f] = [hc[f]][wc[f]][3] uint8, byte for byte ss_render_linear_frames_u8 on the
+ * converted frames (the blend walks a rolling row window: NV12 frames out go through ss_bgr_to_nv12). */
+SS_API int ss_render_linear_frames_nv12(const unsigned char* const* y, const unsigned char* const* uv, const int* pitch,
+                                        const long long* frame_stride, const float* source, const float* T,
+                                        unsigned char* const* out, int frames, int views, int h, int w, const int* hc,
+                                        const int* wc, int mode, float* ws, void* stream);
 
 /* ---- K14: canvas bounding box and mesh normalisation (test_online_tra.py:103-136) ------------
  * mesh: n_points (x,y) pairs at LR scale (480x360); each is scaled to the HR frame as the reference
@@ -543,6 +560,24 @@ SS_API int ss_mask_union(const float* a, const float* b, float* out, long long n
 SS_API int ss_ingest_u8(const unsigned char* frames, float* hr, float* lr, int n, int h, int w, int lr_h, int lr_w,
                  void* stream);
 SS_API int ss_canvas_to_u8(const float* canvas, unsigned char* out, int n, int h, int w, void* stream);
+/* NV12, the frame format of hardware video decoders and encoders, next to packed BGR: a full-resolution Y plane and a
+ * half-resolution plane of interleaved (U, V) bytes, both with the same pitch (bytes per row, >= w: decoder surfaces are padded).
+ * BT.601 limited range in 20-bit fixed point, >> arithmetic, sat8 = clamp to 0..255:
+ *   NV12 -> BGR at (y, x), U and V from the pair at (y >> 1, x >> 1), no chroma interpolation:
+ *     c = max(0, Y - 16) * 1220542, u = U - 128, v = V - 128
+ *     B = sat8((c + 2116026 u + 2^19) >> 20), G = sat8((c - 409993 u - 852492 v + 2^19) >> 20), R = sat8((c + 1673527 v + 2^19) >> 20)
+ *   BGR -> NV12: Y = (269484 R + 528482 G + 102760 B + (16 << 20) + 2^19) >> 20 per pixel; per 2 x 2 block, of the rounded means
+ *     (sum + 2) >> 2 of its B, G, R bytes: U = (-155188 R - 305135 G + 460324 B + (128 << 20) + 2^19) >> 20,
+ *     V = (460324 R - 385875 G - 74448 B + (128 << 20) + 2^19) >> 20
+ * (the first set is OpenCV's COLOR_YUV2BGR_NV12 as far as known: UNPINNED against cv2, like ss_ingest_u8's resize).
+ * Every NV12 entry point returns SS_ERR_ARG for odd h or w, an odd pitch, pitch < w, or a UV pointer that is not 2-byte aligned.
+ * ss_ingest_nv12: n frames (frame f at y / uv + f * frame_stride bytes) -> hr and / or lr as ss_ingest_u8 writes them from the
+ * converted frames, byte-identical, in all three resize modes.  n <= 65535.
+ * ss_bgr_to_nv12: uint8 [n][h][w][3] (B, G, R) -> n NV12 frames (frame f at y / uv + f * frame_stride). */
+SS_API int ss_ingest_nv12(const unsigned char* y, const unsigned char* uv, int pitch, long long frame_stride, float* hr, float* lr,
+                          int n, int h, int w, int lr_h, int lr_w, void* stream);
+SS_API int ss_bgr_to_nv12(const unsigned char* bgr, unsigned char* y, unsigned char* uv, int pitch, long long frame_stride, int n,
+                          int h, int w, void* stream);
 
 /* ---- metric harness (test_metric_ssd.py:444-482, 513-527) -------------------------------------
  * w1, w2: [frames][4][h][w] = 3 colour planes (0..255) + validity-mask plane, as ss_tps_warp_mask_nchw

@@ -76,8 +76,12 @@ SIGNATURES = {
     'ss_mask_union': (c_i, [c_fp, c_fp, c_fp, c_ll, c_st]),
     'ss_ingest_u8': (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
     'ss_canvas_to_u8': (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_st]),
+    'ss_ingest_nv12': (c_i, [c_fp, c_fp, c_i, c_ll, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
+    'ss_bgr_to_nv12': (c_i, [c_fp, c_fp, c_fp, c_i, c_ll, c_i, c_i, c_i, c_st]),
     'ss_render_average': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_ll, c_fp] + [c_i] * 6 + [c_st]),
     'ss_render_average_u8': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_ll, c_fp] + [c_i] * 6 + [c_st]),
+    'ss_render_average_nv12': (c_i, [ctypes.POINTER(c_fp), ctypes.POINTER(c_fp), ctypes.POINTER(c_i), c_fp, c_fp, c_fp, c_ll, c_fp, c_fp] +
+                               [c_i] * 8 + [c_st]),
     'ss_render_average_clip': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_ll, c_fp] + [c_i] * 7 + [c_st]),
     'ss_render_average_clip_u8': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_ll, c_fp] + [c_i] * 7 + [c_st]),
     'ss_render_footprint_floats': (c_ll, [c_i, c_i, c_i]),
@@ -95,6 +99,8 @@ SIGNATURES = {
                                 [ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_i, c_fp, c_st]),
     'ss_render_linear_frames_u8': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, ctypes.POINTER(c_fp)] + [c_i] * 4 +
                                    [ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_i, c_fp, c_st]),
+    'ss_render_linear_frames_nv12': (c_i, [ctypes.POINTER(c_fp), ctypes.POINTER(c_fp), ctypes.POINTER(c_i), ctypes.POINTER(c_ll), c_fp, c_fp,
+                                           ctypes.POINTER(c_fp)] + [c_i] * 4 + [ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_i, c_fp, c_st]),
     'ss_mesh_bbox': (c_i, [c_fp, c_i, c_f, c_f, c_fp, c_i, c_st]),
     'ss_mesh_normalize': (c_i, [c_fp, c_fp, c_fp, c_i, c_f, c_f, c_st]),
     'ss_canvas_watch': (c_i, [c_fp, c_i, c_i, c_f, c_fp, c_fp, c_st]),

@@ -1,6 +1,7 @@
 // Frame I/O either side of the hot path: uint8 ingest with OpenCV-exact LR generation,
 // and the fp32 -> uint8 video-frame cast.  HBM-bound byte work: one pass over the uint8 frame per output.
 #include "common.h"
+#include "nv12.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // HR planes: uint8 [n][h][w][3] -> fp32 [n][3][h][w] (test_online_tra.py:254-256).  One thread = 4 pixels
@@ -139,6 +140,98 @@ extern "C" int ss_ingest_u8(const unsigned char* frames, float* hr, float* lr, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The same two outputs from decoded NV12 frames (Y plane + interleaved UV plane, one pitch): every pixel the resize or the
+// plane split reads is first converted to its B, G, R bytes (nv12.h) -- byte-identical to converting the frame and calling
+// ss_ingest_u8, without the BGR frame.  Overloads of the kernels whose role they extend; frame = blockIdx.z.
+__global__ __launch_bounds__(256) void ingest_hr1_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp, int pitch,
+                                                         long long fs, float* __restrict__ out, int h, int w) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const long long img = blockIdx.z;
+    if (x >= w || y >= h) return;
+    int c[3];
+    nv12_pixel(yp + img * fs, uvp + img * fs, pitch, y, x, c);
+    const long long plane = (long long)h * w;
+    float* o = out + img * 3 * plane + (long long)y * w + x;
+    o[0] = (float)c[0];
+    o[plane] = (float)c[1];
+    o[2 * plane] = (float)c[2];
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void ingest_lr_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ uvp, int pitch,
+                                                        long long fs, float* __restrict__ out, int h, int w, int lr_h, int lr_w,
+                                                        double scale_x, double scale_y) {
+    int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const long long img = blockIdx.z;
+    if (x >= lr_w || y >= lr_h) return;
+    yp += img * fs;
+    uvp += img * fs;
+    int v[3];
+    if (MODE == 2) {
+        nv12_pixel(yp, uvp, pitch, y, x, v);
+    } else if (MODE == 1) {
+        int a[3], b[3], c[3], d[3];
+        nv12_pixel(yp, uvp, pitch, 2 * y, 2 * x, a);
+        nv12_pixel(yp, uvp, pitch, 2 * y, 2 * x + 1, b);
+        nv12_pixel(yp, uvp, pitch, 2 * y + 1, 2 * x, c);
+        nv12_pixel(yp, uvp, pitch, 2 * y + 1, 2 * x + 1, d);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = (a[k] + b[k] + c[k] + d[k] + 2) >> 2;
+    } else {
+        LinTap tx = lin_tap(x, scale_x, w, true);
+        LinTap ty = lin_tap(y, scale_y, h, false);
+        int x0 = tx.s, x1 = min(tx.s + 1, w - 1);
+        int r0 = min(max(ty.s, 0), h - 1), r1 = min(max(ty.s + 1, 0), h - 1);
+        int a[3], b[3], c[3], d[3];
+        nv12_pixel(yp, uvp, pitch, r0, x0, a);
+        nv12_pixel(yp, uvp, pitch, r0, x1, b);
+        nv12_pixel(yp, uvp, pitch, r1, x0, c);
+        nv12_pixel(yp, uvp, pitch, r1, x1, d);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            int s0 = a[k] * tx.w0 + b[k] * tx.w1;
+            int s1 = c[k] * tx.w0 + d[k] * tx.w1;
+            int r = (((ty.w0 * (s0 >> 4)) >> 16) + ((ty.w1 * (s1 >> 4)) >> 16) + 2) >> 2;
+            v[k] = min(max(r, 0), 255);
+        }
+    }
+    long long plane = (long long)lr_h * lr_w;
+    float* o = out + img * 3 * plane + (long long)y * lr_w + x;
+    o[0] = lr_norm(v[0]);
+    o[plane] = lr_norm(v[1]);
+    o[2 * plane] = lr_norm(v[2]);
+}
+
+// what every NV12 entry point asks of a surface: even size, an even pitch >= w, a 2-byte aligned UV plane
+static inline bool nv12_surface_ok(const void* y, const void* uv, int pitch, int h, int w) {
+    return y && uv && h >= 2 && w >= 2 && !(h & 1) && !(w & 1) && !(pitch & 1) && pitch >= w && !(((uintptr_t)uv) & 1);
+}
+
+extern "C" int ss_ingest_nv12(const unsigned char* y, const unsigned char* uv, int pitch, long long frame_stride, float* hr,
+                              float* lr, int n, int h, int w, int lr_h, int lr_w, void* stream) {
+    if (!nv12_surface_ok(y, uv, pitch, h, w) || (!hr && !lr) || n < 0 || n > 65535 || frame_stride < 0 || (frame_stride & 1))
+        return SS_ERR_ARG;
+    if (lr && (lr_h < 1 || lr_w < 1)) return SS_ERR_ARG;
+    if (ss_cdiv(h, 4) > 65535 || (lr && ss_cdiv(lr_h, 4) > 65535)) return SS_ERR_ARG;
+    if (n == 0) return SS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (hr) ingest_hr1_kernel<<<dim3(ss_cdiv(w, 64), ss_cdiv(h, 4), n), dim3(256), 0, st>>>(y, uv, pitch, frame_stride, hr, h, w);
+    if (lr) {
+        dim3 grid(ss_cdiv(lr_w, 64), ss_cdiv(lr_h, 4), n);
+        double scale_x = 1.0 / ((double)lr_w / (double)w), scale_y = 1.0 / ((double)lr_h / (double)h);
+        if (lr_w == w && lr_h == h)
+            ingest_lr_kernel<2><<<grid, dim3(256), 0, st>>>(y, uv, pitch, frame_stride, lr, h, w, lr_h, lr_w, scale_x, scale_y);
+        else if (w == 2 * lr_w && h == 2 * lr_h)
+            ingest_lr_kernel<1><<<grid, dim3(256), 0, st>>>(y, uv, pitch, frame_stride, lr, h, w, lr_h, lr_w, scale_x, scale_y);
+        else
+            ingest_lr_kernel<0><<<grid, dim3(256), 0, st>>>(y, uv, pitch, frame_stride, lr, h, w, lr_h, lr_w, scale_x, scale_y);
+    }
+    return ss_launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // `.astype(np.uint8)` of the fused canvas (test_online_tra.py:151, :413): fp32 [n][3][h][w] -> uint8 [n][h][w][3]
 __device__ __forceinline__ uint32_t to_u8(float v) {
     if (!(fabsf(v) < 2147483648.f)) return 0u;     // x86 cvttss2si "integer indefinite" 0x80000000 -> low byte 0
@@ -185,5 +278,40 @@ extern "C" int ss_canvas_to_u8(const float* canvas, unsigned char* out, int n, i
         hipLaunchKernelGGL(canvas_u8x1_kernel, dim3(ss_cdiv(pixels, 256)), dim3(256), 0, st, canvas, out, pixels,
                            h * w);
     }
+    return ss_launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The video frame as an encoder takes it: uint8 [n][h][w][3] (B, G, R) -> NV12 with a pitch (nv12.h).  One thread = one
+// 2 x 2 block: four Y bytes and the chroma pair of the block's rounded mean colour, the pair as one 16-bit store.
+__global__ __launch_bounds__(256) void canvas_u8x1_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ yp,
+                                                          uint8_t* __restrict__ uvp, int pitch, long long fs, int h, int w) {
+    const int bx = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int by = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const long long img = blockIdx.z;
+    if (2 * bx >= w || 2 * by >= h) return;
+    const uint8_t* p0 = in + ((img * h + 2 * by) * w + 2 * bx) * 3;
+    const uint8_t* p1 = p0 + (long long)w * 3;
+    uint8_t* y0 = yp + img * fs + (long long)(2 * by) * pitch + 2 * bx;
+    int s[3] = {0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int b0 = p0[3 * k], g0 = p0[3 * k + 1], r0 = p0[3 * k + 2];
+        const int b1 = p1[3 * k], g1 = p1[3 * k + 1], r1 = p1[3 * k + 2];
+        y0[k] = bgr_to_y(b0, g0, r0);
+        y0[pitch + k] = bgr_to_y(b1, g1, r1);
+        s[0] += b0 + b1; s[1] += g0 + g1; s[2] += r0 + r1;
+    }
+    *reinterpret_cast<unsigned short*>(uvp + img * fs + (long long)by * pitch + 2 * bx) = bgr4_to_uv(s[0], s[1], s[2]);
+}
+
+extern "C" int ss_bgr_to_nv12(const unsigned char* bgr, unsigned char* y, unsigned char* uv, int pitch, long long frame_stride,
+                              int n, int h, int w, void* stream) {
+    if (!bgr || !nv12_surface_ok(y, uv, pitch, h, w) || n < 0 || n > 65535 || frame_stride < 0 || (frame_stride & 1) ||
+        ss_cdiv(h, 8) > 65535)
+        return SS_ERR_ARG;
+    if (n == 0) return SS_OK;
+    canvas_u8x1_kernel<<<dim3(ss_cdiv(w / 2, 64), ss_cdiv(h / 2, 4), n), dim3(256), 0, (hipStream_t)stream>>>(bgr, y, uv, pitch,
+                                                                                                          frame_stride, h, w);
     return ss_launch_status();
 }

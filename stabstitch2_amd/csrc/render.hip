@@ -7,8 +7,11 @@
 // bilinear taps are gathered straight from the planar source frames, and for the AVERAGE mode the
 // two (three) views are fused before the single store.  HBM traffic = source frames once (L2 absorbs
 // the 4-tap overlap) + the canvas once.
+#include <type_traits>
+
 #include "common.h"
 #include "device_math.h"
+#include "nv12.h"
 
 // grid_sample(bilinear, zeros, align_corners=True) taps: x = (xn+1)/2*(W-1), out-of-range taps -> 0
 __device__ __forceinline__ float sample_fast(const float* __restrict__ pl, float xn, float yn, int W, int H) {
@@ -470,6 +473,44 @@ __device__ __forceinline__ void sample3_u8(const unsigned char* __restrict__ in,
         }
     }
 }
+// the same samples from a decoded NV12 frame: every tap's B, G, R are nv12_to_bgr of the tap's Y byte and of the chroma pair of
+// its 2 x 2 block (nv12.h), so the values equal those of sample3_u8 on the converted frame bit for bit
+__device__ __forceinline__ void sample3_nv12(const unsigned char* __restrict__ yp, const unsigned char* __restrict__ uvp, int pitch,
+                                             float xn, float yn, int w, int h, int mode, float (&v)[3]) {
+    int a[3] = {0, 0, 0}, b[3] = {0, 0, 0}, c[3] = {0, 0, 0}, d[3] = {0, 0, 0};
+    if (mode == SS_WARP_NORMAL) {
+        SsTaps t = taps_normal(xn, yn, w, h);
+        nv12_pixel(yp, uvp, pitch, t.y0, t.x0, a);
+        nv12_pixel(yp, uvp, pitch, t.y1, t.x0, b);
+        nv12_pixel(yp, uvp, pitch, t.y0, t.x1, c);
+        nv12_pixel(yp, uvp, pitch, t.y1, t.x1, d);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) v[ch] = blend4(t, (float)a[ch], (float)b[ch], (float)c[ch], (float)d[ch]);
+    } else {
+        float x = ((xn + 1.f) / 2.f) * (float)(w - 1);
+        float y = ((yn + 1.f) / 2.f) * (float)(h - 1);
+        float xf = fminf(fmaxf(floorf(x), -4.f), (float)w + 4.f);
+        float yf = fminf(fmaxf(floorf(y), -4.f), (float)h + 4.f);
+        int x0 = (int)xf, y0 = (int)yf, x1 = x0 + 1, y1 = y0 + 1;
+        float w00 = (xf + 1.f - x) * (yf + 1.f - y), w01 = (x - xf) * (yf + 1.f - y);
+        float w10 = (xf + 1.f - x) * (y - yf), w11 = (x - xf) * (y - yf);
+        bool vx0 = (unsigned)x0 < (unsigned)w, vx1 = (unsigned)x1 < (unsigned)w;
+        bool vy0 = (unsigned)y0 < (unsigned)h, vy1 = (unsigned)y1 < (unsigned)h;
+        if (vx0 && vy0) nv12_pixel(yp, uvp, pitch, y0, x0, a);
+        if (vx1 && vy0) nv12_pixel(yp, uvp, pitch, y0, x1, b);
+        if (vx0 && vy1) nv12_pixel(yp, uvp, pitch, y1, x0, c);
+        if (vx1 && vy1) nv12_pixel(yp, uvp, pitch, y1, x1, d);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {            // sample_fast, term by term
+            float r = 0.f;
+            if (vx0 && vy0) r += (float)a[ch] * w00;
+            if (vx1 && vy0) r += (float)b[ch] * w01;
+            if (vx0 && vy1) r += (float)c[ch] * w10;
+            if (vx1 && vy1) r += (float)d[ch] * w11;
+            v[ch] = r;
+        }
+    }
+}
 __device__ __forceinline__ unsigned char render_to_u8(float v) {          // `.astype(np.uint8)` (frameio.hip to_u8)
     if (!(fabsf(v) < 2147483648.f)) return 0;
     return (unsigned char)((unsigned)((int)v) & 255u);
@@ -645,6 +686,139 @@ extern "C" int ss_render_average_u8(const unsigned char* const* frames, const fl
                                     int w, int hc, int wc, int mode, void* stream) {
     return render_average_launch(reinterpret_cast<const void* const*>(frames), source, T, footprint, footprint_floats, out, 1,
                                  0, 0, views, h, w, hc, wc, mode, stream, true);
+}
+
+// The fused render from decoded NV12 frames (sample3_nv12) to the uint8 video frame, packed B, G, R (NV12OUT = false: out8 =
+// [hc][wc][3]) or NV12 (NV12OUT = true: out8 = the Y plane, out_uv the interleaved UV plane, out_pitch bytes per row of both; hc and
+// wc even).  Per pixel the arithmetic of render_average_kernel<VIEWS, true>: the spline of a pixel does not depend on which wave
+// evaluates it, so here wave w owns rows 2 w and 2 w + 1 of the tile -- a lane holds both rows of its column, its horizontal
+// neighbour is one lane away, and the chroma pair of a 2 x 2 block (tiles are 64 x 8 and even-aligned: a block never straddles
+// two) is formed in registers from the bytes the BGR frame would hold.  A tile no view reaches is black: Y 16, U 128, V 128.
+template <int VIEWS, bool NV12OUT>
+__global__ __launch_bounds__(256) void render_average_kernel(Nv12Views nv, const float* __restrict__ source,
+                                                             const float* __restrict__ T, const float* __restrict__ fp,
+                                                             unsigned char* __restrict__ out8, unsigned char* __restrict__ out_uv,
+                                                             int out_pitch, int h, int w, int hc, int wc, int mode, long long out_fs,
+                                                             long long fp_fs) {
+    {
+        const long long frame = blockIdx.y;
+        source += frame * (VIEWS * SS_NV * 2);
+        T += frame * (VIEWS * 2 * SS_NT);
+        if (fp) fp += frame * fp_fs;
+        out8 += frame * out_fs;
+        if (NV12OUT) out_uv += frame * out_fs;
+#pragma unroll
+        for (int k = 0; k < VIEWS; ++k) { nv.y[k] += frame * nv.fs[k]; nv.uv[k] += frame * nv.fs[k]; }
+    }
+    const int lx = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int ny = (hc + 7) / 8 + 1, nx = 2 * ((wc + 63) / 64) + 1, nbx = (nx - 1) / 2;
+    int tbx, tby;
+    unsigned mask;
+    if (fp) {                                       // tile and its view set from the frame's order table (longest first)
+        const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)render_tile_entry(fp, VIEWS, ny, nx, blockIdx.x));
+        tbx = (int)(e & 0xFFFu); tby = (int)((e >> 12) & 0xFFFu); mask = e >> 24;
+    } else {
+        tby = blockIdx.x / nbx; tbx = blockIdx.x - tby * nbx; mask = (1u << VIEWS) - 1u;
+    }
+    const int x = tbx * 64 + lx;
+    const int ya = tby * 8 + 2 * wv, yb = ya + 1;
+    if (tbx * 64 >= wc || ya >= hc) return;       // (whole waves only: the lanes past the canvas edge still help build the table)
+    const bool xin = x < wc, rowb = yb < hc;
+    unsigned char ba[3] = {0, 0, 0}, bb[3] = {0, 0, 0};       // the video frame's B, G, R bytes at (x, ya) and (x, yb)
+    if (mask != 0u) {
+        const float gx = linspace_at(-1.f, 1.f, wc, min(x, wc - 1));
+        __shared__ ss_f2 dytab[4][VIEWS][64];
+        const float gya = linspace_at(-1.f, 1.f, hc, ya), gyb = linspace_at(-1.f, 1.f, hc, min(yb, hc - 1));
+#pragma unroll
+        for (int k = 0; k < VIEWS; ++k)
+            if (mask & (1u << k)) tps_rows_table(source + k * SS_NV * 2, gya, gyb, lx, dytab[wv][k]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // same wave reads it back: ordering only, no barrier
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        float va[VIEWS][3], vb[VIEWS][3];
+#pragma unroll
+        for (int k = 0; k < VIEWS; ++k) {
+            if (mask & (1u << k)) {
+                ss_f2 px, py;
+                tps_eval_rows(source + k * SS_NV * 2, T + k * 2 * SS_NT, dytab[wv][k], gx, gya, gyb, px, py);
+                sample3_nv12(nv.y[k], nv.uv[k], nv.pitch[k], px.x, py.x, w, h, mode, va[k]);
+                sample3_nv12(nv.y[k], nv.uv[k], nv.pitch[k], px.y, py.y, w, h, mode, vb[k]);
+            } else {
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) { va[k][ch] = 0.f; vb[k][ch] = 0.f; }
+            }
+        }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            // the chained fusion in the reference's order ((1 (+) 2) (+) 3), zeros in the places of views that do not reach
+            float fa = avg_fuse(va[0][ch], va[1][ch]), fb = avg_fuse(vb[0][ch], vb[1][ch]);
+            if (VIEWS == 3) { fa = avg_fuse(fa, va[2][ch]); fb = avg_fuse(fb, vb[2][ch]); }
+            ba[ch] = render_to_u8(fa);
+            bb[ch] = render_to_u8(fb);
+        }
+    }
+    if (!NV12OUT) {
+        if (!xin) return;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            out8[((long long)ya * wc + x) * 3 + ch] = ba[ch];
+            if (rowb) out8[((long long)yb * wc + x) * 3 + ch] = bb[ch];
+        }
+    } else {
+        // (hc and wc are even: rowb holds, and the two lanes of a block are inside the canvas together)
+        int s[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const int own = (int)ba[ch] + (int)bb[ch];
+            s[ch] = own + __shfl_xor(own, 1, 64);
+        }
+        if (!xin) return;
+        out8[(long long)ya * out_pitch + x] = bgr_to_y(ba[0], ba[1], ba[2]);
+        out8[(long long)yb * out_pitch + x] = bgr_to_y(bb[0], bb[1], bb[2]);
+        if (!(lx & 1))
+            *reinterpret_cast<unsigned short*>(out_uv + (long long)(ya >> 1) * out_pitch + x) = bgr4_to_uv(s[0], s[1], s[2]);
+    }
+}
+
+// NV12 views of an entry point -> the kernels' descriptor; false: a surface the NV12 routes refuse (nv12.h)
+static bool nv12_views_make(Nv12Views& nv, const unsigned char* const* y, const unsigned char* const* uv, const int* pitch,
+                            const long long* frame_stride, int views, int h, int w) {
+    if (!y || !uv || !pitch || h < 2 || w < 2 || (h & 1) || (w & 1)) return false;
+    for (int i = 0; i < 3; ++i) {
+        nv.y[i] = nullptr; nv.uv[i] = nullptr; nv.pitch[i] = 0; nv.fs[i] = 0;
+        if (i >= views) continue;
+        if (!y[i] || !uv[i] || (pitch[i] & 1) || pitch[i] < w || (reinterpret_cast<unsigned long long>(uv[i]) & 1ull)) return false;
+        if (frame_stride && (frame_stride[i] < 0 || (frame_stride[i] & 1))) return false;
+        nv.y[i] = y[i]; nv.uv[i] = uv[i]; nv.pitch[i] = pitch[i]; nv.fs[i] = frame_stride ? frame_stride[i] : 0;
+    }
+    return true;
+}
+
+// ss_render_average_u8 with NV12 views (y / uv / pitch: host arrays of `views` entries); out_format 0: out = uint8 [hc][wc][3]
+// (out_uv, out_pitch unused), 1: out = the Y plane, out_uv the UV plane, out_pitch bytes per row of both
+extern "C" int ss_render_average_nv12(const unsigned char* const* y, const unsigned char* const* uv, const int* pitch,
+                                      const float* source, const float* T, const float* footprint, long long footprint_floats,
+                                      unsigned char* out, unsigned char* out_uv, int out_pitch, int out_format, int views, int h,
+                                      int w, int hc, int wc, int mode, void* stream) {
+    if (!source || !T || !out || (views != 2 && views != 3) || hc <= 1 || wc <= 1 || (mode != SS_WARP_NORMAL && mode != SS_WARP_FAST) ||
+        (out_format != 0 && out_format != 1))
+        return SS_ERR_ARG;
+    Nv12Views nv;
+    if (!nv12_views_make(nv, y, uv, pitch, nullptr, views, h, w)) return SS_ERR_ARG;
+    if (out_format == 1 && (!out_uv || (hc & 1) || (wc & 1) || (out_pitch & 1) || out_pitch < wc ||
+                            (reinterpret_cast<unsigned long long>(out_uv) & 1ull)))
+        return SS_ERR_ARG;
+    const long long fp_fs = ss_render_footprint_floats(views, hc, wc);
+    if (footprint && footprint_floats != fp_fs) return SS_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 g(ss_cdiv(wc, 64) * ss_cdiv(hc, 8), 1, 1);
+    if (views == 2) {
+        if (out_format) render_average_kernel<2, true><<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
+        else render_average_kernel<2, false><<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
+    } else {
+        if (out_format) render_average_kernel<3, true><<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
+        else render_average_kernel<3, false><<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
+    }
+    return ss_launch_status();
 }
 
 // whole clip, one launch: view k's frame f at views[k] + f * 3 h w floats (planar fp32 [n,3,h,w]), canvas f at
@@ -904,8 +1078,9 @@ __device__ __forceinline__ unsigned lane_index_sum(unsigned long long m) {
 }
 
 // one 64 x 8 tile of ONE frame: rv / source / T / W are that frame's, tile_part its partials of this tile [4 waves][P][LBC_PW]
-template <int VIEWS, bool U8>
-__device__ __forceinline__ void lb_warp_tile(RenderViews rv, const float* __restrict__ source,
+// (Views = Nv12Views: decoded NV12 frames, sampled as sample3_nv12 does; U8 is not looked at then)
+template <int VIEWS, bool U8, typename Views>
+__device__ __forceinline__ void lb_warp_tile(Views rv, const float* __restrict__ source,
                                              const float* __restrict__ T, float* __restrict__ W,
                                              unsigned* __restrict__ tile_part, unsigned tile, int h, int w, int hc, int wc, int mode) {
     constexpr int P = VIEWS - 1;
@@ -935,7 +1110,10 @@ __device__ __forceinline__ void lb_warp_tile(RenderViews rv, const float* __rest
         ss_f2 px, py;
         tps_eval_rows(source + k * SS_NV * 2, T + k * 2 * SS_NT, dytab[wv][k], gx, gya, gyb, px, py);
         float va[3], vb[3];
-        if (U8) {
+        if constexpr (std::is_same<Views, Nv12Views>::value) {
+            sample3_nv12(rv.y[k], rv.uv[k], rv.pitch[k], px.x, py.x, w, h, mode, va);
+            sample3_nv12(rv.y[k], rv.uv[k], rv.pitch[k], px.y, py.y, w, h, mode, vb);
+        } else if (U8) {
             const unsigned char* img8 = reinterpret_cast<const unsigned char*>(rv.img[k]);
             sample3_u8(img8, px.x, py.x, w, h, mode, va);
             sample3_u8(img8, px.y, py.y, w, h, mode, vb);
@@ -1469,6 +1647,21 @@ __global__ __launch_bounds__(256) void lb_frames_warp_kernel(RenderViews rv, con
                             (int)t.hc[f], (int)t.wc[f], mode);
 }
 
+// the same from decoded NV12 frames (frame f of view k at y[k] / uv[k] + f * fs[k])
+template <int VIEWS>
+__global__ __launch_bounds__(256) void lb_frames_warp_kernel(Nv12Views nv, const float* __restrict__ source,
+                                                             const float* __restrict__ T, float* __restrict__ ws,
+                                                             unsigned* __restrict__ partials, int h, int w, int mode, LbFrameTab t) {
+    constexpr int P = VIEWS - 1;
+    const int f = lb_frame_of(t.tile0, t.n, blockIdx.x);
+    const unsigned tile = blockIdx.x - t.tile0[f];
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k) { nv.y[k] += (long long)f * nv.fs[k]; nv.uv[k] += (long long)f * nv.fs[k]; }
+    lb_warp_tile<VIEWS, true>(nv, source + (long long)f * (VIEWS * SS_NV * 2), T + (long long)f * (VIEWS * 2 * SS_NT),
+                              ws + t.w_off[f], partials + t.part_off[f] + ((long long)tile * 4) * (P * LBC_PW), tile, h, w,
+                              (int)t.hc[f], (int)t.wc[f], mode);
+}
+
 // one workgroup per (frame, pass)
 __global__ __launch_bounds__(256) void lb_frames_reduce_kernel(const unsigned* __restrict__ partials,
                                                                unsigned long long* __restrict__ scalars, int passes, LbFrameTab t) {
@@ -1507,17 +1700,18 @@ __global__ __launch_bounds__(64) void lb_frames_blend_rows_kernel(float* __restr
     lb_blend_strip<UNION, U8OUT>(a, hc, wc, rs, bx, by, g);
 }
 
+// nv12 != nullptr: the views are decoded NV12 frames (views_base unused), uint8 frames out
 static int render_linear_frames_launch(const void* const* views_base, const float* source, const float* T, void* const* out,
                                        int frames, int views, int h, int w, const int* hc, const int* wc, int mode, float* ws,
-                                       void* stream, bool u8) {
-    if (!views_base || !source || !T || !out || !hc || !wc || !ws || frames <= 0 || frames > LBF_MAX || (views != 2 && views != 3) ||
+                                       void* stream, bool u8, const Nv12Views* nv12 = nullptr) {
+    if ((!views_base && !nv12) || !source || !T || !out || !hc || !wc || !ws || frames <= 0 || frames > LBF_MAX || (views != 2 && views != 3) ||
         h <= 1 || w <= 1 || (mode != SS_WARP_NORMAL && mode != SS_WARP_FAST))
         return SS_ERR_ARG;
     if (reinterpret_cast<unsigned long long>(ws) & 7ull) return SS_ERR_ARG;
     RenderViews rv;
-    for (int i = 0; i < 3; ++i) rv.img[i] = i < views ? static_cast<const float*>(views_base[i]) : nullptr;
+    for (int i = 0; i < 3; ++i) rv.img[i] = i < views && !nv12 ? static_cast<const float*>(views_base[i]) : nullptr;
     for (int i = 0; i < views; ++i)
-        if (!rv.img[i]) return SS_ERR_ARG;
+        if (!rv.img[i] && !nv12) return SS_ERR_ARG;
     const int P = views - 1;
     // rolling blend only (the 64 x 64-tile form of ss_linear_clip_set_rows(r < 0) does not exist here: default strip height)
     const int rs = g_lb_rows > 0 ? g_lb_rows : 96;
@@ -1549,7 +1743,10 @@ static int render_linear_frames_launch(const void* const* views_base, const floa
     hipStream_t st = (hipStream_t)stream;
     const long long img_fs = u8 ? 3ll * h * w : 12ll * h * w;
     const dim3 ga(t.tile0[frames]), gr(t.strip0[frames]);
-    if (views == 2) {
+    if (nv12) {
+        if (views == 2) lb_frames_warp_kernel<2><<<ga, dim3(256), 0, st>>>(*nv12, source, T, ws, partials, h, w, mode, t);
+        else lb_frames_warp_kernel<3><<<ga, dim3(256), 0, st>>>(*nv12, source, T, ws, partials, h, w, mode, t);
+    } else if (views == 2) {
         if (u8) hipLaunchKernelGGL((lb_frames_warp_kernel<2, true>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
         else hipLaunchKernelGGL((lb_frames_warp_kernel<2, false>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
     } else {
@@ -1586,4 +1783,17 @@ extern "C" int ss_render_linear_frames_u8(const unsigned char* const* views_base
                                           const int* wc, int mode, float* ws, void* stream) {
     return render_linear_frames_launch(reinterpret_cast<const void* const*>(views_base), source, T,
                                        reinterpret_cast<void* const*>(out), frames, views, h, w, hc, wc, mode, ws, stream, true);
+}
+
+// the same from decoded NV12 frames per view (y / uv / pitch / frame_stride: host arrays of `views` entries, frame f of view k at
+// y[k] / uv[k] + f * frame_stride[k]) to uint8 video frames out[f] = [hc[f]][wc[f]][3]; NV12 frames out: ss_bgr_to_nv12 behind it
+extern "C" int ss_render_linear_frames_nv12(const unsigned char* const* y, const unsigned char* const* uv, const int* pitch,
+                                            const long long* frame_stride, const float* source, const float* T,
+                                            unsigned char* const* out, int frames, int views, int h, int w, const int* hc,
+                                            const int* wc, int mode, float* ws, void* stream) {
+    if ((views != 2 && views != 3) || !frame_stride) return SS_ERR_ARG;
+    Nv12Views nv;
+    if (!nv12_views_make(nv, y, uv, pitch, frame_stride, views, h, w)) return SS_ERR_ARG;
+    return render_linear_frames_launch(nullptr, source, T, reinterpret_cast<void* const*>(out), frames, views, h, w, hc, wc, mode,
+                                       ws, stream, true, &nv);
 }

@@ -136,6 +136,24 @@ def _check_u8(what, frames, shape):
     _check_shapes('uint8 frames', frames, (shape,))
 
 
+def _check_nv12(st, frames, out):
+    """push_nv12's arguments: decoded NV12 frames uint8 [H*3/2, W] of the stitcher's H x W (dense columns, any row stride >= W) and
+    the output format; run before any state changes."""
+    if out not in ('bgr', 'nv12'):
+        raise ValueError("push_nv12: out must be 'bgr' or 'nv12', got %r" % (out,))
+    if st.meshes_only:
+        raise ValueError('push_nv12 renders frames: not for meshes_only stitchers')
+    if st.h % 2 or st.w % 2:
+        raise ValueError('NV12 frames have an even height and width: not for a %d x %d stitcher' % (st.h, st.w))
+    shape = (st.h // 2 * 3, st.w)
+    if any(f.dtype != torch.uint8 or tuple(f.shape) != shape or f.stride(-1) != 1 or f.stride(0) < st.w for f in frames):
+        raise ValueError('push_nv12 takes %d uint8 NV12 frames [%d,%d] = [H*3/2, W] with dense columns (a row stride > W is fine), got %s'
+                         % (len(frames), shape[0], shape[1], [(str(f.dtype), tuple(f.shape), tuple(f.stride())) for f in frames]))
+    if out == 'nv12' and (st.viewport is None or st.viewport[0] % 2 or st.viewport[1] % 2):
+        raise ValueError("push_nv12(out='nv12') needs a stitcher built with an even viewport=(Hout, Wout): an NV12 frame has an even, "
+                         'fixed size (this stitcher: viewport=%r)' % (st.viewport,))
+
+
 def _canvas_size(bb):
     """(Hc, Wc) of a canvas (wmin, wmax, hmin, hmax), CPU fp32 [4]."""
     return int((bb[3] - bb[2]).int()), int((bb[1] - bb[0]).int())
@@ -497,10 +515,16 @@ class _Stitcher:
             self.trunk_pair = None
             self._drop_graphs()
 
-    def _push_static(self, *frames, u8=None):
-        """One steady-state push: frames = its HR frames then its LR frames, or u8 = its decoded uint8 frames (push_u8)."""
+    def _push_static(self, *frames, u8=None, nv12=None):
+        """One steady-state push: frames = its HR frames then its LR frames, or u8 = its decoded uint8 frames (push_u8), or nv12 =
+        (its decoded NV12 frames, the output format) (push_nv12).  The step -- and so the captured graph -- is the same for all three:
+        they differ in what writes the graph's LR inputs in front of it and in the render behind it."""
         self._refresh()
-        self._load(frames, u8)
+        if nv12 is not None:                 # the cv2-exact resize of the converted bytes writes the graph's LR inputs
+            for img, lr in zip(nv12[0], self._lr_inputs()):
+                ops.ingest_nv12(img, pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=lr)
+        else:
+            self._load(frames, u8)
         if not self.use_graph:
             self._step_static()
         else:
@@ -512,6 +536,8 @@ class _Stitcher:
             return tuple(m.clone() for m in self.last_meshes)
         if self.grow == 'recapture':
             self.watch.post_copy()
+        if nv12 is not None:
+            return self._render_direct_nv12(self._deferred_splines(), *nv12)
         return self._take(self._deferred_splines(), self.static['out'], u8 or frames[:len(frames) // 2], u8 is not None)
 
     def _deferred_splines(self):
@@ -568,14 +594,46 @@ class _Stitcher:
         shp = (1, 3, self.h, self.w)
         return [ops.render_average([f.reshape(shp) for f in imgs], src, T, self.hc, self.wc, self.warp_mode, footprint=fp)]
 
-    def _render_linear(self, views, src, T, sizes):
+    def _render_direct_nv12(self, deferred, imgs, out):
+        """_render_direct from the caller's NV12 frames: AVERAGE writes the requested format itself; LINEAR writes the uint8 frame
+        (its blend walks a rolling row window) and the sink makes NV12 of it."""
+        src, T, fp = deferred
+        if self.fusion_mode == 'LINEAR':
+            bgr = self._render_linear([f[None] for f in imgs], src[None], T[None], [(self.hc, self.wc)], nv12=True)
+            return [ops.bgr_to_nv12(f) for f in bgr] if out == 'nv12' else bgr
+        if out == 'nv12' and not NV12_FUSED_SINK:
+            return [ops.bgr_to_nv12(ops.render_average_nv12(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp))]
+        return [ops.render_average_nv12(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp, out_format=out)]
+
+    def _push_nv12(self, imgs, out):
+        """push_nv12 of V views (checked): the steady state with the direct render samples the caller's NV12 frames; every other
+        configuration, and the window fill, goes ingest_nv12 -> _push -> canvas_to_u8 (-> bgr_to_nv12)."""
+        with ops.deterministic(self.deterministic):
+            # (the NV12 render has no SS_RENDER_EPS_FOLD form: with that opt-in set the fp32 route keeps the two formats equal)
+            if self._u8_steady() and not (ops.RENDER_EPS_FOLD and self.fusion_mode == 'AVERAGE'):
+                return self._push_static(nv12=(imgs, out))
+            v = len(imgs)
+            hr = torch.empty((v, 3, self.h, self.w), device=self.dev)
+            lr = torch.empty((v, 3, pipeline.LR_H, pipeline.LR_W), device=self.dev)
+            for k, img in enumerate(imgs):
+                ops.ingest_nv12(img, pipeline.LR_H, pipeline.LR_W, hr_out=hr[k:k + 1], lr_out=lr[k:k + 1])
+            frames = self._push(*([hr[k:k + 1] for k in range(v)] + [lr[k:k + 1] for k in range(v)]))
+            frames = [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
+            return [ops.bgr_to_nv12(f) for f in frames] if out == 'nv12' else frames
+
+    def _render_linear(self, views, src, T, sizes, nv12=False):
         """Direct LINEAR render of n frames on their own canvases `sizes` (ops.render_linear_frames, <= 32 frames per call) with
-        the workspaces this stitcher holds; they are re-made when a canvas is set or regrown (the sizes are their key)."""
+        the workspaces this stitcher holds; they are re-made when a canvas is set or regrown (the sizes are their key).  nv12: the
+        views are NV12 frames [n,H*3/2,W] (any pitch), sampled where they lie."""
         res = []
         for c in range(0, len(sizes), 32):
             key = (tuple(sizes[c:c + 32]), len(views))
             if self._lin_ws.get(c, (None, None))[0] != key:
                 self._lin_ws[c] = (key, ops.linear_frames_workspace(key[0], key[1], self.dev))
+            if nv12:
+                res += ops.render_linear_frames_nv12([f[c:c + 32] for f in views], src[c:c + 32], T[c:c + 32], key[0],
+                                                     self.warp_mode, ws=self._lin_ws[c][1])
+                continue
             res += ops.render_linear_frames([f[c:c + 32].contiguous() for f in views], src[c:c + 32], T[c:c + 32], key[0],
                                             self.warp_mode, ws=self._lin_ws[c][1])
         return res
@@ -828,6 +886,22 @@ class OnlineStitcher(_Stitcher):
             frames = self._push(hr[0:1], hr[1:2], lr[0:1], lr[1:2])
             return [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
 
+    def _lr_inputs(self):
+        return [self.static['lr1'], self.static['lr2']]
+
+    @torch.no_grad()
+    def push_nv12(self, img1, img2, out='bgr'):
+        """One DECODED frame pair as a hardware decoder delivers it: img* uint8 NV12 [H*3/2,W] device tensors (rows 0..H-1 the Y
+        plane, then the interleaved UV plane; a row stride > W -- a padded decoder surface -- is accepted) -> list of stitched video
+        frames with push_u8's cadence: out='bgr' uint8 [Hc,Wc,3], byte for byte push_u8 of the frames converted to packed BGR
+        (DESIGN.md, "Frame formats"); out='nv12' uint8 [Hc*3/2,Wc], byte for byte ops.bgr_to_nv12 of those -- what an encoder takes;
+        it needs a stitcher built with an even viewport=(Hout, Wout).  In the steady state with the direct render no BGR frame
+        exists on either side: the resize and the render's taps convert the bytes they read, and AVERAGE fusion writes NV12 itself
+        (LINEAR: the uint8 frame, then the sink).  A stream is fed through one of push, push_u8 and push_nv12; the output format
+        may change from push to push (the captured graph does not depend on it).  Not for the Pipelined / Multi stitchers."""
+        _check_nv12(self, (img1, img2), out)
+        return self._push_nv12((img1, img2), out)
+
     def _push(self, hr1, hr2, lr1, lr2):
         if self.static is not None:
             return self._push_static(hr1, hr2, lr1, lr2)
@@ -965,6 +1039,9 @@ DIRECT_RENDER = os.environ.get('SS_DIRECT_RENDER', '1') != '0'
 # MultiOnlineStitcher, whatever their canvas sizes, instead of the per-frame chain warp + 7 blender launches + copy per stream; under
 # push_u8 from the uint8 frames to the uint8 video frame.  Bit-identical frames.  Read when a stitcher is constructed.
 DIRECT_LINEAR = os.environ.get('SS_DIRECT_LINEAR', '1') != '0'
+# push_nv12(out='nv12') under AVERAGE fusion: the render writes NV12 itself (ops.render_average_nv12, out_format='nv12'); '0': it
+# writes the uint8 frame and ops.bgr_to_nv12 follows, as under LINEAR.  Byte-identical frames (LAB_NOTES.md has the timing).
+NV12_FUSED_SINK = os.environ.get('SS_NV12_FUSED_SINK', '1') != '0'
 _DEFER = object()                      # `out=_DEFER`: compute splines and footprints, leave the render launch to the push
 FUSED_SPLINES = os.environ.get('SS_FUSED_SPLINES', '1') != '0'   # ThreeViewOnlineStitcher: composition + splines in one launch
 PIPE_STREAM_CANDIDATES = 5        # streams tried pairwise by _TwoInFlight._pick_streams
@@ -1173,6 +1250,9 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
 
     def push_many_u8(self, *frames):
         raise ValueError('PipelinedOnlineStitcher has no push_many_u8: use OnlineStitcher.push_many_u8')
+
+    def push_nv12(self, *frames, **kw):
+        raise ValueError('PipelinedOnlineStitcher has no push_nv12: use OnlineStitcher.push_nv12')
 
     def _pipe_alloc(self):
         d = self.dev
@@ -1667,6 +1747,17 @@ class ThreeViewOnlineStitcher(_Stitcher):
             frames = self.push(hr[0:1], hr[1:2], hr[2:3], lr[0:1], lr[1:2], lr[2:3])
             return [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
 
+    def _lr_inputs(self):
+        return [self.chains.static['lrc'][k:k + 1] for k in range(3)]
+
+    @torch.no_grad()
+    def push_nv12(self, img1, img2, img3, out='bgr'):
+        """One DECODED frame triple: uint8 NV12 [H*3/2,W] device tensors -> list of stitched video frames, uint8 [Hc,Wc,3] (out='bgr')
+        or NV12 [Hc*3/2,Wc] (out='nv12', even viewport); byte for byte push_u8 of the converted frames (see OnlineStitcher.push_nv12)."""
+        imgs = (img1, img2, img3)
+        _check_nv12(self, imgs, out)
+        return self._push_nv12(imgs, out)
+
     @torch.no_grad()
     def push(self, hr1, hr2, hr3, lr1, lr2, lr3):
         """One frame triple: hr* [1,3,H,W] (0..255), lr* [1,3,360,480] ([-1,1]), device tensors.
@@ -1807,6 +1898,9 @@ class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
 
     def push_many_u8(self, *frames):
         raise ValueError('PipelinedThreeViewOnlineStitcher has no push_many_u8: use ThreeViewOnlineStitcher.push_many_u8')
+
+    def push_nv12(self, *frames, **kw):
+        raise ValueError('PipelinedThreeViewOnlineStitcher has no push_nv12: use ThreeViewOnlineStitcher.push_nv12')
 
     def _pipe_alloc(self):
         d = self.dev

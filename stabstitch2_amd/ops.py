@@ -977,6 +977,119 @@ def canvas_to_u8(canvas, out=None):
     return out
 
 
+# ---- NV12 frames ("Frame formats"): uint8 [H*3/2, W] -- rows 0..H-1 the Y plane, rows H.. the interleaved UV plane -- or
+# [n, H*3/2, W]; the columns are dense, the row stride is the pitch (>= W: a decoder surface is a view of a wider buffer)
+def _nv12_geometry(t, batched=False):
+    """-> (h, w, pitch, frame stride) of an NV12 device tensor; the frame stride is 0 for a single frame."""
+    if not t.is_cuda:
+        raise H.HipError('stabstitch2_amd kernels need device tensors (got %s); there is no CPU path' % t.device)
+    if t.dtype != torch.uint8 or t.dim() != (3 if batched else 2) or t.shape[-2] % 3 or t.stride(-1) != 1:
+        raise ValueError('an NV12 frame is a uint8 tensor [%sH*3/2, W] with dense columns, got %s %s strides %s'
+                         % ('n, ' if batched else '', t.dtype, tuple(t.shape), tuple(t.stride())))
+    return t.shape[-2] // 3 * 2, t.shape[-1], t.stride(-2), (t.stride(0) if batched else 0)
+
+
+def _nv12_ptr(t, offset=0):
+    p = H.DevPtr(t.data_ptr() + offset)
+    p.dev = t.device.index
+    return p
+
+
+def _nv12_views(frames, batched=False):
+    """list of V NV12 tensors of one size -> (y**, uv**, pitch*, frame_stride*, h, w) host arrays for the NV12 renders."""
+    geo = [_nv12_geometry(f, batched) for f in frames]
+    h, w = geo[0][:2]
+    if any(g[:2] != (h, w) for g in geo) or any(f.device != frames[0].device for f in frames):
+        raise ValueError('the NV12 views of one render share a size and a GPU')
+    v = len(frames)
+    ys = (ctypes.c_void_p * v)(*[f.data_ptr() for f in frames])
+    uvs = (ctypes.c_void_p * v)(*[f.data_ptr() + h * g[2] for f, g in zip(frames, geo)])
+    ys.dev = uvs.dev = frames[0].device.index
+    return ys, uvs, (ctypes.c_int * v)(*[g[2] for g in geo]), (ctypes.c_longlong * v)(*[g[3] for g in geo]), h, w
+
+
+def ingest_nv12(frames, lr_h=360, lr_w=480, want_hr=True, hr_out=None, lr_out=None):
+    """frames NV12 [n,H*3/2,W] (or one frame [H*3/2,W]) -> (hr [n,3,H,W] in 0..255, B,G,R planes | None, lr [n,3,lr_h,lr_w]):
+    byte for byte ingest_u8 of the frames converted to packed BGR, which are never written."""
+    if frames.dim() == 2:
+        frames = frames[None]
+    h, w, pitch, fs = _nv12_geometry(frames, True)
+    n, dev = frames.shape[0], frames.device
+    hr = None
+    if want_hr:
+        hr = hr_out if hr_out is not None else torch.empty((n, 3, h, w), device=dev, dtype=torch.float32)
+    lr = lr_out if lr_out is not None else torch.empty((n, 3, lr_h, lr_w), device=dev, dtype=torch.float32)
+    H.call('ss_ingest_nv12', _nv12_ptr(frames), _nv12_ptr(frames, h * pitch), pitch, fs, H.dptr(hr, allow_none=True), H.dptr(lr),
+           n, h, w, lr_h, lr_w, H.stream())
+    return hr, lr
+
+
+def bgr_to_nv12(bgr, out=None):
+    """uint8 video frames [n,h,w,3] (or [h,w,3]) in B,G,R order -> NV12 [n,h*3/2,w] ([h*3/2,w]); out: an NV12 tensor to write
+    (its row stride is the pitch).  h and w even."""
+    single = bgr.dim() == 3
+    if single:
+        bgr = bgr[None]
+    n, h, w, c = bgr.shape
+    if c != 3 or h % 2 or w % 2:
+        raise ValueError('bgr_to_nv12 takes uint8 [n,h,w,3] frames of even height and width, got %s' % (tuple(bgr.shape),))
+    if out is None:
+        out = torch.empty((n, h // 2 * 3, w), device=bgr.device, dtype=torch.uint8)
+    elif out.dim() == 2:
+        out = out[None]
+    oh, ow, pitch, fs = _nv12_geometry(out, True)
+    if (out.shape[0], oh, ow) != (n, h, w):
+        raise ValueError('bgr_to_nv12: out must be NV12 [%d,%d,%d], got %s' % (n, h // 2 * 3, w, tuple(out.shape)))
+    H.call('ss_bgr_to_nv12', _u8ptr(bgr), _nv12_ptr(out), _nv12_ptr(out, h * pitch), pitch, fs, n, h, w, H.stream())
+    return out[0] if single else out
+
+
+def render_average_nv12(frames, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, out_format='bgr'):
+    """render_average_u8 from decoded NV12 frames: frames = list of 2|3 NV12 device tensors [H*3/2,W]; out_format 'bgr' -> the uint8
+    video frame [hc,wc,3] (byte for byte render_average_u8 of the converted frames), 'nv12' -> that frame as NV12 [hc*3/2,wc]
+    (byte for byte bgr_to_nv12 of it; hc, wc even).  Neither the converted frames nor, for 'nv12', the BGR frame are written."""
+    if out_format not in ('bgr', 'nv12'):
+        raise ValueError("out_format must be 'bgr' or 'nv12'")
+    ys, uvs, pitches, _, h, w = _nv12_views(list(frames))
+    dev = frames[0].device
+    fp, fpn = _fp_args(footprint)
+    if out_format == 'bgr':
+        if out is None:
+            out = torch.empty((hc, wc, 3), device=dev, dtype=torch.uint8)
+        o_y, o_uv, o_pitch = _u8ptr(out), None, 0
+    else:
+        if hc % 2 or wc % 2:
+            raise ValueError('NV12 output needs an even canvas, got %d x %d' % (hc, wc))
+        if out is None:
+            out = torch.empty((hc // 2 * 3, wc), device=dev, dtype=torch.uint8)
+        oh, ow, o_pitch, _ = _nv12_geometry(out)
+        if (oh, ow) != (hc, wc):
+            raise ValueError('render_average_nv12: out must be NV12 [%d,%d], got %s' % (hc // 2 * 3, wc, tuple(out.shape)))
+        o_y, o_uv = _nv12_ptr(out), _nv12_ptr(out, hc * o_pitch)
+    H.call('ss_render_average_nv12', ys, uvs, pitches, H.dptr(_f(source)), H.dptr(T), fp, fpn, o_y, o_uv, o_pitch,
+           int(out_format == 'nv12'), len(frames), h, w, hc, wc, MODES[mode], H.stream())
+    return out
+
+
+def render_linear_frames_nv12(views, source, T, sizes, mode='NORMAL', outs=None, ws=None):
+    """render_linear_frames from decoded NV12 frames: views = list of 2|3 NV12 device tensors [n,H*3/2,W] -> the uint8 video frames
+    [hc_i,wc_i,3], byte for byte render_linear_frames of the converted frames (NV12 frames out: bgr_to_nv12 behind it)."""
+    ys, uvs, pitches, strides, h, w = _nv12_views(list(views), True)
+    n, v, dev = views[0].shape[0], len(views), views[0].device
+    assert source.shape[0] == n and T.shape[0] == n and len(sizes) == n and all(t.shape[0] == n for t in views)
+    sizes = [(int(a), int(b)) for a, b in sizes]
+    if outs is None:
+        outs = [torch.empty((hc, wc, 3), device=dev, dtype=torch.uint8) for hc, wc in sizes]
+    assert len(outs) == n and all(tuple(o.shape) == (hc, wc, 3) and o.dtype == torch.uint8 for o, (hc, wc) in zip(outs, sizes))
+    if ws is None:
+        ws = linear_frames_workspace(sizes, v, dev)
+    hcs = (ctypes.c_int * n)(*[s[0] for s in sizes])
+    wcs = (ctypes.c_int * n)(*[s[1] for s in sizes])
+    H.call('ss_render_linear_frames_nv12', ys, uvs, pitches, strides, H.dptr(_f(source)), H.dptr(T),
+           H.ptr_array(outs, dtype=torch.uint8), n, v, h, w, hcs, wcs, MODES[mode], H.dptr(ws), H.stream())
+    return list(outs)
+
+
 def linear_blend(ref, tgt, ref_m, tgt_m, want_mask=False, out=None):
     """ref,tgt [3,hc,wc]; ref_m,tgt_m [hc,wc] -> fused [3,hc,wc] (or mask1 [hc,wc])."""
     hc, wc = ref_m.shape[-2:]
