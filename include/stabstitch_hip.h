@@ -385,6 +385,63 @@ SS_API int ss_render_linear_frames_nv12(const unsigned char* const* y, const uns
                                         unsigned char* const* out, int frames, int views, int h, int w, const int* hc,
                                         const int* wc, int mode, float* ws, void* stream);
 
+/* ---- exposure compensation of a stream: per-view, per-channel gains ----------------------------
+ * Neither the reference nor its frame loop corrects the exposure / white-balance difference of two physical cameras (AVERAGE
+ * fusion, test_online_tra.py:138-142, shows it as a step at the edge of the overlap; linear_blender :34-58 spreads it over its
+ * ramp): this block ADDS Brown-Lowe gain compensation (the arithmetic of OpenCV's GainCompensator, per channel).
+ * ss_exposure_update: one launch for `frames` consecutive frames of a stream (two when frames > 1: the smoothing walk).
+ * views_base = HOST array of `views` (2 | 3) device pointers: fp32 planes [frames][3][h][w], values 0..255 (u8 = 0), or decoded
+ * uint8 frames [frames][h][w][3] (u8 = 1); img_fs = BYTES between consecutive frames of a view.  footprint = the frames' rows of
+ * ss_render_footprints, fp_fs floats apart, footprint_floats = ss_render_footprint_floats(views, hc, wc) (anything else is
+ * SS_ERR_ARG).  The sample set is the rows' lattice: node (i, j) = canvas pixel (32 j, 8 i) of view pair (a, b), a < b, counts when
+ * 8 i <= hc - 1 and 32 j <= wc - 1, both stored coordinates have |xn| <= 1 and |yn| <= 1, and all three channels of both samples
+ * (the renders' sampler of `mode` at the stored coordinates) lie in [lo, hi].  Per pair and channel n, Sa = sum I_a, Sb = sum I_b
+ * are accumulated in fp64 in one fixed order (no atomics: the result does not depend on timing).  Pairs with n < min_nodes are
+ * dropped; with m_ab = Sa / n, m_ba = Sb / n the target gains of a channel minimise
+ *   sum n_ab [ (g_a m_ab - g_b m_ba)^2 / sigma_n^2 + ((1 - g_a)^2 + (1 - g_b)^2) / sigma_g^2 ]
+ * (fp64, closed form; a view in no kept pair keeps 1), clamped to [gain_min, gain_max] and rounded to fp32.  Smoothing, in fp32 with
+ * one rounding per operation and in stream order: the first frame with a kept pair sets s = target, later ones
+ * s += alpha (target - s), a frame with no kept pair leaves s alone; gains [frames][views][3] receives s after each frame --
+ * what the gain renders below read -- and equals `frames` single-frame calls bit for bit.
+ * state: 12 words on the device -- s [3][3] fp32 (start at 1), word 9 the started flag (int, start at 0), two spare words.
+ * diag: optional [frames][40] doubles: [p * 9 + c * 3 + (n, Sa, Sb)] for pair p of (0,1), (0,2), (1,2) | [27 + v * 3 + c] the
+ * targets | [36] 1 when a pair was kept.  No host synchronisation: capturable.
+ * SS_ERR_ARG: a null pointer, views outside 2..3, a wrong footprint length, lo > hi, alpha outside (0, 1], gain_min <= 0 or
+ * > gain_max, sigma_n or sigma_g <= 0, min_nodes < 1, a mode other than SS_WARP_NORMAL | SS_WARP_FAST. */
+SS_API int ss_exposure_update(const void* const* views_base, int u8, long long img_fs, const float* footprint,
+                              long long footprint_floats, long long fp_fs, int frames, int views, int h, int w, int hc, int wc,
+                              int mode, float alpha, float sigma_n, float sigma_g, float lo, float hi, int min_nodes,
+                              float gain_min, float gain_max, float* state, float* gains, double* diag, void* stream);
+/* The fused renders with exposure gains: the entry of the same name without _gains, with gains [frames][views][3] fp32 on the
+ * device (frames = 1 for the single-frame forms).  The sampled value s of view v, channel c becomes fminf(gains[v][c] * s, 255)
+ * (one fp32 multiply; the clamp because the uint8 sink wraps) before the fusion sees it; masks, footprint skipping (a skipped view
+ * still contributes exactly 0) and everything else are the entry's.  Gains of exactly 1 on values <= 255 reproduce it bit for bit.
+ * gains = NULL and, for the AVERAGE forms, SS_WARP_EPS_FOLD are SS_ERR_ARG. */
+SS_API int ss_render_average_gains(const float* const* imgs, const float* source, const float* T, const float* footprint,
+                                   long long footprint_floats, float* out, int views, int h, int w, int hc, int wc, int mode,
+                                   const float* gains, void* stream);
+SS_API int ss_render_average_u8_gains(const unsigned char* const* frames, const float* source, const float* T,
+                                      const float* footprint, long long footprint_floats, unsigned char* out, int views, int h,
+                                      int w, int hc, int wc, int mode, const float* gains, void* stream);
+SS_API int ss_render_average_clip_gains(const float* const* views_base, const float* source, const float* T,
+                                        const float* footprint, long long footprint_floats, float* out, int frames, int views,
+                                        int h, int w, int hc, int wc, int mode, const float* gains, void* stream);
+SS_API int ss_render_average_clip_u8_gains(const unsigned char* const* views_base, const float* source, const float* T,
+                                           const float* footprint, long long footprint_floats, unsigned char* out, int frames,
+                                           int views, int h, int w, int hc, int wc, int mode, const float* gains, void* stream);
+SS_API int ss_render_linear_clip_gains(const float* const* views_base, const float* source, const float* T, float* out,
+                                       float* mask1_out, int frames, int views, int h, int w, int hc, int wc, int mode,
+                                       float* ws, const float* gains, void* stream);
+SS_API int ss_render_linear_clip_u8_gains(const unsigned char* const* views_base, const float* source, const float* T,
+                                          unsigned char* out, float* mask1_out, int frames, int views, int h, int w, int hc,
+                                          int wc, int mode, float* ws, const float* gains, void* stream);
+SS_API int ss_render_linear_frames_gains(const float* const* views_base, const float* source, const float* T, float* const* out,
+                                         int frames, int views, int h, int w, const int* hc, const int* wc, int mode, float* ws,
+                                         const float* gains, void* stream);
+SS_API int ss_render_linear_frames_u8_gains(const unsigned char* const* views_base, const float* source, const float* T,
+                                            unsigned char* const* out, int frames, int views, int h, int w, const int* hc,
+                                            const int* wc, int mode, float* ws, const float* gains, void* stream);
+
 /* ---- K14: canvas bounding box and mesh normalisation (test_online_tra.py:103-136) ------------
  * mesh: n_points (x,y) pairs at LR scale (480x360); each is scaled to the HR frame as the reference
  * does (x*img_w/480, y*img_h/360) before the min/max; img_w <= 0 / img_h <= 0 means the mesh is

@@ -101,6 +101,18 @@ SIGNATURES = {
                                    [ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_i, c_fp, c_st]),
     'ss_render_linear_frames_nv12': (c_i, [ctypes.POINTER(c_fp), ctypes.POINTER(c_fp), ctypes.POINTER(c_i), ctypes.POINTER(c_ll), c_fp, c_fp,
                                            ctypes.POINTER(c_fp)] + [c_i] * 4 + [ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_i, c_fp, c_st]),
+    'ss_exposure_update': (c_i, [ctypes.POINTER(c_fp), c_i, c_ll, c_fp, c_ll, c_ll] + [c_i] * 7 + [c_f] * 5 + [c_i, c_f, c_f, c_fp, c_fp,
+                                 c_fp, c_st]),
+    'ss_render_average_gains': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_ll, c_fp] + [c_i] * 6 + [c_fp, c_st]),
+    'ss_render_average_u8_gains': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_ll, c_fp] + [c_i] * 6 + [c_fp, c_st]),
+    'ss_render_average_clip_gains': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_ll, c_fp] + [c_i] * 7 + [c_fp, c_st]),
+    'ss_render_average_clip_u8_gains': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_ll, c_fp] + [c_i] * 7 + [c_fp, c_st]),
+    'ss_render_linear_clip_gains': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_fp] + [c_i] * 7 + [c_fp, c_fp, c_st]),
+    'ss_render_linear_clip_u8_gains': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, c_fp, c_fp] + [c_i] * 7 + [c_fp, c_fp, c_st]),
+    'ss_render_linear_frames_gains': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, ctypes.POINTER(c_fp)] + [c_i] * 4 +
+                                      [ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_i, c_fp, c_fp, c_st]),
+    'ss_render_linear_frames_u8_gains': (c_i, [ctypes.POINTER(c_fp), c_fp, c_fp, ctypes.POINTER(c_fp)] + [c_i] * 4 +
+                                         [ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_i, c_fp, c_fp, c_st]),
     'ss_mesh_bbox': (c_i, [c_fp, c_i, c_f, c_f, c_fp, c_i, c_st]),
     'ss_mesh_normalize': (c_i, [c_fp, c_fp, c_fp, c_i, c_f, c_f, c_st]),
     'ss_canvas_watch': (c_i, [c_fp, c_i, c_i, c_f, c_fp, c_fp, c_st]),

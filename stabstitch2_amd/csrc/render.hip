@@ -125,6 +125,16 @@ extern "C" int ss_tps_warp_mask_nchw(const float* U, const float* source, const 
 struct RenderViews {
     const float* img[3];
 };
+// the same views with per-view, per-channel exposure gains [frames][views][3] (ss_exposure_update): a sampled value s of view v,
+// channel c enters the fusion as fminf(g[v][c] * s, 255) -- the clamp because the uint8 sink wraps (render_to_u8)
+struct GainViews {
+    const float* img[3];
+    const float* gains;
+};
+__device__ __forceinline__ void apply_gains(const float* __restrict__ g, float (&v)[3]) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) v[ch] = fminf(__fmul_rn(g[ch], v[ch]), 255.f);
+}
 
 __global__ __launch_bounds__(256) void tps_warp_views_kernel(RenderViews rv, const float* __restrict__ source,
                                                              const float* __restrict__ T, float* __restrict__ out,
@@ -624,9 +634,110 @@ __global__ __launch_bounds__(256) void render_average_kernel(RenderViews rv, con
     }
 }
 
+// The same render with exposure gains (GainViews): the kernel above, every sampled value scaled and clamped before the fusion sees it;
+// a view the footprint skips still contributes exactly 0.  (A copy, not a shared body: the kernels above keep their machine code.)
+template <int VIEWS, bool U8>
+__global__ __launch_bounds__(256) void render_average_kernel(GainViews rv, const float* __restrict__ source,
+                                                             const float* __restrict__ T, const float* __restrict__ fp,
+                                                             float* __restrict__ out, int h, int w, int hc, int wc,
+                                                             int mode, long long img_fs, long long out_fs,
+                                                             long long fp_fs) {
+    {
+        const long long frame = blockIdx.y;
+        source += frame * (VIEWS * SS_NV * 2);
+        T += frame * (VIEWS * 2 * SS_NT);
+        if (fp) fp += frame * fp_fs;
+        out = reinterpret_cast<float*>(reinterpret_cast<char*>(out) + frame * out_fs);
+#pragma unroll
+        for (int k = 0; k < VIEWS; ++k)
+            rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + frame * img_fs);
+        rv.gains += frame * (VIEWS * 3);
+    }
+    unsigned char* const out8 = reinterpret_cast<unsigned char*>(out);
+    // workgroup = 64 x 8 canvas pixels; wave w owns rows w and w + 4 of the tile and evaluates, for every view that
+    // reaches the tile, that view's spline at its 64 columns of both rows (packed over the rows)
+    const int lx = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long hw = (long long)h * w, ohw = (long long)hc * wc;
+    const int ny = (hc + 7) / 8 + 1, nx = 2 * ((wc + 63) / 64) + 1, nbx = (nx - 1) / 2;
+    int tbx, tby;
+    unsigned mask;
+    if (fp) {                                       // tile and its view set from the frame's order table (longest first)
+        const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)render_tile_entry(fp, VIEWS, ny, nx, blockIdx.x));
+        tbx = (int)(e & 0xFFFu); tby = (int)((e >> 12) & 0xFFFu); mask = e >> 24;
+    } else {
+        tby = blockIdx.x / nbx; tbx = blockIdx.x - tby * nbx; mask = (1u << VIEWS) - 1u;
+    }
+    const int x = tbx * 64 + lx;
+    const int ya = tby * 8 + wv, yb = ya + 4;
+    if (tbx * 64 >= wc || ya >= hc) return;       // (whole waves only: the lanes past the canvas edge still help build the table)
+    const bool xin = x < wc;
+    const float gx = linspace_at(-1.f, 1.f, wc, min(x, wc - 1));
+    if (mask == 0u) {                               // no view reaches this tile: avg_fuse(0, 0) = 0
+        if (xin) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                if (U8) {
+                    out8[((long long)ya * wc + x) * 3 + ch] = 0;
+                    if (yb < hc) out8[((long long)yb * wc + x) * 3 + ch] = 0;
+                } else {
+                    out[ch * ohw + (long long)ya * wc + x] = 0.f;
+                    if (yb < hc) out[ch * ohw + (long long)yb * wc + x] = 0.f;
+                }
+            }
+        }
+        return;
+    }
+    // every view that reaches the tile: its spline at this lane's column of the wave's two rows (packed over the rows);
+    // the row-only part of the radial terms comes from a per-wave LDS table (tps_rows_table)
+    __shared__ ss_f2 dytab[4][VIEWS][64];
+    const float gya = linspace_at(-1.f, 1.f, hc, ya), gyb = linspace_at(-1.f, 1.f, hc, min(yb, hc - 1));
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k)
+        if (mask & (1u << k)) tps_rows_table(source + k * SS_NV * 2, gya, gyb, lx, dytab[wv][k]);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // same wave reads it back: ordering only, no barrier
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    float va[VIEWS][3], vb[VIEWS][3];
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k) {
+        if (mask & (1u << k)) {
+            ss_f2 px, py;
+            tps_eval_rows(source + k * SS_NV * 2, T + k * 2 * SS_NT, dytab[wv][k], gx, gya, gyb, px, py);
+            if (U8) {
+                const unsigned char* img8 = reinterpret_cast<const unsigned char*>(rv.img[k]);
+                sample3_u8(img8, px.x, py.x, w, h, mode, va[k]);
+                sample3_u8(img8, px.y, py.y, w, h, mode, vb[k]);
+            } else {
+                sample3(rv.img[k], px.x, py.x, w, h, hw, mode, va[k]);
+                sample3(rv.img[k], px.y, py.y, w, h, hw, mode, vb[k]);
+            }
+            apply_gains(rv.gains + k * 3, va[k]);
+            apply_gains(rv.gains + k * 3, vb[k]);
+        } else {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) { va[k][ch] = 0.f; vb[k][ch] = 0.f; }
+        }
+    }
+    if (!xin) return;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        // the chained fusion in the reference's order ((1 (+) 2) (+) 3), zeros in the places of views that do not reach
+        float fa = avg_fuse(va[0][ch], va[1][ch]), fb = avg_fuse(vb[0][ch], vb[1][ch]);
+        if (VIEWS == 3) { fa = avg_fuse(fa, va[2][ch]); fb = avg_fuse(fb, vb[2][ch]); }
+        if (U8) {
+            out8[((long long)ya * wc + x) * 3 + ch] = render_to_u8(fa);
+            if (yb < hc) out8[((long long)yb * wc + x) * 3 + ch] = render_to_u8(fb);
+        } else {
+            out[ch * ohw + (long long)ya * wc + x] = fa;
+            if (yb < hc) out[ch * ohw + (long long)yb * wc + x] = fb;
+        }
+    }
+}
+
 static int render_average_launch(const void* const* imgs, const float* source, const float* T, const float* footprint,
                                  long long footprint_floats, void* out, int frames, long long img_fs, long long out_fs,
-                                 int views, int h, int w, int hc, int wc, int mode, void* stream, bool u8) {
+                                 int views, int h, int w, int hc, int wc, int mode, void* stream, bool u8,
+                                 const float* gains = nullptr, bool with_gains = false) {
+    if (with_gains && (!gains || (mode & SS_WARP_EPS_FOLD))) return SS_ERR_ARG;       // (the gain forms have no folded variant)
     if (!imgs || !source || !T || !out || frames <= 0 || (views != 2 && views != 3) || h <= 1 || w <= 1 || hc <= 1 ||
         wc <= 1 || ((mode & 0xEF) != SS_WARP_NORMAL && (mode & 0xEF) != SS_WARP_FAST))
         return SS_ERR_ARG;
@@ -655,7 +766,18 @@ static int render_average_launch(const void* const* imgs, const float* source, c
         const float* t_ = T + (long long)f0 * views * 2 * SS_NT;
         const float* p_ = footprint ? footprint + (long long)f0 * fp_fs : nullptr;
         float* o = reinterpret_cast<float*>(static_cast<char*>(out) + (long long)f0 * out_fs);
-        if (fold) {        // opt-in: the reference's + 1e-6 folded into the row table (not its arithmetic; see device_math.h)
+        if (with_gains) {
+            GainViews gv;
+            for (int i = 0; i < 3; ++i) gv.img[i] = r.img[i];
+            gv.gains = gains + (long long)f0 * views * 3;
+            if (views == 2) {
+                if (u8) render_average_kernel<2, true><<<g, dim3(256), 0, st>>>(gv, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
+                else render_average_kernel<2, false><<<g, dim3(256), 0, st>>>(gv, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
+            } else {
+                if (u8) render_average_kernel<3, true><<<g, dim3(256), 0, st>>>(gv, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
+                else render_average_kernel<3, false><<<g, dim3(256), 0, st>>>(gv, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
+            }
+        } else if (fold) {        // opt-in: the reference's + 1e-6 folded into the row table (not its arithmetic; see device_math.h)
             if (views == 2) {
                 if (u8) hipLaunchKernelGGL((render_average_kernel<2, true, true>), g, dim3(256), 0, st, r, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
                 else hipLaunchKernelGGL((render_average_kernel<2, false, true>), g, dim3(256), 0, st, r, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
@@ -836,6 +958,296 @@ extern "C" int ss_render_average_clip_u8(const unsigned char* const* views_base,
                                          int views, int h, int w, int hc, int wc, int mode, void* stream) {
     return render_average_launch(reinterpret_cast<const void* const*>(views_base), source, T, footprint, footprint_floats,
                                  out, frames, 3ll * h * w, 3ll * hc * wc, views, h, w, hc, wc, mode, stream, true);
+}
+
+// the four AVERAGE entries with exposure gains [frames][views][3] on the device (frames = 1 for the single-frame forms)
+extern "C" int ss_render_average_gains(const float* const* imgs, const float* source, const float* T, const float* footprint,
+                                       long long footprint_floats, float* out, int views, int h, int w, int hc, int wc, int mode,
+                                       const float* gains, void* stream) {
+    return render_average_launch(reinterpret_cast<const void* const*>(imgs), source, T, footprint, footprint_floats, out, 1,
+                                 0, 0, views, h, w, hc, wc, mode, stream, false, gains, true);
+}
+extern "C" int ss_render_average_u8_gains(const unsigned char* const* frames, const float* source, const float* T,
+                                          const float* footprint, long long footprint_floats, unsigned char* out, int views, int h,
+                                          int w, int hc, int wc, int mode, const float* gains, void* stream) {
+    return render_average_launch(reinterpret_cast<const void* const*>(frames), source, T, footprint, footprint_floats, out, 1,
+                                 0, 0, views, h, w, hc, wc, mode, stream, true, gains, true);
+}
+extern "C" int ss_render_average_clip_gains(const float* const* views_base, const float* source, const float* T,
+                                            const float* footprint, long long footprint_floats, float* out, int frames, int views,
+                                            int h, int w, int hc, int wc, int mode, const float* gains, void* stream) {
+    return render_average_launch(reinterpret_cast<const void* const*>(views_base), source, T, footprint, footprint_floats,
+                                 out, frames, 12ll * h * w, 12ll * hc * wc, views, h, w, hc, wc, mode, stream, false, gains, true);
+}
+extern "C" int ss_render_average_clip_u8_gains(const unsigned char* const* views_base, const float* source, const float* T,
+                                               const float* footprint, long long footprint_floats, unsigned char* out, int frames,
+                                               int views, int h, int w, int hc, int wc, int mode, const float* gains, void* stream) {
+    return render_average_launch(reinterpret_cast<const void* const*>(views_base), source, T, footprint, footprint_floats,
+                                 out, frames, 3ll * h * w, 3ll * hc * wc, views, h, w, hc, wc, mode, stream, true, gains, true);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Exposure compensation: per-view, per-channel gains of a stream (Brown-Lowe gain compensation, the arithmetic of OpenCV's
+// GainCompensator, per channel), estimated on the footprint lattice -- both views' exactly evaluated sampling coordinates at canvas
+// pixels (32 j, 8 i) are a sample set of the overlap that the push has computed anyway.  Third walker of the footprint, an overload
+// of render_lattice_kernel.  One workgroup per frame:
+//   usable node of pair (a, b): on the canvas (8 i <= hc - 1, 32 j <= wc - 1), both stored coordinates inside [-1, 1]^2, all three
+//     channels of both samples (sample3 / sample3_u8: the render's own sampler) inside [lo, hi];
+//   statistics per pair and channel: n, Sa = sum I_a, Sb = sum I_b in fp64 -- per-thread sums over the nodes tid, tid + 256, ..,
+//     an xor butterfly inside each wave, the four waves added in order: no atomics, one fixed order whatever the timing;
+//   targets (thread 0, fp64, closed form): pairs with n < min_nodes are dropped; with m_a = Sa / n, m_b = Sb / n and
+//     lambda = sigma_n^2 / sigma_g^2 the minimiser of sum n [(g_a m_a - g_b m_b)^2 / sigma_n^2 + ((1 - g_a)^2 + (1 - g_b)^2) / sigma_g^2]
+//     is g = 1 + d with  A d = r,  A_aa = sum n (m_a^2 + lambda),  A_ab = -n m_a m_b,  r_a = sum n m_a (m_b - m_a)   (solved for
+//     the deviation from 1: equal means give r = 0 and gains of exactly 1); a view in no kept pair keeps 1; clamped, rounded to fp32;
+//   smoothing (fp32, one rounding per operation, the frames of a call in stream order): the first frame with a kept pair sets
+//     s = target, later ones s += alpha (target - s), a frame without one leaves s alone; gains[f] = s after frame f.
+// frames = 1: one launch.  frames > 1: the workgroups leave their targets in gains[f] (gains[f][0] = -1: no kept pair -- gain_min > 0)
+// and a second launch of one thread (phase 1) walks them.
+//   state [12]: gains [3][3] (rows of views beyond `views` unused), word 9 = started flag (int), 10, 11 unused
+//   diag [frames][SS_EXPOSURE_DIAG] doubles (optional): [p * 9 + c * 3 + (n, Sa, Sb)] for pair p = (0,1), (0,2), (1,2) | [27 + v * 3 + c]
+//     targets | [36] 1 when a pair was kept
+#define SS_EXPOSURE_DIAG 40
+struct ExposureArgs {
+    const void* img[3];
+    const float* fp;
+    long long img_fs, fp_fs;          // bytes between the frames of a view, floats between footprint rows
+    int frames, h, w, hc, wc, mode, phase, min_nodes;
+    float lo, hi, alpha, gain_min, gain_max;
+    double lambda;
+    float* state;
+    float* gains;
+    double* diag;
+};
+
+// s <- the smoothed gains after a frame whose targets are t (kept: did the frame keep a pair?)
+template <int VIEWS>
+__device__ __forceinline__ void exposure_smooth(float (&s)[VIEWS * 3], int& started, const float (&t)[VIEWS * 3], bool kept, float alpha) {
+    if (!kept) return;
+#pragma unroll
+    for (int q = 0; q < VIEWS * 3; ++q) s[q] = started ? __fadd_rn(s[q], __fmul_rn(alpha, __fsub_rn(t[q], s[q]))) : t[q];
+    started = 1;
+}
+
+template <int VIEWS, bool U8>
+__global__ __launch_bounds__(256) void render_lattice_kernel(ExposureArgs a) {
+    constexpr int P = VIEWS * (VIEWS - 1) / 2;
+    int* const state_i = reinterpret_cast<int*>(a.state);
+    if (a.phase == 1) {                              // the smoothing walk over the targets the workgroups left
+        if (blockIdx.x != 0 || threadIdx.x != 0) return;
+        float s[VIEWS * 3], t[VIEWS * 3];
+#pragma unroll
+        for (int q = 0; q < VIEWS * 3; ++q) s[q] = a.state[q];
+        int started = state_i[9];
+        for (int f = 0; f < a.frames; ++f) {
+            float* g = a.gains + (long long)f * (VIEWS * 3);
+#pragma unroll
+            for (int q = 0; q < VIEWS * 3; ++q) t[q] = g[q];
+            exposure_smooth<VIEWS>(s, started, t, t[0] >= 0.f, a.alpha);
+#pragma unroll
+            for (int q = 0; q < VIEWS * 3; ++q) g[q] = s[q];
+        }
+#pragma unroll
+        for (int q = 0; q < VIEWS * 3; ++q) a.state[q] = s[q];
+        state_i[9] = started;
+        return;
+    }
+    const long long frame = blockIdx.x;
+    const int ny = (a.hc + 7) / 8 + 1, nx = 2 * ((a.wc + 63) / 64) + 1, nn = ny * nx;
+    const float* lat = a.fp + frame * a.fp_fs;
+    const long long hw = (long long)a.h * a.w;
+    int cnt[P];
+    double sa[P][3], sb[P][3];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        cnt[p] = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { sa[p][c] = 0.0; sb[p][c] = 0.0; }
+    }
+    for (int idx = threadIdx.x; idx < nn; idx += 256) {
+        const int i = idx / nx, j = idx - i * nx;
+        if (8 * i > a.hc - 1 || 32 * j > a.wc - 1) continue;       // the lattice's last row / column may lie beyond the canvas
+        float v[VIEWS][3];
+        bool ok[VIEWS];
+#pragma unroll
+        for (int k = 0; k < VIEWS; ++k) {
+            const float xn = lat[((long long)k * nn + idx) * 2], yn = lat[((long long)k * nn + idx) * 2 + 1];
+            ok[k] = fabsf(xn) <= 1.f && fabsf(yn) <= 1.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[k][c] = 0.f;
+            if (ok[k]) {
+                const char* img = static_cast<const char*>(a.img[k]) + frame * a.img_fs;
+                if (U8) sample3_u8(reinterpret_cast<const unsigned char*>(img), xn, yn, a.w, a.h, a.mode, v[k]);
+                else sample3(reinterpret_cast<const float*>(img), xn, yn, a.w, a.h, hw, a.mode, v[k]);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ok[k] = ok[k] && v[k][c] >= a.lo && v[k][c] <= a.hi;
+            }
+        }
+        int p = 0;
+#pragma unroll
+        for (int ka = 0; ka < VIEWS; ++ka)
+#pragma unroll
+            for (int kb = ka + 1; kb < VIEWS; ++kb, ++p)
+                if (ok[ka] && ok[kb]) {
+                    cnt[p] += 1;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) { sa[p][c] += (double)v[ka][c]; sb[p][c] += (double)v[kb][c]; }
+                }
+    }
+    // fixed tree: xor butterfly inside the wave (every lane ends with the same bits), then the four waves in order
+    __shared__ double red[4][P][6];
+    __shared__ int redn[4][P];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            cnt[p] += __shfl_xor(cnt[p], o, 64);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { sa[p][c] += __shfl_xor(sa[p][c], o, 64); sb[p][c] += __shfl_xor(sb[p][c], o, 64); }
+        }
+        if (lane == 0) {
+            redn[wv][p] = cnt[p];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { red[wv][p][c] = sa[p][c]; red[wv][p][3 + c] = sb[p][c]; }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        cnt[p] = redn[0][p] + redn[1][p] + redn[2][p] + redn[3][p];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            sa[p][c] = ((red[0][p][c] + red[1][p][c]) + red[2][p][c]) + red[3][p][c];
+            sb[p][c] = ((red[0][p][3 + c] + red[1][p][3 + c]) + red[2][p][3 + c]) + red[3][p][3 + c];
+        }
+    }
+    bool keep[P], any = false, inv[VIEWS];
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k) inv[k] = false;
+    {
+        int p = 0;
+#pragma unroll
+        for (int ka = 0; ka < VIEWS; ++ka)
+#pragma unroll
+            for (int kb = ka + 1; kb < VIEWS; ++kb, ++p) {
+                keep[p] = cnt[p] >= a.min_nodes;
+                if (keep[p]) { any = true; inv[ka] = true; inv[kb] = true; }
+            }
+    }
+    float t[VIEWS * 3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double A[VIEWS][VIEWS], r[VIEWS], d[VIEWS];
+#pragma unroll
+        for (int k = 0; k < VIEWS; ++k) {
+            r[k] = 0.0;
+#pragma unroll
+            for (int l = 0; l < VIEWS; ++l) A[k][l] = 0.0;
+        }
+        int p = 0;
+#pragma unroll
+        for (int ka = 0; ka < VIEWS; ++ka)
+#pragma unroll
+            for (int kb = ka + 1; kb < VIEWS; ++kb, ++p)
+                if (keep[p]) {
+                    const double n = (double)cnt[p], ma = sa[p][c] / n, mb = sb[p][c] / n;
+                    A[ka][ka] += n * (ma * ma + a.lambda);
+                    A[kb][kb] += n * (mb * mb + a.lambda);
+                    A[ka][kb] -= n * ma * mb;
+                    A[kb][ka] -= n * ma * mb;
+                    r[ka] += n * ma * (mb - ma);
+                    r[kb] += n * mb * (ma - mb);
+                }
+#pragma unroll
+        for (int k = 0; k < VIEWS; ++k)
+            if (!inv[k]) A[k][k] = 1.0;                // a view in no kept pair: its row reads d = 0
+        if constexpr (VIEWS == 2) {
+            const double det = A[0][0] * A[1][1] - A[0][1] * A[1][0];
+            d[0] = (r[0] * A[1][1] - A[0][1] * r[1]) / det;
+            d[1] = (A[0][0] * r[1] - r[0] * A[1][0]) / det;
+        } else {
+            constexpr int X = VIEWS - 1;               // (= 2 here; keeps the V = 2 instantiation's indices inside its arrays)
+            const double c00 = A[1][1] * A[X][X] - A[1][X] * A[X][1], c01 = A[1][0] * A[X][X] - A[1][X] * A[X][0],
+                         c02 = A[1][0] * A[X][1] - A[1][1] * A[X][0];
+            const double det = A[0][0] * c00 - A[0][1] * c01 + A[0][X] * c02;
+            d[0] = (r[0] * c00 - A[0][1] * (r[1] * A[X][X] - A[1][X] * r[X]) + A[0][X] * (r[1] * A[X][1] - A[1][1] * r[X])) / det;
+            d[1] = (A[0][0] * (r[1] * A[X][X] - A[1][X] * r[X]) - r[0] * c01 + A[0][X] * (A[1][0] * r[X] - r[1] * A[X][0])) / det;
+            d[X] = (A[0][0] * (A[1][1] * r[X] - r[1] * A[X][1]) - A[0][1] * (A[1][0] * r[X] - r[1] * A[X][0]) + r[0] * c02) / det;
+        }
+#pragma unroll
+        for (int k = 0; k < VIEWS; ++k) {
+            double g = inv[k] ? 1.0 + d[k] : 1.0;
+            g = fmin(fmax(g, (double)a.gain_min), (double)a.gain_max);
+            t[k * 3 + c] = (float)g;
+        }
+    }
+    if (a.diag) {
+        double* dg = a.diag + frame * SS_EXPOSURE_DIAG;
+#pragma unroll
+        for (int q = 0; q < SS_EXPOSURE_DIAG; ++q) dg[q] = 0.0;
+#pragma unroll
+        for (int p = 0; p < P; ++p)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                dg[p * 9 + c * 3] = (double)cnt[p];
+                dg[p * 9 + c * 3 + 1] = sa[p][c];
+                dg[p * 9 + c * 3 + 2] = sb[p][c];
+            }
+#pragma unroll
+        for (int q = 0; q < VIEWS * 3; ++q) dg[27 + q] = (double)t[q];
+        dg[36] = any ? 1.0 : 0.0;
+    }
+    float* g = a.gains + frame * (VIEWS * 3);
+    if (a.frames == 1) {                             // the whole update in this launch
+        float s[VIEWS * 3];
+#pragma unroll
+        for (int q = 0; q < VIEWS * 3; ++q) s[q] = a.state[q];
+        int started = state_i[9];
+        exposure_smooth<VIEWS>(s, started, t, any, a.alpha);
+#pragma unroll
+        for (int q = 0; q < VIEWS * 3; ++q) { g[q] = s[q]; a.state[q] = s[q]; }
+        state_i[9] = started;
+    } else {
+#pragma unroll
+        for (int q = 0; q < VIEWS * 3; ++q) g[q] = t[q];
+        if (!any) g[0] = -1.f;
+    }
+}
+
+extern "C" int ss_exposure_update(const void* const* views_base, int u8, long long img_fs, const float* footprint,
+                                  long long footprint_floats, long long fp_fs, int frames, int views, int h, int w, int hc, int wc,
+                                  int mode, float alpha, float sigma_n, float sigma_g, float lo, float hi, int min_nodes,
+                                  float gain_min, float gain_max, float* state, float* gains, double* diag, void* stream) {
+    if (!views_base || !footprint || !state || !gains || frames <= 0 || frames > 65535 || (views != 2 && views != 3) || h <= 1 ||
+        w <= 1 || hc <= 1 || wc <= 1 || (mode != SS_WARP_NORMAL && mode != SS_WARP_FAST) || (u8 != 0 && u8 != 1) || img_fs < 0)
+        return SS_ERR_ARG;
+    if (footprint_floats != ss_render_footprint_floats(views, hc, wc) || (frames > 1 && fp_fs < footprint_floats)) return SS_ERR_ARG;
+    if (!(lo <= hi) || !(alpha > 0.f && alpha <= 1.f) || !(gain_min > 0.f) || !(gain_min <= gain_max) || !(gain_max < INFINITY) ||
+        !(sigma_n > 0.f) || !(sigma_g > 0.f) || min_nodes < 1)
+        return SS_ERR_ARG;
+    ExposureArgs a;
+    for (int i = 0; i < 3; ++i) a.img[i] = i < views ? views_base[i] : nullptr;
+    for (int i = 0; i < views; ++i)
+        if (!a.img[i]) return SS_ERR_ARG;
+    a.fp = footprint; a.img_fs = img_fs; a.fp_fs = fp_fs;
+    a.frames = frames; a.h = h; a.w = w; a.hc = hc; a.wc = wc; a.mode = mode; a.phase = 0; a.min_nodes = min_nodes;
+    a.lo = lo; a.hi = hi; a.alpha = alpha; a.gain_min = gain_min; a.gain_max = gain_max;
+    a.lambda = ((double)sigma_n * (double)sigma_n) / ((double)sigma_g * (double)sigma_g);
+    a.state = state; a.gains = gains; a.diag = diag;
+    hipStream_t st = (hipStream_t)stream;
+    for (int phase = 0; phase < (frames > 1 ? 2 : 1); ++phase) {
+        a.phase = phase;
+        const dim3 g(phase ? 1 : frames), b(phase ? 64 : 256);
+        if (views == 2) {
+            if (u8) render_lattice_kernel<2, true><<<g, b, 0, st>>>(a);
+            else render_lattice_kernel<2, false><<<g, b, 0, st>>>(a);
+        } else {
+            if (u8) render_lattice_kernel<3, true><<<g, b, 0, st>>>(a);
+            else render_lattice_kernel<3, false><<<g, b, 0, st>>>(a);
+        }
+    }
+    return ss_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1078,7 +1490,8 @@ __device__ __forceinline__ unsigned lane_index_sum(unsigned long long m) {
 }
 
 // one 64 x 8 tile of ONE frame: rv / source / T / W are that frame's, tile_part its partials of this tile [4 waves][P][LBC_PW]
-// (Views = Nv12Views: decoded NV12 frames, sampled as sample3_nv12 does; U8 is not looked at then)
+// (Views = Nv12Views: decoded NV12 frames, sampled as sample3_nv12 does; U8 is not looked at then;
+//  Views = GainViews: rv.gains = this frame's exposure gains [VIEWS][3], applied to the sampled colours)
 template <int VIEWS, bool U8, typename Views>
 __device__ __forceinline__ void lb_warp_tile(Views rv, const float* __restrict__ source,
                                              const float* __restrict__ T, float* __restrict__ W,
@@ -1120,6 +1533,10 @@ __device__ __forceinline__ void lb_warp_tile(Views rv, const float* __restrict__
         } else {
             sample3(rv.img[k], px.x, py.x, w, h, hw, mode, va);
             sample3(rv.img[k], px.y, py.y, w, h, hw, mode, vb);
+        }
+        if constexpr (std::is_same<Views, GainViews>::value) {       // exposure gains: the colour planes only, the masks are untouched
+            apply_gains(rv.gains + k * 3, va);
+            apply_gains(rv.gains + k * 3, vb);
         }
         if (mode == SS_WARP_NORMAL) {
             const SsTaps ta = taps_normal(px.x, py.x, w, h), tb = taps_normal(px.y, py.y, w, h);
@@ -1183,6 +1600,23 @@ __global__ __launch_bounds__(256) void lb_clip_warp_kernel(RenderViews rv, const
 #pragma unroll
     for (int k = 0; k < VIEWS; ++k)
         rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + frame * img_fs);
+    lb_warp_tile<VIEWS, U8>(rv, source + frame * (VIEWS * SS_NV * 2), T + frame * (VIEWS * 2 * SS_NT),
+                            W + frame * (VIEWS * 4) * ((long long)hc * wc),
+                            partials + ((frame * gridDim.x + blockIdx.x) * 4) * (P * LBC_PW), blockIdx.x, h, w, hc, wc, mode);
+}
+
+// the same with exposure gains [frames][VIEWS][3]
+template <int VIEWS, bool U8>
+__global__ __launch_bounds__(256) void lb_clip_warp_kernel(GainViews rv, const float* __restrict__ source,
+                                                           const float* __restrict__ T, float* __restrict__ W,
+                                                           unsigned* __restrict__ partials, int h, int w, int hc, int wc,
+                                                           int mode, long long img_fs) {
+    constexpr int P = VIEWS - 1;
+    const long long frame = blockIdx.y;
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k)
+        rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + frame * img_fs);
+    rv.gains += frame * (VIEWS * 3);
     lb_warp_tile<VIEWS, U8>(rv, source + frame * (VIEWS * SS_NV * 2), T + frame * (VIEWS * 2 * SS_NT),
                             W + frame * (VIEWS * 4) * ((long long)hc * wc),
                             partials + ((frame * gridDim.x + blockIdx.x) * 4) * (P * LBC_PW), blockIdx.x, h, w, hc, wc, mode);
@@ -1500,7 +1934,8 @@ extern "C" int ss_linear_clip_set_rows(int rows) {
 
 static int render_linear_clip_launch(const void* const* views_base, const float* source, const float* T, void* out,
                                      float* mask1_out, int frames, int views, int h, int w, int hc, int wc, int mode,
-                                     float* ws, void* stream, bool u8) {
+                                     float* ws, void* stream, bool u8, const float* gains = nullptr, bool with_gains = false) {
+    if (with_gains && !gains) return SS_ERR_ARG;
     if (!views_base || !source || !T || !out || !ws || frames <= 0 || frames > 65535 || (views != 2 && views != 3) || h <= 1 ||
         w <= 1 || hc < 11 || wc < 11 || wc > 65535 || hc > 65535 || (mode != SS_WARP_NORMAL && mode != SS_WARP_FAST))
         return SS_ERR_ARG;
@@ -1520,7 +1955,18 @@ static int render_linear_clip_launch(const void* const* views_base, const float*
     unsigned* partials = reinterpret_cast<unsigned*>(scalars + (long long)frames * P * 16);
     const long long img_fs = u8 ? 3ll * h * w : 12ll * h * w;
     const dim3 ga(tiles, frames);
-    if (views == 2) {
+    if (with_gains) {
+        GainViews gv;
+        for (int i = 0; i < 3; ++i) gv.img[i] = rv.img[i];
+        gv.gains = gains;
+        if (views == 2) {
+            if (u8) lb_clip_warp_kernel<2, true><<<ga, dim3(256), 0, st>>>(gv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
+            else lb_clip_warp_kernel<2, false><<<ga, dim3(256), 0, st>>>(gv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
+        } else {
+            if (u8) lb_clip_warp_kernel<3, true><<<ga, dim3(256), 0, st>>>(gv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
+            else lb_clip_warp_kernel<3, false><<<ga, dim3(256), 0, st>>>(gv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
+        }
+    } else if (views == 2) {
         if (u8) hipLaunchKernelGGL((lb_clip_warp_kernel<2, true>), ga, dim3(256), 0, st, rv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
         else hipLaunchKernelGGL((lb_clip_warp_kernel<2, false>), ga, dim3(256), 0, st, rv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
     } else {
@@ -1588,6 +2034,20 @@ extern "C" int ss_render_linear_clip_u8(const unsigned char* const* views_base, 
                                      h, w, hc, wc, mode, ws, stream, true);
 }
 
+// the two clip entries with exposure gains [frames][views][3] on the device
+extern "C" int ss_render_linear_clip_gains(const float* const* views_base, const float* source, const float* T, float* out,
+                                           float* mask1_out, int frames, int views, int h, int w, int hc, int wc, int mode,
+                                           float* ws, const float* gains, void* stream) {
+    return render_linear_clip_launch(reinterpret_cast<const void* const*>(views_base), source, T, out, mask1_out, frames, views,
+                                     h, w, hc, wc, mode, ws, stream, false, gains, true);
+}
+extern "C" int ss_render_linear_clip_u8_gains(const unsigned char* const* views_base, const float* source, const float* T,
+                                              unsigned char* out, float* mask1_out, int frames, int views, int h, int w, int hc,
+                                              int wc, int mode, float* ws, const float* gains, void* stream) {
+    return render_linear_clip_launch(reinterpret_cast<const void* const*>(views_base), source, T, out, mask1_out, frames, views,
+                                     h, w, hc, wc, mode, ws, stream, true, gains, true);
+}
+
 // ------------------------------------------------------------------------------------------------
 // LINEAR fusion of up to 32 frames that each have their OWN canvas (the current frames of S live streams, or one streaming push:
 // frames = 1): the clip render above with ragged sizes, still three launches (four with three views) whatever `frames` is.  The
@@ -1642,6 +2102,24 @@ __global__ __launch_bounds__(256) void lb_frames_warp_kernel(RenderViews rv, con
 #pragma unroll
     for (int k = 0; k < VIEWS; ++k)
         rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + (long long)f * img_fs);
+    lb_warp_tile<VIEWS, U8>(rv, source + (long long)f * (VIEWS * SS_NV * 2), T + (long long)f * (VIEWS * 2 * SS_NT),
+                            ws + t.w_off[f], partials + t.part_off[f] + ((long long)tile * 4) * (P * LBC_PW), tile, h, w,
+                            (int)t.hc[f], (int)t.wc[f], mode);
+}
+
+// the same with exposure gains [frames][VIEWS][3]
+template <int VIEWS, bool U8>
+__global__ __launch_bounds__(256) void lb_frames_warp_kernel(GainViews rv, const float* __restrict__ source,
+                                                             const float* __restrict__ T, float* __restrict__ ws,
+                                                             unsigned* __restrict__ partials, int h, int w, int mode,
+                                                             long long img_fs, LbFrameTab t) {
+    constexpr int P = VIEWS - 1;
+    const int f = lb_frame_of(t.tile0, t.n, blockIdx.x);
+    const unsigned tile = blockIdx.x - t.tile0[f];
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k)
+        rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + (long long)f * img_fs);
+    rv.gains += (long long)f * (VIEWS * 3);
     lb_warp_tile<VIEWS, U8>(rv, source + (long long)f * (VIEWS * SS_NV * 2), T + (long long)f * (VIEWS * 2 * SS_NT),
                             ws + t.w_off[f], partials + t.part_off[f] + ((long long)tile * 4) * (P * LBC_PW), tile, h, w,
                             (int)t.hc[f], (int)t.wc[f], mode);
@@ -1703,7 +2181,9 @@ __global__ __launch_bounds__(64) void lb_frames_blend_rows_kernel(float* __restr
 // nv12 != nullptr: the views are decoded NV12 frames (views_base unused), uint8 frames out
 static int render_linear_frames_launch(const void* const* views_base, const float* source, const float* T, void* const* out,
                                        int frames, int views, int h, int w, const int* hc, const int* wc, int mode, float* ws,
-                                       void* stream, bool u8, const Nv12Views* nv12 = nullptr) {
+                                       void* stream, bool u8, const Nv12Views* nv12 = nullptr, const float* gains = nullptr,
+                                       bool with_gains = false) {
+    if (with_gains && (!gains || nv12)) return SS_ERR_ARG;
     if ((!views_base && !nv12) || !source || !T || !out || !hc || !wc || !ws || frames <= 0 || frames > LBF_MAX || (views != 2 && views != 3) ||
         h <= 1 || w <= 1 || (mode != SS_WARP_NORMAL && mode != SS_WARP_FAST))
         return SS_ERR_ARG;
@@ -1746,6 +2226,17 @@ static int render_linear_frames_launch(const void* const* views_base, const floa
     if (nv12) {
         if (views == 2) lb_frames_warp_kernel<2><<<ga, dim3(256), 0, st>>>(*nv12, source, T, ws, partials, h, w, mode, t);
         else lb_frames_warp_kernel<3><<<ga, dim3(256), 0, st>>>(*nv12, source, T, ws, partials, h, w, mode, t);
+    } else if (with_gains) {
+        GainViews gv;
+        for (int i = 0; i < 3; ++i) gv.img[i] = rv.img[i];
+        gv.gains = gains;
+        if (views == 2) {
+            if (u8) lb_frames_warp_kernel<2, true><<<ga, dim3(256), 0, st>>>(gv, source, T, ws, partials, h, w, mode, img_fs, t);
+            else lb_frames_warp_kernel<2, false><<<ga, dim3(256), 0, st>>>(gv, source, T, ws, partials, h, w, mode, img_fs, t);
+        } else {
+            if (u8) lb_frames_warp_kernel<3, true><<<ga, dim3(256), 0, st>>>(gv, source, T, ws, partials, h, w, mode, img_fs, t);
+            else lb_frames_warp_kernel<3, false><<<ga, dim3(256), 0, st>>>(gv, source, T, ws, partials, h, w, mode, img_fs, t);
+        }
     } else if (views == 2) {
         if (u8) hipLaunchKernelGGL((lb_frames_warp_kernel<2, true>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
         else hipLaunchKernelGGL((lb_frames_warp_kernel<2, false>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
@@ -1783,6 +2274,22 @@ extern "C" int ss_render_linear_frames_u8(const unsigned char* const* views_base
                                           const int* wc, int mode, float* ws, void* stream) {
     return render_linear_frames_launch(reinterpret_cast<const void* const*>(views_base), source, T,
                                        reinterpret_cast<void* const*>(out), frames, views, h, w, hc, wc, mode, ws, stream, true);
+}
+
+// the two frames entries with exposure gains [frames][views][3] on the device
+extern "C" int ss_render_linear_frames_gains(const float* const* views_base, const float* source, const float* T, float* const* out,
+                                             int frames, int views, int h, int w, const int* hc, const int* wc, int mode, float* ws,
+                                             const float* gains, void* stream) {
+    return render_linear_frames_launch(reinterpret_cast<const void* const*>(views_base), source, T,
+                                       reinterpret_cast<void* const*>(out), frames, views, h, w, hc, wc, mode, ws, stream, false,
+                                       nullptr, gains, true);
+}
+extern "C" int ss_render_linear_frames_u8_gains(const unsigned char* const* views_base, const float* source, const float* T,
+                                                unsigned char* const* out, int frames, int views, int h, int w, const int* hc,
+                                                const int* wc, int mode, float* ws, const float* gains, void* stream) {
+    return render_linear_frames_launch(reinterpret_cast<const void* const*>(views_base), source, T,
+                                       reinterpret_cast<void* const*>(out), frames, views, h, w, hc, wc, mode, ws, stream, true,
+                                       nullptr, gains, true);
 }
 
 // the same from decoded NV12 frames per view (y / uv / pitch / frame_stride: host arrays of `views` entries, frame f of view k at

@@ -154,6 +154,24 @@ def _check_nv12(st, frames, out):
                          'fixed size (this stitcher: viewport=%r)' % (st.viewport,))
 
 
+def _exposure_params(exposure, meshes_only=False):
+    """OnlineStitcher's exposure= -> None | ops.ExposureParams (True: the defaults)."""
+    if exposure is None or exposure is False:
+        return None
+    if meshes_only:
+        raise ValueError('exposure compensation scales rendered frames: not for meshes_only stitchers')
+    if exposure is True:
+        return ops.ExposureParams()
+    if not isinstance(exposure, ops.ExposureParams):
+        raise ValueError('exposure must be None, True or an ops.ExposureParams, got %r' % (exposure,))
+    return exposure
+
+
+def _no_exposure(cls, exposure):
+    if exposure is not None and exposure is not False:
+        raise ValueError('%s has no exposure compensation yet: it is built for OnlineStitcher only' % cls)
+
+
 def _canvas_size(bb):
     """(Hc, Wc) of a canvas (wmin, wmax, hmin, hmax), CPU fp32 [4]."""
     return int((bb[3] - bb[2]).int()), int((bb[1] - bb[0]).int())
@@ -366,7 +384,8 @@ class _Stitcher:
     _LINEAR_DIRECT = True    # may LINEAR fusion take the direct render (DIRECT_LINEAR)?  Not with two pushes in flight (_TwoInFlight)
 
     def __init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only=False, canvases=1,
-                 viewport=None, zoom_limit=2.0):
+                 viewport=None, zoom_limit=2.0, exposure=None):
+        self.exposure = _exposure_params(exposure, meshes_only)      # None: no launch, buffer or graph node of it exists
         if grow not in ('never', 'recapture', 'refit'):
             raise ValueError("grow must be 'never', 'recapture' or 'refit'")
         if viewport is not None:
@@ -411,6 +430,10 @@ class _Stitcher:
         self._batch = collections.OrderedDict()   # push_many: batch size k -> its work buffers and graph, least recently used first
         self.graph_nodes_batch = {}      # push_many: nodes of the steady-state graph captured for batch size k (None: not exposed)
         self.batch_captures = 0          # push_many: graphs captured so far
+        # exposure compensation: the stream's gain state (ops.exposure_state) -- it belongs to the stream, not to a canvas or a
+        # graph, and survives a regrow / recapture
+        self._exp_state = None if self.exposure is None else ops.exposure_state(self.dev)
+        self._exp_fp = None              # direct render: the footprint row the step left for the push's exposure update
 
     # ------------------------------------------------------------------ canvas overflow
     def overflow_report(self):
@@ -487,7 +510,22 @@ class _Stitcher:
 
     def _state(self):
         st = self.static
-        return [st[k] for k in _STATE] + ([] if self.meshes_only else [self.watch.wi, self.watch.wf] + self.watch.fit_state())
+        return ([st[k] for k in _STATE] + ([] if self.meshes_only else [self.watch.wi, self.watch.wf] + self.watch.fit_state()) +
+                ([] if self._exp_state is None else [self._exp_state]))
+
+    @property
+    def exposure_gains(self):
+        """The smoothed exposure gains [2,3] (view, channel) the last frame was rendered with (ones before the first frame with a
+        usable overlap); None without exposure=.  Synchronises."""
+        if self._exp_state is None:
+            return None
+        self._sync_state()
+        return self._exp_state[:6].reshape(2, 3).cpu()
+
+    def _exposure_gains(self, views, fp):
+        """The gains of the n frames `views` (V x [n,3,H,W] fp32 or [n,H,W,3] uint8) with footprint rows fp [n, .]: the stream's
+        state advanced through them in order -> [n,V,3]."""
+        return ops.exposure_update(views, fp, self.hc, self.wc, self._exp_state, self.exposure, self.warp_mode)
 
     def _drop_graphs(self):
         """The canvas grew or a net was reloaded: the captured steady-state graphs hold the old canvas / weights by address."""
@@ -556,21 +594,37 @@ class _Stitcher:
         imgs [1,3,H,W] (written to `out` if given; out=_DEFER: splines and footprint left in self._deferred for the push's render).
         watch = (guard, watch_i [1,4], watch_f [1,4]): the overflow watcher has not seen `src` yet; fit (grow='refit'): the
         ops.CanvasFit of this canvas -- the launch that carries the watcher re-fixes the box behind it."""
-        if watch is not None and not (self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE):
+        skip = self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE
+        if watch is not None and not (skip or self.exposure is not None):
             ops.canvas_watch(src[None], watch[1], watch[2], watch[0], fit=fit)   # no footprint launch to carry it
             watch = None
+        efp = gains = None
+        if self.exposure is not None:        # the footprint lattice is the estimator's sample set: made whatever the fusion is
+            efp = ops.render_footprints(src[None], T[None], self.h, self.w, self.hc, self.wc, watch=watch,
+                                        fit=None if watch is None else fit)
+            if out is _DEFER:                # the update reads the frames the render reads: the push runs both on the caller's
+                self._exp_fp = efp
+            else:
+                shp = (1, 3, self.h, self.w)
+                gains = self._exposure_gains([f.reshape(shp) for f in imgs], efp)
         if self.fusion_mode == 'AVERAGE':
             fp = None
-            if pipeline.SKIP_OUTSIDE:        # same footprint skipping as the offline render (pipeline.render_frames)
+            if efp is not None:
+                fp = efp[0] if skip else None
+            elif pipeline.SKIP_OUTSIDE:      # same footprint skipping as the offline render (pipeline.render_frames)
                 fp = ops.render_footprints(src[None], T[None], self.h, self.w, self.hc, self.wc, watch=watch,
                                            fit=None if watch is None else fit)[0]
             if out is _DEFER:
                 self._deferred = (src, T, fp)
                 return None
-            return ops.render_average(imgs, src, T, self.hc, self.wc, self.warp_mode, out=out, footprint=fp)
+            return ops.render_average(imgs, src, T, self.hc, self.wc, self.warp_mode, out=out, footprint=fp, gains=gains)
         if out is _DEFER:                    # LINEAR: the graph ends with the splines and the watcher
             self._deferred = (src, T, None)
             return None
+        if gains is not None:                # LINEAR with exposure: the fused render at n = 1 (bit-identical to the chain below)
+            shp = (1, 3, self.h, self.w)
+            return self._render_linear([f.reshape(shp) for f in imgs], src[None], T[None], [(self.hc, self.wc)], gains=gains,
+                                       outs=None if out is None else [out])[0]
         w = ops.tps_warp_views(imgs, src, T, self.hc, self.wc, self.warp_mode)        # [V,4,Hc,Wc]
         res = ops.linear_blend(w[0, 0:3], w[1, 0:3], w[0, 3], w[1, 3])
         if len(imgs) == 3:
@@ -586,13 +640,18 @@ class _Stitcher:
     def _render_direct(self, deferred, imgs, u8):
         """One canvas, two or three views."""
         src, T, fp = deferred
+        gains = None
+        if self.exposure is not None:        # the gains through this frame, from the caller's frames, in front of the render launch
+            shp = (1, self.h, self.w, 3) if u8 else (1, 3, self.h, self.w)
+            gains = self._exposure_gains([f.reshape(shp) for f in imgs], self._exp_fp)
         if self.fusion_mode == 'LINEAR':     # the fused three / four launches at n = 1, uint8 frames in -> the uint8 video frame out
             shp = (1, self.h, self.w, 3) if u8 else (1, 3, self.h, self.w)
-            return self._render_linear([f.reshape(shp) for f in imgs], src[None], T[None], [(self.hc, self.wc)])
+            return self._render_linear([f.reshape(shp) for f in imgs], src[None], T[None], [(self.hc, self.wc)], gains=gains)
         if u8:                           # uint8 frames in, the uint8 video frame out: no fp32 frame planes, no fp32 canvas
-            return [ops.render_average_u8(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp)]
+            return [ops.render_average_u8(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp, gains=gains)]
         shp = (1, 3, self.h, self.w)
-        return [ops.render_average([f.reshape(shp) for f in imgs], src, T, self.hc, self.wc, self.warp_mode, footprint=fp)]
+        return [ops.render_average([f.reshape(shp) for f in imgs], src, T, self.hc, self.wc, self.warp_mode, footprint=fp,
+                                   gains=gains)]
 
     def _render_direct_nv12(self, deferred, imgs, out):
         """_render_direct from the caller's NV12 frames: AVERAGE writes the requested format itself; LINEAR writes the uint8 frame
@@ -621,7 +680,7 @@ class _Stitcher:
             frames = [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
             return [ops.bgr_to_nv12(f) for f in frames] if out == 'nv12' else frames
 
-    def _render_linear(self, views, src, T, sizes, nv12=False):
+    def _render_linear(self, views, src, T, sizes, nv12=False, gains=None, outs=None):
         """Direct LINEAR render of n frames on their own canvases `sizes` (ops.render_linear_frames, <= 32 frames per call) with
         the workspaces this stitcher holds; they are re-made when a canvas is set or regrown (the sizes are their key).  nv12: the
         views are NV12 frames [n,H*3/2,W] (any pitch), sampled where they lie."""
@@ -635,7 +694,8 @@ class _Stitcher:
                                                      self.warp_mode, ws=self._lin_ws[c][1])
                 continue
             res += ops.render_linear_frames([f[c:c + 32].contiguous() for f in views], src[c:c + 32], T[c:c + 32], key[0],
-                                            self.warp_mode, ws=self._lin_ws[c][1])
+                                            self.warp_mode, ws=self._lin_ws[c][1], outs=None if outs is None else outs[c:c + 32],
+                                            gains=None if gains is None else gains[c:c + 32])
         return res
 
     # ------------------------------------------------------------------ k frames of every view per call (one canvas)
@@ -725,20 +785,27 @@ class _Stitcher:
         """The batch's frames from the caller's frames imgs (V x [k,3,H,W] fp32, or [k,H,W,3] uint8 when u8) in one render: AVERAGE
         with the footprints, LINEAR through the fused clip render (bit-identical per frame to the push's tps_warp_views +
         linear_blend)."""
-        src, T, fp = deferred
+        src, T, fp = deferred[:3]
         views = [f.contiguous() for f in imgs]
+        # exposure: the k frames' gains in one update (stream order, bit-identical to k single-frame updates)
+        gains = None if self.exposure is None else self._exposure_gains(views, deferred[3])
         if self.fusion_mode == 'AVERAGE':
             render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
-            out = render(views, src, T, self.hc, self.wc, self.warp_mode, footprint=fp)
+            out = render(views, src, T, self.hc, self.wc, self.warp_mode, footprint=fp, gains=gains)
         else:
-            out = ops.render_linear_clip(views, src, T, self.hc, self.wc, self.warp_mode)
+            out = ops.render_linear_clip(views, src, T, self.hc, self.wc, self.warp_mode, gains=gains)
         return list(out.unbind(0))
 
 
 class OnlineStitcher(_Stitcher):
     def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 use_graph=True, grow='never', meshes_only=False, deterministic=False, viewport=None, zoom_limit=2.0):
+                 use_graph=True, grow='never', meshes_only=False, deterministic=False, viewport=None, zoom_limit=2.0, exposure=None):
         """canvas: optional (wmin, wmax, hmin, hmax) in HR pixels (e.g. the offline bbox).
+        exposure: None (default: nothing of it exists), True (ops.ExposureParams() defaults) or an ops.ExposureParams -- exposure
+        compensation of the two cameras: every frame handed out (the first window's seven, in order, included) is rendered with
+        per-view, per-channel gains estimated on that frame's overlap (the footprint lattice: DESIGN.md, "Exposure compensation")
+        and smoothed through that frame; `exposure_gains` reads them.  The gain state belongs to the stream: a regrown or recaptured
+        canvas keeps it.  Not with meshes_only, not with push_nv12.
         viewport: optional (Hout, Wout), each in 11..65535 -- the size of EVERY frame this stitcher returns ([3,Hout,Wout] fp32,
         [Hout,Wout,3] uint8 from push_u8 / push_many_u8; the first window's seven included), known from construction: `hc, wc ==
         Hout, Wout`, so an encoder or a pinned result ring can be sized before the first push.  The canvas box is the box the
@@ -760,8 +827,9 @@ class OnlineStitcher(_Stitcher):
         exceed `zoom_limit` x the one the canvas was set with (a diverging mesh must not shrink the picture to nothing), or when no
         side moves by half a pixel.  `canvas_epoch`, `canvas_box` and `overflow_report()` then read the device (they synchronise).
         push_many takes one refit per call, behind the batch's watcher: a drift inside one call can crop up to k counted frames."""
+        _exposure_params(exposure, meshes_only)
         _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only,
-                           viewport=viewport, zoom_limit=zoom_limit)
+                           viewport=viewport, zoom_limit=zoom_limit, exposure=exposure)
         self.deterministic = bool(deterministic)
         self.last_meshes = None
         self.bbox = None if canvas is None else torch.tensor(canvas, dtype=torch.float32, device=self.dev)
@@ -899,6 +967,8 @@ class OnlineStitcher(_Stitcher):
         exists on either side: the resize and the render's taps convert the bytes they read, and AVERAGE fusion writes NV12 itself
         (LINEAR: the uint8 frame, then the sink).  A stream is fed through one of push, push_u8 and push_nv12; the output format
         may change from push to push (the captured graph does not depend on it).  Not for the Pipelined / Multi stitchers."""
+        if getattr(self, 'exposure', None) is not None:
+            raise ValueError('push_nv12 has no exposure compensation yet: feed an exposure stitcher through push_u8 or push')
         _check_nv12(self, (img1, img2), out)
         return self._push_nv12((img1, img2), out)
 
@@ -1019,10 +1089,12 @@ class OnlineStitcher(_Stitcher):
         src, T = ops.stream_splines([m1[0, -1], m2[0, -1]], WINDOW * e, self.bbox, self.nrigid, self.h, self.w, frames=k)
         guard, wi, wf = self.watch.args()
         ops.canvas_watch_frames(src, wi, wf, guard, fit=self.watch.fit_args())
-        fp = None
-        if self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE:
-            fp = ops.render_footprints(src, T, self.h, self.w, self.hc, self.wc)
-        B['deferred'] = (src, T, fp)
+        fp = efp = None
+        skip = self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE
+        if skip or self.exposure is not None:        # (exposure: the lattice is the estimator's sample set whatever the fusion is)
+            efp = ops.render_footprints(src, T, self.h, self.w, self.hc, self.wc)
+            fp = efp if skip else None
+        B['deferred'] = (src, T, fp) if self.exposure is None else (src, T, fp, efp)
 
 
 BATCH_MAX = 32                         # push_many: frames of every view per call
@@ -1238,8 +1310,9 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
     overflow is counted as in OnlineStitcher) or, with a viewport, re-fixed on the device (grow='refit').  LINEAR fusion renders inside the graphs (no direct LINEAR render: _TwoInFlight)."""
 
     def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE', deterministic=False,
-                 grow='never', viewport=None, zoom_limit=2.0):
+                 grow='never', viewport=None, zoom_limit=2.0, exposure=None):
         """grow: 'never', or 'refit' with a viewport (see OnlineStitcher and _TwoInFlight)."""
+        _no_exposure('PipelinedOnlineStitcher', exposure)
         self._check_grow(grow)
         OnlineStitcher.__init__(self, nets, height, width, canvas, margin, warp_mode, fusion_mode, use_graph=True, grow=grow,
                                 meshes_only=False, deterministic=deterministic, viewport=viewport, zoom_limit=zoom_limit)
@@ -1313,7 +1386,8 @@ class MultiOnlineStitcher(_Stitcher):
     stream's result is independent of its neighbours bit for bit (tests/test_gpu_round4.py)."""
 
     def __init__(self, nets, height, width, streams, canvases=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 use_graph=True, grow='never', meshes_only=False, deterministic=False, chain=False, viewport=None, zoom_limit=2.0):
+                 use_graph=True, grow='never', meshes_only=False, deterministic=False, chain=False, viewport=None, zoom_limit=2.0,
+                 exposure=None):
         """grow: as OnlineStitcher -- 'never' counts the frames whose mesh left their stream's canvas (`clipped_frames`, per
         stream), 'recapture' re-fixes the canvases of the streams that come near an edge and captures the graph again, 'refit' (with
         a viewport) re-fixes each stream's box on the device inside the push's launches.
@@ -1321,6 +1395,7 @@ class MultiOnlineStitcher(_Stitcher):
         meshes_only: no canvases, no render -- `push` returns the S streams' newly smoothed meshes (m1, m2) [S,k,7,9,2] (k = 7 on the
         7th push, then 1) or None; ThreeViewOnlineStitcher runs its two pair chains as such a batch of two and captures the graph
         itself (use_graph is ignored)."""
+        _no_exposure(type(self).__name__, exposure)
         _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only,
                            canvases=max(1, int(streams)), viewport=viewport, zoom_limit=zoom_limit)
         self.deterministic = bool(deterministic)      # geometry-only kernel policy: S batched streams == S single streams, bit for bit
@@ -1588,8 +1663,9 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
     _U8_STEADY = False       # push_u8: ingest_u8 -> push -> canvas_to_u8
 
     def __init__(self, nets, height, width, streams, canvases=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 deterministic=False, grow='never', viewport=None, zoom_limit=2.0):
+                 deterministic=False, grow='never', viewport=None, zoom_limit=2.0, exposure=None):
         """grow: 'never', or 'refit' with a viewport (see MultiOnlineStitcher and _TwoInFlight)."""
+        _no_exposure('PipelinedMultiOnlineStitcher', exposure)
         self._check_grow(grow)
         MultiOnlineStitcher.__init__(self, nets, height, width, streams, canvases, margin, warp_mode, fusion_mode, use_graph=True,
                                      grow=grow, meshes_only=False, deterministic=deterministic, viewport=viewport,
@@ -1660,9 +1736,10 @@ class ThreeViewOnlineStitcher(_Stitcher):
     `push_many` / `push_many_u8` take k consecutive triples per call (see OnlineStitcher.push_many)."""
 
     def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 use_graph=True, grow='never', deterministic=False, viewport=None, zoom_limit=2.0):
+                 use_graph=True, grow='never', deterministic=False, viewport=None, zoom_limit=2.0, exposure=None):
         """deterministic: every push under the conv engine's geometry-only kernel policy (ops.deterministic; as OnlineStitcher's):
         push_many's frames then equal single pushes' bit for bit."""
+        _no_exposure(type(self).__name__, exposure)
         # the two pair chains as a batch of two streams over the CHAIN of three views: every launch serves both pairs, view 2's
         # trunk features are computed once
         self.chains = MultiOnlineStitcher(nets, height, width, streams=2, margin=margin, warp_mode=warp_mode, fusion_mode=fusion_mode,
@@ -1886,8 +1963,9 @@ class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
     _U8_STEADY = False       # push_u8: ingest_u8 -> push -> canvas_to_u8
 
     def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 grow='never', viewport=None, zoom_limit=2.0):
+                 grow='never', viewport=None, zoom_limit=2.0, exposure=None):
         """grow: 'never', or 'refit' with a viewport (see ThreeViewOnlineStitcher and _TwoInFlight)."""
+        _no_exposure('PipelinedThreeViewOnlineStitcher', exposure)
         self._check_grow(grow)
         ThreeViewOnlineStitcher.__init__(self, nets, height, width, canvas, first_canvas, margin, warp_mode, fusion_mode,
                                          use_graph=True, grow=grow, viewport=viewport, zoom_limit=zoom_limit)

@@ -858,7 +858,68 @@ def _fp_args(footprint):
     return H.dptr(footprint, True), (0 if footprint is None else footprint.numel())
 
 
-def render_average(imgs, source, T, hc, wc, mode='NORMAL', out=None, footprint=None):
+class ExposureParams(collections.namedtuple('ExposureParams', 'alpha sigma_n sigma_g lo hi min_nodes gain_min gain_max')):
+    """Parameters of exposure_update (include/stabstitch_hip.h, ss_exposure_update): smoothing factor alpha in (0, 1], the error
+    model's sigma_n (grey levels) and sigma_g (gain), the usable sample range [lo, hi], the fewest nodes a view pair needs to count,
+    and the clamp [gain_min, gain_max] of the target gains."""
+    __slots__ = ()
+
+    def __new__(cls, alpha=0.1, sigma_n=10.0, sigma_g=0.1, lo=4.0, hi=251.0, min_nodes=16, gain_min=0.5, gain_max=2.0):
+        return super().__new__(cls, float(alpha), float(sigma_n), float(sigma_g), float(lo), float(hi), int(min_nodes),
+                               float(gain_min), float(gain_max))
+
+
+EXPOSURE_DIAG = 40      # doubles per frame of exposure_update's diagnostics
+
+
+def exposure_state(device):
+    """A stream's exposure state [12] fp32: smoothed gains [3][3] (1), word 9 the started flag (int 0), two spare words."""
+    st = torch.zeros(12, device=device, dtype=torch.float32)
+    st[:9] = 1.0
+    return st
+
+
+def exposure_update(views, footprint, hc, wc, state, params=None, mode='NORMAL', gains=None, want_diag=False):
+    """Exposure gains of n consecutive frames of a stream, smoothed through each of them: views = list of 2|3 contiguous device
+    tensors [n,3,h,w] fp32 (0..255) or [n,h,w,3] uint8 (a single frame may come without the n axis); footprint [n, ss_render_footprint_floats]
+    (or one row) = the frames' rows of render_footprints on the hc x wc canvas; state = exposure_state(device), advanced in place;
+    -> gains [n,V,3] fp32, what the renders' gains= takes (with want_diag also [n, EXPOSURE_DIAG] float64: per pair (0,1), (0,2),
+    (1,2) and channel (n, Sa, Sb), at 27 the targets [V,3], at 36 whether a pair was kept).  One launch for n = 1, two otherwise; no
+    host synchronisation.  Bit-identical to n single-frame calls."""
+    p = ExposureParams() if params is None else params
+    v = len(views)
+    u8 = views[0].dtype == torch.uint8
+    views = [t if t.dim() == 4 else t[None] for t in views]
+    if u8:
+        n, h, w, _ = views[0].shape
+        assert all(tuple(t.shape) == (n, h, w, 3) for t in views)
+    else:
+        n, _, h, w = views[0].shape
+        assert all(tuple(t.shape) == (n, 3, h, w) for t in views)
+    fp = footprint if footprint.dim() == 2 else footprint[None]
+    assert fp.shape[0] == n and fp.stride(1) == 1 and tuple(state.shape) == (12,)
+    if gains is None:
+        gains = torch.empty((n, v, 3), device=state.device, dtype=torch.float32)
+    assert tuple(gains.shape) == (n, v, 3)
+    diag = torch.empty((n, EXPOSURE_DIAG), device=state.device, dtype=torch.float64) if want_diag else None
+    arr = H.ptr_array(views, dtype=torch.uint8 if u8 else torch.float32)
+    fpp = H.DevPtr(fp.data_ptr())
+    fpp.dev = fp.device.index
+    assert fp.is_cuda and fp.dtype == torch.float32
+    H.call('ss_exposure_update', arr, int(u8), (3 if u8 else 12) * h * w, fpp, fp.shape[1], fp.stride(0) if n > 1 else fp.shape[1],
+           n, v, h, w, hc, wc, MODES[mode], p.alpha, p.sigma_n, p.sigma_g, p.lo, p.hi, p.min_nodes, p.gain_min, p.gain_max,
+           H.dptr(state), H.dptr(gains), H.dptr(diag, True, dtype=torch.float64), H.stream())
+    return (gains, diag) if want_diag else gains
+
+
+def _gains(gains, n, v):
+    """gains= of a render of n frames of v views -> its device pointer ([n,V,3] fp32; [V,3] for one frame)."""
+    if tuple(gains.shape) not in ((n, v, 3),) + (((v, 3),) if n == 1 else ()):
+        raise ValueError('gains must be [%d,%d,3], got %s' % (n, v, tuple(gains.shape)))
+    return H.dptr(gains)
+
+
+def render_average(imgs, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
     """imgs: list of 2|3 device tensors [1,3,h,w] / [3,h,w]; source [V,63,2]; T [V,2,66] -> [3,hc,wc].
     footprint: this frame's row of `render_footprints` (views that cannot reach a tile are skipped there and count as
     exactly 0 -- a deliberate deviation from the reference, whose clamped sampler returns a rounding residue of up to
@@ -871,12 +932,16 @@ def render_average(imgs, source, T, hc, wc, mode='NORMAL', out=None, footprint=N
     if out is None:
         out = torch.empty((3, hc, wc), device=imgs[0].device, dtype=torch.float32)
     fp, fpn = _fp_args(footprint)
+    if gains is not None:                # exposure gains [V,3] (exposure_update): sampled values scaled and clamped to 255
+        H.call('ss_render_average_gains', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, H.dptr(out), v, h, w, hc, wc,
+               MODES[mode], _gains(gains, 1, v), H.stream())
+        return out
     H.call('ss_render_average', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, H.dptr(out), v, h, w, hc, wc,
            _avg_mode(mode), H.stream())
     return out
 
 
-def render_average_u8(frames, source, T, hc, wc, mode='NORMAL', out=None, footprint=None):
+def render_average_u8(frames, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
     """The fused AVERAGE render straight from decoded uint8 frames to the uint8 video frame: frames = list of 2|3 device
     tensors [h,w,3] uint8 (cv2 channel order); -> uint8 [hc,wc,3] = `.astype(np.uint8)` of the fused values.  Equal,
     bit for bit, to ingest (uint8 -> fp32 planes) + render_average + canvas_to_u8; the fp32 planes and canvas are never
@@ -887,12 +952,16 @@ def render_average_u8(frames, source, T, hc, wc, mode='NORMAL', out=None, footpr
     if out is None:
         out = torch.empty((hc, wc, 3), device=frames[0].device, dtype=torch.uint8)
     fp, fpn = _fp_args(footprint)
+    if gains is not None:
+        H.call('ss_render_average_u8_gains', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, _u8ptr(out), v, h, w, hc, wc,
+               MODES[mode], _gains(gains, 1, v), H.stream())
+        return out
     H.call('ss_render_average_u8', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, _u8ptr(out), v, h, w, hc, wc,
            _avg_mode(mode), H.stream())
     return out
 
 
-def render_average_clip(views, source, T, hc, wc, mode='NORMAL', out=None, footprint=None):
+def render_average_clip(views, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
     """A whole clip in one launch: views = list of 2|3 contiguous device tensors [n,3,h,w]; source [n,V,63,2];
     T [n,V,2,66]; footprint [n, ss_render_footprint_floats] | None -> [n,3,hc,wc].  Bit-identical to n render_average calls."""
     v = len(views)
@@ -903,12 +972,16 @@ def render_average_clip(views, source, T, hc, wc, mode='NORMAL', out=None, footp
         out = torch.empty((n, 3, hc, wc), device=views[0].device, dtype=torch.float32)
     assert tuple(out.shape) == (n, 3, hc, wc)
     fp, fpn = H.dptr(footprint, True), (0 if footprint is None else footprint.shape[-1])
+    if gains is not None:
+        H.call('ss_render_average_clip_gains', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, H.dptr(out), n, v, h, w, hc, wc,
+               MODES[mode], _gains(gains, n, v), H.stream())
+        return out
     H.call('ss_render_average_clip', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, H.dptr(out), n, v, h, w, hc, wc,
            _avg_mode(mode), H.stream())
     return out
 
 
-def render_average_clip_u8(views, source, T, hc, wc, mode='NORMAL', out=None, footprint=None):
+def render_average_clip_u8(views, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
     """The same from decoded uint8 clips: views = list of 2|3 contiguous device tensors [n,h,w,3] uint8 -> uint8 [n,hc,wc,3]."""
     v = len(views)
     n, h, w, _ = views[0].shape
@@ -918,6 +991,10 @@ def render_average_clip_u8(views, source, T, hc, wc, mode='NORMAL', out=None, fo
         out = torch.empty((n, hc, wc, 3), device=views[0].device, dtype=torch.uint8)
     assert tuple(out.shape) == (n, hc, wc, 3)
     fp, fpn = H.dptr(footprint, True), (0 if footprint is None else footprint.shape[-1])
+    if gains is not None:
+        H.call('ss_render_average_clip_u8_gains', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, _u8ptr(out), n, v, h, w, hc, wc,
+               MODES[mode], _gains(gains, n, v), H.stream())
+        return out
     H.call('ss_render_average_clip_u8', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, _u8ptr(out), n, v, h, w, hc, wc,
            _avg_mode(mode), H.stream())
     return out
@@ -1104,7 +1181,7 @@ def linear_blend(ref, tgt, ref_m, tgt_m, want_mask=False, out=None):
     return mk if want_mask else out
 
 
-def render_linear_clip(views, source, T, hc, wc, mode='NORMAL', out=None, want_masks=False):
+def render_linear_clip(views, source, T, hc, wc, mode='NORMAL', out=None, want_masks=False, gains=None):
     """LINEAR fusion of a whole clip in three launches (four with three views): views = list of 2|3 contiguous device tensors
     [n,3,h,w] fp32 -> [n,3,hc,wc]; or [n,h,w,3] uint8 -> the uint8 video frames [n,hc,wc,3].  source [n,V,63,2]; T [n,V,2,66].
     want_masks: also return the blender's mask1 of every pass [n,V-1,hc,wc].  Bit-identical to the per-frame chain
@@ -1126,6 +1203,11 @@ def render_linear_clip(views, source, T, hc, wc, mode='NORMAL', out=None, want_m
     assert tuple(out.shape) == shape and out.dtype == views[0].dtype
     ws = torch.empty(int(H.lib().ss_linear_clip_workspace_floats(n, v, hc, wc)), device=dev, dtype=torch.float32)
     mk = torch.empty((n, v - 1, hc, wc), device=dev, dtype=torch.float32) if want_masks else None
+    if gains is not None:                # exposure gains [n,V,3]: the colour planes scaled and clamped, the masks untouched
+        H.call('ss_render_linear_clip_u8_gains' if u8 else 'ss_render_linear_clip_gains', arr, H.dptr(_f(source)), H.dptr(T),
+               _u8ptr(out) if u8 else H.dptr(out), H.dptr(mk, True), n, v, h, w, hc, wc, MODES[mode], H.dptr(ws),
+               _gains(gains, n, v), H.stream())
+        return (out, mk) if want_masks else out
     H.call('ss_render_linear_clip_u8' if u8 else 'ss_render_linear_clip', arr, H.dptr(_f(source)), H.dptr(T),
            _u8ptr(out) if u8 else H.dptr(out), H.dptr(mk, True), n, v, h, w, hc, wc, MODES[mode], H.dptr(ws), H.stream())
     return (out, mk) if want_masks else out
@@ -1143,7 +1225,7 @@ def linear_frames_workspace(sizes, views, device):
     return torch.empty(need, device=device, dtype=torch.float32)
 
 
-def render_linear_frames(views, source, T, sizes, mode='NORMAL', outs=None, ws=None):
+def render_linear_frames(views, source, T, sizes, mode='NORMAL', outs=None, ws=None, gains=None):
     """LINEAR fusion of n frames that each have their OWN canvas in three launches (four with three views) whatever n is: views =
     list of 2|3 contiguous device tensors [n,3,h,w] fp32 -> list of n frames [3,hc_i,wc_i]; or [n,h,w,3] uint8 -> the uint8 video
     frames [hc_i,wc_i,3].  source [n,V,63,2]; T [n,V,2,66]; sizes = n pairs (hc, wc); 1 <= n <= 32.  outs: n tensors to write;
@@ -1168,6 +1250,11 @@ def render_linear_frames(views, source, T, sizes, mode='NORMAL', outs=None, ws=N
         ws = linear_frames_workspace(sizes, v, dev)
     hcs = (ctypes.c_int * n)(*[s[0] for s in sizes])
     wcs = (ctypes.c_int * n)(*[s[1] for s in sizes])
+    if gains is not None:
+        H.call('ss_render_linear_frames_u8_gains' if u8 else 'ss_render_linear_frames_gains', H.ptr_array(views, dtype=dt),
+               H.dptr(_f(source)), H.dptr(T), H.ptr_array(outs, dtype=dt), n, v, h, w, hcs, wcs, MODES[mode], H.dptr(ws),
+               _gains(gains, n, v), H.stream())
+        return list(outs)
     H.call('ss_render_linear_frames_u8' if u8 else 'ss_render_linear_frames', H.ptr_array(views, dtype=dt), H.dptr(_f(source)),
            H.dptr(T), H.ptr_array(outs, dtype=dt), n, v, h, w, hcs, wcs, MODES[mode], H.dptr(ws), H.stream())
     return list(outs)
