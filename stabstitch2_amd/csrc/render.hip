@@ -14,22 +14,33 @@
 #include "nv12.h"
 
 // grid_sample(bilinear, zeros, align_corners=True) taps: x = (xn+1)/2*(W-1), out-of-range taps -> 0
-__device__ __forceinline__ float sample_fast(const float* __restrict__ pl, float xn, float yn, int W, int H) {
+// the four taps of one coordinate: corner indices, weights, and which rows / columns lie inside the image
+struct SsFastTaps {
+    int x0, y0, x1, y1;
+    float w00, w01, w10, w11;
+    bool vx0, vx1, vy0, vy1;
+};
+__device__ __forceinline__ SsFastTaps taps_fast(float xn, float yn, int W, int H) {
+    SsFastTaps t;
     float x = ((xn + 1.f) / 2.f) * (float)(W - 1);
     float y = ((yn + 1.f) / 2.f) * (float)(H - 1);
     float xf = fminf(fmaxf(floorf(x), -4.f), (float)W + 4.f);
     float yf = fminf(fmaxf(floorf(y), -4.f), (float)H + 4.f);
-    int x0 = (int)xf, y0 = (int)yf, x1 = x0 + 1, y1 = y0 + 1;
+    t.x0 = (int)xf; t.y0 = (int)yf; t.x1 = t.x0 + 1; t.y1 = t.y0 + 1;
     // ATen grid_sampler_2d: nw = (ix_se - ix)(iy_se - iy), ne = (ix - ix_sw)(iy_sw - iy), ...
-    float w00 = (xf + 1.f - x) * (yf + 1.f - y), w01 = (x - xf) * (yf + 1.f - y);
-    float w10 = (xf + 1.f - x) * (y - yf), w11 = (x - xf) * (y - yf);
-    bool vx0 = (unsigned)x0 < (unsigned)W, vx1 = (unsigned)x1 < (unsigned)W;
-    bool vy0 = (unsigned)y0 < (unsigned)H, vy1 = (unsigned)y1 < (unsigned)H;
+    t.w00 = (xf + 1.f - x) * (yf + 1.f - y); t.w01 = (x - xf) * (yf + 1.f - y);
+    t.w10 = (xf + 1.f - x) * (y - yf); t.w11 = (x - xf) * (y - yf);
+    t.vx0 = (unsigned)t.x0 < (unsigned)W; t.vx1 = (unsigned)t.x1 < (unsigned)W;
+    t.vy0 = (unsigned)t.y0 < (unsigned)H; t.vy1 = (unsigned)t.y1 < (unsigned)H;
+    return t;
+}
+__device__ __forceinline__ float sample_fast(const float* __restrict__ pl, float xn, float yn, int W, int H) {
+    const SsFastTaps t = taps_fast(xn, yn, W, H);
     float r = 0.f;
-    if (vx0 && vy0) r += pl[(long long)y0 * W + x0] * w00;
-    if (vx1 && vy0) r += pl[(long long)y0 * W + x1] * w01;
-    if (vx0 && vy1) r += pl[(long long)y1 * W + x0] * w10;
-    if (vx1 && vy1) r += pl[(long long)y1 * W + x1] * w11;
+    if (t.vx0 && t.vy0) r += pl[(long long)t.y0 * W + t.x0] * t.w00;
+    if (t.vx1 && t.vy0) r += pl[(long long)t.y0 * W + t.x1] * t.w01;
+    if (t.vx0 && t.vy1) r += pl[(long long)t.y1 * W + t.x0] * t.w10;
+    if (t.vx1 && t.vy1) r += pl[(long long)t.y1 * W + t.x1] * t.w11;
     return r;
 }
 
@@ -127,13 +138,49 @@ struct RenderViews {
 };
 // the same views with per-view, per-channel exposure gains [frames][views][3] (ss_exposure_update): a sampled value s of view v,
 // channel c enters the fusion as fminf(g[v][c] * s, 255) -- the clamp because the uint8 sink wraps (render_to_u8)
-struct GainViews {
-    const float* img[3];
+struct GainViews : RenderViews {
     const float* gains;
 };
 __device__ __forceinline__ void apply_gains(const float* __restrict__ g, float (&v)[3]) {
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) v[ch] = fminf(__fmul_rn(g[ch], v[ch]), 255.f);
+}
+// a descriptor of frame 0 -> of frame f: image pointers by img_fs BYTES, gains by VIEWS * 3, NV12 planes by their own fs[k]
+template <int VIEWS>
+__device__ __forceinline__ void views_to_frame(RenderViews& rv, long long f, long long img_fs) {
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k)
+        rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + f * img_fs);
+}
+template <int VIEWS>
+__device__ __forceinline__ void views_to_frame(GainViews& rv, long long f, long long img_fs) {
+    views_to_frame<VIEWS>(static_cast<RenderViews&>(rv), f, img_fs);
+    rv.gains += f * (VIEWS * 3);
+}
+template <int VIEWS>
+__device__ __forceinline__ void views_to_frame(Nv12Views& nv, long long f) {
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k) { nv.y[k] += f * nv.fs[k]; nv.uv[k] += f * nv.fs[k]; }
+}
+
+// ---- host dispatch: the run-time (views, u8, ..) of an entry point as compile-time constants, so that a launcher names each of its
+// kernels once: f gets one std::bool_constant per flag / std::integral_constant<int, VIEWS> and instantiates on their values
+template <typename F>
+static void with_flags(bool b0, bool b1, F&& f) {
+    if (b0) { if (b1) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
+    else { if (b1) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
+}
+template <typename F>
+static void with_views(int views, bool u8, F&& f) {       // views = 2 or 3: every caller has checked it
+    with_flags(views == 3, u8, [&](auto three, auto U8) { f(std::integral_constant<int, decltype(three)::value ? 3 : 2>{}, U8); });
+}
+// the view pointers of an entry point (+ its exposure gains, nullptr without) -> the kernels' descriptor; false: a view is missing
+static bool views_make(GainViews& gv, const void* const* imgs, int views, const float* gains) {
+    for (int i = 0; i < 3; ++i) gv.img[i] = i < views ? static_cast<const float*>(imgs[i]) : nullptr;
+    gv.gains = gains;
+    for (int i = 0; i < views; ++i)
+        if (!gv.img[i]) return false;
+    return true;
 }
 
 __global__ __launch_bounds__(256) void tps_warp_views_kernel(RenderViews rv, const float* __restrict__ source,
@@ -363,6 +410,20 @@ __device__ __forceinline__ unsigned render_tile_entry(const float* __restrict__ 
     return cnt[4 + (unsigned long long)k * nt + off];
 }
 
+// this workgroup's tile (tbx, tby) of its frame -> the views that reach it: from the frame's order table (longest first), or, without
+// a footprint, row-major and every view
+template <int VIEWS>
+__device__ __forceinline__ unsigned render_tile(const float* __restrict__ fp, int hc, int wc, int& tbx, int& tby) {
+    const int ny = (hc + 7) / 8 + 1, nx = 2 * ((wc + 63) / 64) + 1, nbx = (nx - 1) / 2;
+    if (fp) {
+        const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)render_tile_entry(fp, VIEWS, ny, nx, blockIdx.x));
+        tbx = (int)(e & 0xFFFu); tby = (int)((e >> 12) & 0xFFFu);
+        return e >> 24;
+    }
+    tby = blockIdx.x / nbx; tbx = blockIdx.x - tby * nbx;
+    return (1u << VIEWS) - 1u;
+}
+
 extern "C" long long ss_render_footprint_floats(int views, int hc, int wc) {
     if (views <= 0 || hc <= 1 || wc <= 1) return 0;
     return (long long)views * ((long long)(ss_cdiv(hc, 8) + 1) * (2 * ss_cdiv(wc, 64) + 1) * 2 + 4) +
@@ -463,22 +524,14 @@ __device__ __forceinline__ void sample3_u8(const unsigned char* __restrict__ in,
         for (int ch = 0; ch < 3; ++ch)
             v[ch] = blend4(t, (float)in[ia + ch], (float)in[ib + ch], (float)in[ic + ch], (float)in[id + ch]);
     } else {
-        float x = ((xn + 1.f) / 2.f) * (float)(w - 1);
-        float y = ((yn + 1.f) / 2.f) * (float)(h - 1);
-        float xf = fminf(fmaxf(floorf(x), -4.f), (float)w + 4.f);
-        float yf = fminf(fmaxf(floorf(y), -4.f), (float)h + 4.f);
-        int x0 = (int)xf, y0 = (int)yf, x1 = x0 + 1, y1 = y0 + 1;
-        float w00 = (xf + 1.f - x) * (yf + 1.f - y), w01 = (x - xf) * (yf + 1.f - y);
-        float w10 = (xf + 1.f - x) * (y - yf), w11 = (x - xf) * (y - yf);
-        bool vx0 = (unsigned)x0 < (unsigned)w, vx1 = (unsigned)x1 < (unsigned)w;
-        bool vy0 = (unsigned)y0 < (unsigned)h, vy1 = (unsigned)y1 < (unsigned)h;
+        const SsFastTaps t = taps_fast(xn, yn, w, h);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {            // sample_fast, term by term
             float r = 0.f;
-            if (vx0 && vy0) r += (float)in[((long long)y0 * w + x0) * 3 + ch] * w00;
-            if (vx1 && vy0) r += (float)in[((long long)y0 * w + x1) * 3 + ch] * w01;
-            if (vx0 && vy1) r += (float)in[((long long)y1 * w + x0) * 3 + ch] * w10;
-            if (vx1 && vy1) r += (float)in[((long long)y1 * w + x1) * 3 + ch] * w11;
+            if (t.vx0 && t.vy0) r += (float)in[((long long)t.y0 * w + t.x0) * 3 + ch] * t.w00;
+            if (t.vx1 && t.vy0) r += (float)in[((long long)t.y0 * w + t.x1) * 3 + ch] * t.w01;
+            if (t.vx0 && t.vy1) r += (float)in[((long long)t.y1 * w + t.x0) * 3 + ch] * t.w10;
+            if (t.vx1 && t.vy1) r += (float)in[((long long)t.y1 * w + t.x1) * 3 + ch] * t.w11;
             v[ch] = r;
         }
     }
@@ -497,26 +550,18 @@ __device__ __forceinline__ void sample3_nv12(const unsigned char* __restrict__ y
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) v[ch] = blend4(t, (float)a[ch], (float)b[ch], (float)c[ch], (float)d[ch]);
     } else {
-        float x = ((xn + 1.f) / 2.f) * (float)(w - 1);
-        float y = ((yn + 1.f) / 2.f) * (float)(h - 1);
-        float xf = fminf(fmaxf(floorf(x), -4.f), (float)w + 4.f);
-        float yf = fminf(fmaxf(floorf(y), -4.f), (float)h + 4.f);
-        int x0 = (int)xf, y0 = (int)yf, x1 = x0 + 1, y1 = y0 + 1;
-        float w00 = (xf + 1.f - x) * (yf + 1.f - y), w01 = (x - xf) * (yf + 1.f - y);
-        float w10 = (xf + 1.f - x) * (y - yf), w11 = (x - xf) * (y - yf);
-        bool vx0 = (unsigned)x0 < (unsigned)w, vx1 = (unsigned)x1 < (unsigned)w;
-        bool vy0 = (unsigned)y0 < (unsigned)h, vy1 = (unsigned)y1 < (unsigned)h;
-        if (vx0 && vy0) nv12_pixel(yp, uvp, pitch, y0, x0, a);
-        if (vx1 && vy0) nv12_pixel(yp, uvp, pitch, y0, x1, b);
-        if (vx0 && vy1) nv12_pixel(yp, uvp, pitch, y1, x0, c);
-        if (vx1 && vy1) nv12_pixel(yp, uvp, pitch, y1, x1, d);
+        const SsFastTaps t = taps_fast(xn, yn, w, h);
+        if (t.vx0 && t.vy0) nv12_pixel(yp, uvp, pitch, t.y0, t.x0, a);
+        if (t.vx1 && t.vy0) nv12_pixel(yp, uvp, pitch, t.y0, t.x1, b);
+        if (t.vx0 && t.vy1) nv12_pixel(yp, uvp, pitch, t.y1, t.x0, c);
+        if (t.vx1 && t.vy1) nv12_pixel(yp, uvp, pitch, t.y1, t.x1, d);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {            // sample_fast, term by term
             float r = 0.f;
-            if (vx0 && vy0) r += (float)a[ch] * w00;
-            if (vx1 && vy0) r += (float)b[ch] * w01;
-            if (vx0 && vy1) r += (float)c[ch] * w10;
-            if (vx1 && vy1) r += (float)d[ch] * w11;
+            if (t.vx0 && t.vy0) r += (float)a[ch] * t.w00;
+            if (t.vx1 && t.vy0) r += (float)b[ch] * t.w01;
+            if (t.vx0 && t.vy1) r += (float)c[ch] * t.w10;
+            if (t.vx1 && t.vy1) r += (float)d[ch] * t.w11;
             v[ch] = r;
         }
     }
@@ -534,8 +579,11 @@ __device__ __forceinline__ unsigned char render_to_u8(float v) {          // `.a
 // then the next frame's: the light tail of one frame runs beside the heavy head of the next -- 32 launch boundaries and
 // 32 partially filled last rounds per clip less than one launch per frame).  Per-frame strides: `img_fs` / `out_fs` in
 // BYTES (frames of a view / canvases are equally spaced), `fp_fs` in floats; source [frame][VIEWS][63][2], T [frame][VIEWS][2][66].
-template <int VIEWS, bool U8, bool FOLD = false>
-__global__ __launch_bounds__(256) void render_average_kernel(RenderViews rv, const float* __restrict__ source,
+// Views = RenderViews, or GainViews: every sampled value scaled and clamped before the fusion sees it (a view the footprint skips
+// still contributes exactly 0).  One definition for both, and a template of the KERNEL rather than a shared device body behind thin
+// kernels: this way every instantiation keeps its machine code (LAB_NOTES.md, "Source-only changes").
+template <int VIEWS, bool U8, bool FOLD = false, typename Views>
+__global__ __launch_bounds__(256) void render_average_kernel(Views rv, const float* __restrict__ source,
                                                              const float* __restrict__ T, const float* __restrict__ fp,
                                                              float* __restrict__ out, int h, int w, int hc, int wc,
                                                              int mode, long long img_fs, long long out_fs,
@@ -546,28 +594,19 @@ __global__ __launch_bounds__(256) void render_average_kernel(RenderViews rv, con
         T += frame * (VIEWS * 2 * SS_NT);
         if (fp) fp += frame * fp_fs;
         out = reinterpret_cast<float*>(reinterpret_cast<char*>(out) + frame * out_fs);
-#pragma unroll
-        for (int k = 0; k < VIEWS; ++k)
-            rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + frame * img_fs);
+        views_to_frame<VIEWS>(rv, frame, img_fs);
     }
     unsigned char* const out8 = reinterpret_cast<unsigned char*>(out);
     // workgroup = 64 x 8 canvas pixels; wave w owns rows w and w + 4 of the tile and evaluates, for every view that
     // reaches the tile, that view's spline at its 64 columns of both rows (packed over the rows)
     const int lx = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const long long hw = (long long)h * w, ohw = (long long)hc * wc;
-    const int ny = (hc + 7) / 8 + 1, nx = 2 * ((wc + 63) / 64) + 1, nbx = (nx - 1) / 2;
     int tbx, tby;
-    unsigned mask;
-    if (fp) {                                       // tile and its view set from the frame's order table (longest first)
-        const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)render_tile_entry(fp, VIEWS, ny, nx, blockIdx.x));
-        tbx = (int)(e & 0xFFFu); tby = (int)((e >> 12) & 0xFFFu); mask = e >> 24;
-    } else {
-        tby = blockIdx.x / nbx; tbx = blockIdx.x - tby * nbx; mask = (1u << VIEWS) - 1u;
-    }
+    unsigned mask = render_tile<VIEWS>(fp, hc, wc, tbx, tby);
     const int x = tbx * 64 + lx;
 #ifdef SS_TUNING
     if ((mode >> 8) == 9) mask = ((tbx + tby) & 1) ? 3u : 1u;          // checkerboard of single / both
-    else if ((mode >> 8) == 10) mask = (tbx < nbx / 2) ? 1u : 3u;        // left half single, right half both
+    else if ((mode >> 8) == 10) mask = (tbx < (wc + 63) / 64 / 2) ? 1u : 3u;        // left half single, right half both
     else if (mode >> 8) mask = (unsigned)(mode >> 8) - 1u;          // forced tile class (timing experiments)
     mode &= 0xFF;
 #endif
@@ -613,105 +652,10 @@ __global__ __launch_bounds__(256) void render_average_kernel(RenderViews rv, con
                 sample3(rv.img[k], px.x, py.x, w, h, hw, mode, va[k]);
                 sample3(rv.img[k], px.y, py.y, w, h, hw, mode, vb[k]);
             }
-        } else {
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) { va[k][ch] = 0.f; vb[k][ch] = 0.f; }
-        }
-    }
-    if (!xin) return;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        // the chained fusion in the reference's order ((1 (+) 2) (+) 3), zeros in the places of views that do not reach
-        float fa = avg_fuse(va[0][ch], va[1][ch]), fb = avg_fuse(vb[0][ch], vb[1][ch]);
-        if (VIEWS == 3) { fa = avg_fuse(fa, va[2][ch]); fb = avg_fuse(fb, vb[2][ch]); }
-        if (U8) {
-            out8[((long long)ya * wc + x) * 3 + ch] = render_to_u8(fa);
-            if (yb < hc) out8[((long long)yb * wc + x) * 3 + ch] = render_to_u8(fb);
-        } else {
-            out[ch * ohw + (long long)ya * wc + x] = fa;
-            if (yb < hc) out[ch * ohw + (long long)yb * wc + x] = fb;
-        }
-    }
-}
-
-// The same render with exposure gains (GainViews): the kernel above, every sampled value scaled and clamped before the fusion sees it;
-// a view the footprint skips still contributes exactly 0.  (A copy, not a shared body: the kernels above keep their machine code.)
-template <int VIEWS, bool U8>
-__global__ __launch_bounds__(256) void render_average_kernel(GainViews rv, const float* __restrict__ source,
-                                                             const float* __restrict__ T, const float* __restrict__ fp,
-                                                             float* __restrict__ out, int h, int w, int hc, int wc,
-                                                             int mode, long long img_fs, long long out_fs,
-                                                             long long fp_fs) {
-    {
-        const long long frame = blockIdx.y;
-        source += frame * (VIEWS * SS_NV * 2);
-        T += frame * (VIEWS * 2 * SS_NT);
-        if (fp) fp += frame * fp_fs;
-        out = reinterpret_cast<float*>(reinterpret_cast<char*>(out) + frame * out_fs);
-#pragma unroll
-        for (int k = 0; k < VIEWS; ++k)
-            rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + frame * img_fs);
-        rv.gains += frame * (VIEWS * 3);
-    }
-    unsigned char* const out8 = reinterpret_cast<unsigned char*>(out);
-    // workgroup = 64 x 8 canvas pixels; wave w owns rows w and w + 4 of the tile and evaluates, for every view that
-    // reaches the tile, that view's spline at its 64 columns of both rows (packed over the rows)
-    const int lx = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long long hw = (long long)h * w, ohw = (long long)hc * wc;
-    const int ny = (hc + 7) / 8 + 1, nx = 2 * ((wc + 63) / 64) + 1, nbx = (nx - 1) / 2;
-    int tbx, tby;
-    unsigned mask;
-    if (fp) {                                       // tile and its view set from the frame's order table (longest first)
-        const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)render_tile_entry(fp, VIEWS, ny, nx, blockIdx.x));
-        tbx = (int)(e & 0xFFFu); tby = (int)((e >> 12) & 0xFFFu); mask = e >> 24;
-    } else {
-        tby = blockIdx.x / nbx; tbx = blockIdx.x - tby * nbx; mask = (1u << VIEWS) - 1u;
-    }
-    const int x = tbx * 64 + lx;
-    const int ya = tby * 8 + wv, yb = ya + 4;
-    if (tbx * 64 >= wc || ya >= hc) return;       // (whole waves only: the lanes past the canvas edge still help build the table)
-    const bool xin = x < wc;
-    const float gx = linspace_at(-1.f, 1.f, wc, min(x, wc - 1));
-    if (mask == 0u) {                               // no view reaches this tile: avg_fuse(0, 0) = 0
-        if (xin) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                if (U8) {
-                    out8[((long long)ya * wc + x) * 3 + ch] = 0;
-                    if (yb < hc) out8[((long long)yb * wc + x) * 3 + ch] = 0;
-                } else {
-                    out[ch * ohw + (long long)ya * wc + x] = 0.f;
-                    if (yb < hc) out[ch * ohw + (long long)yb * wc + x] = 0.f;
-                }
+            if constexpr (std::is_same<Views, GainViews>::value) {
+                apply_gains(rv.gains + k * 3, va[k]);
+                apply_gains(rv.gains + k * 3, vb[k]);
             }
-        }
-        return;
-    }
-    // every view that reaches the tile: its spline at this lane's column of the wave's two rows (packed over the rows);
-    // the row-only part of the radial terms comes from a per-wave LDS table (tps_rows_table)
-    __shared__ ss_f2 dytab[4][VIEWS][64];
-    const float gya = linspace_at(-1.f, 1.f, hc, ya), gyb = linspace_at(-1.f, 1.f, hc, min(yb, hc - 1));
-#pragma unroll
-    for (int k = 0; k < VIEWS; ++k)
-        if (mask & (1u << k)) tps_rows_table(source + k * SS_NV * 2, gya, gyb, lx, dytab[wv][k]);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // same wave reads it back: ordering only, no barrier
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    float va[VIEWS][3], vb[VIEWS][3];
-#pragma unroll
-    for (int k = 0; k < VIEWS; ++k) {
-        if (mask & (1u << k)) {
-            ss_f2 px, py;
-            tps_eval_rows(source + k * SS_NV * 2, T + k * 2 * SS_NT, dytab[wv][k], gx, gya, gyb, px, py);
-            if (U8) {
-                const unsigned char* img8 = reinterpret_cast<const unsigned char*>(rv.img[k]);
-                sample3_u8(img8, px.x, py.x, w, h, mode, va[k]);
-                sample3_u8(img8, px.y, py.y, w, h, mode, vb[k]);
-            } else {
-                sample3(rv.img[k], px.x, py.x, w, h, hw, mode, va[k]);
-                sample3(rv.img[k], px.y, py.y, w, h, hw, mode, vb[k]);
-            }
-            apply_gains(rv.gains + k * 3, va[k]);
-            apply_gains(rv.gains + k * 3, vb[k]);
         } else {
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) { va[k][ch] = 0.f; vb[k][ch] = 0.f; }
@@ -750,48 +694,31 @@ static int render_average_launch(const void* const* imgs, const float* source, c
     // order with this geometry, so a row of another size is an argument error, not an out-of-bounds read
     const long long fp_fs = ss_render_footprint_floats(views, hc, wc);
     if (footprint && footprint_floats != fp_fs) return SS_ERR_ARG;
-    RenderViews rv;
-    for (int i = 0; i < 3; ++i) rv.img[i] = i < views ? static_cast<const float*>(imgs[i]) : nullptr;
-    for (int i = 0; i < views; ++i)
-        if (!rv.img[i]) return SS_ERR_ARG;
+    GainViews gv;
+    if (!views_make(gv, imgs, views, gains)) return SS_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     // grid.y = frame; HIP caps grid.y at 65535: longer clips go in several launches
     for (int f0 = 0; f0 < frames; f0 += 65535) {
         const int nf = frames - f0 < 65535 ? frames - f0 : 65535;
         dim3 g(ss_cdiv(wc, 64) * ss_cdiv(hc, 8), nf, 1);
-        RenderViews r = rv;
+        GainViews r = gv;
         for (int i = 0; i < views; ++i)
-            r.img[i] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[i]) + (long long)f0 * img_fs);
+            r.img[i] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(gv.img[i]) + (long long)f0 * img_fs);
+        if (with_gains) r.gains = gains + (long long)f0 * views * 3;
         const float* s_ = source + (long long)f0 * views * SS_NV * 2;
         const float* t_ = T + (long long)f0 * views * 2 * SS_NT;
         const float* p_ = footprint ? footprint + (long long)f0 * fp_fs : nullptr;
         float* o = reinterpret_cast<float*>(static_cast<char*>(out) + (long long)f0 * out_fs);
-        if (with_gains) {
-            GainViews gv;
-            for (int i = 0; i < 3; ++i) gv.img[i] = r.img[i];
-            gv.gains = gains + (long long)f0 * views * 3;
-            if (views == 2) {
-                if (u8) render_average_kernel<2, true><<<g, dim3(256), 0, st>>>(gv, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-                else render_average_kernel<2, false><<<g, dim3(256), 0, st>>>(gv, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-            } else {
-                if (u8) render_average_kernel<3, true><<<g, dim3(256), 0, st>>>(gv, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-                else render_average_kernel<3, false><<<g, dim3(256), 0, st>>>(gv, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-            }
-        } else if (fold) {        // opt-in: the reference's + 1e-6 folded into the row table (not its arithmetic; see device_math.h)
-            if (views == 2) {
-                if (u8) hipLaunchKernelGGL((render_average_kernel<2, true, true>), g, dim3(256), 0, st, r, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-                else hipLaunchKernelGGL((render_average_kernel<2, false, true>), g, dim3(256), 0, st, r, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-            } else {
-                if (u8) hipLaunchKernelGGL((render_average_kernel<3, true, true>), g, dim3(256), 0, st, r, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-                else hipLaunchKernelGGL((render_average_kernel<3, false, true>), g, dim3(256), 0, st, r, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-            }
-        } else if (views == 2) {
-            if (u8) hipLaunchKernelGGL((render_average_kernel<2, true>), g, dim3(256), 0, st, r, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-            else hipLaunchKernelGGL((render_average_kernel<2, false>), g, dim3(256), 0, st, r, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-        } else {
-            if (u8) hipLaunchKernelGGL((render_average_kernel<3, true>), g, dim3(256), 0, st, r, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-            else hipLaunchKernelGGL((render_average_kernel<3, false>), g, dim3(256), 0, st, r, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
-        }
+        with_views(views, u8, [&](auto V, auto U8) {
+            auto launch = [&](auto rv, auto FOLD) {
+                render_average_kernel<decltype(V)::value, decltype(U8)::value, decltype(FOLD)::value>
+                    <<<g, dim3(256), 0, st>>>(rv, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
+            };
+            // (fold: opt-in, the reference's + 1e-6 folded into the row table -- not its arithmetic; see device_math.h)
+            if (with_gains) launch(r, std::false_type{});
+            else if (fold) launch(RenderViews(r), std::true_type{});
+            else launch(RenderViews(r), std::false_type{});
+        });
     }
     return ss_launch_status();
 }
@@ -829,19 +756,11 @@ __global__ __launch_bounds__(256) void render_average_kernel(Nv12Views nv, const
         if (fp) fp += frame * fp_fs;
         out8 += frame * out_fs;
         if (NV12OUT) out_uv += frame * out_fs;
-#pragma unroll
-        for (int k = 0; k < VIEWS; ++k) { nv.y[k] += frame * nv.fs[k]; nv.uv[k] += frame * nv.fs[k]; }
+        views_to_frame<VIEWS>(nv, frame);
     }
     const int lx = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int ny = (hc + 7) / 8 + 1, nx = 2 * ((wc + 63) / 64) + 1, nbx = (nx - 1) / 2;
     int tbx, tby;
-    unsigned mask;
-    if (fp) {                                       // tile and its view set from the frame's order table (longest first)
-        const unsigned e = (unsigned)__builtin_amdgcn_readfirstlane((int)render_tile_entry(fp, VIEWS, ny, nx, blockIdx.x));
-        tbx = (int)(e & 0xFFFu); tby = (int)((e >> 12) & 0xFFFu); mask = e >> 24;
-    } else {
-        tby = blockIdx.x / nbx; tbx = blockIdx.x - tby * nbx; mask = (1u << VIEWS) - 1u;
-    }
+    unsigned mask = render_tile<VIEWS>(fp, hc, wc, tbx, tby);
     const int x = tbx * 64 + lx;
     const int ya = tby * 8 + 2 * wv, yb = ya + 1;
     if (tbx * 64 >= wc || ya >= hc) return;       // (whole waves only: the lanes past the canvas edge still help build the table)
@@ -933,13 +852,10 @@ extern "C" int ss_render_average_nv12(const unsigned char* const* y, const unsig
     if (footprint && footprint_floats != fp_fs) return SS_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const dim3 g(ss_cdiv(wc, 64) * ss_cdiv(hc, 8), 1, 1);
-    if (views == 2) {
-        if (out_format) render_average_kernel<2, true><<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
-        else render_average_kernel<2, false><<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
-    } else {
-        if (out_format) render_average_kernel<3, true><<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
-        else render_average_kernel<3, false><<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
-    }
+    with_views(views, out_format == 1, [&](auto V, auto NV12OUT) {
+        render_average_kernel<decltype(V)::value, decltype(NV12OUT)::value>
+            <<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
+    });
     return ss_launch_status();
 }
 
@@ -1239,13 +1155,7 @@ extern "C" int ss_exposure_update(const void* const* views_base, int u8, long lo
     for (int phase = 0; phase < (frames > 1 ? 2 : 1); ++phase) {
         a.phase = phase;
         const dim3 g(phase ? 1 : frames), b(phase ? 64 : 256);
-        if (views == 2) {
-            if (u8) render_lattice_kernel<2, true><<<g, b, 0, st>>>(a);
-            else render_lattice_kernel<2, false><<<g, b, 0, st>>>(a);
-        } else {
-            if (u8) render_lattice_kernel<3, true><<<g, b, 0, st>>>(a);
-            else render_lattice_kernel<3, false><<<g, b, 0, st>>>(a);
-        }
+        with_views(views, u8 != 0, [&](auto V, auto U8) { render_lattice_kernel<decltype(V)::value, decltype(U8)::value><<<g, b, 0, st>>>(a); });
     }
     return ss_launch_status();
 }
@@ -1590,33 +1500,14 @@ __device__ __forceinline__ void lb_warp_tile(Views rv, const float* __restrict__
     }
 }
 
-template <int VIEWS, bool U8>
-__global__ __launch_bounds__(256) void lb_clip_warp_kernel(RenderViews rv, const float* __restrict__ source,
+template <int VIEWS, bool U8, typename Views>
+__global__ __launch_bounds__(256) void lb_clip_warp_kernel(Views rv, const float* __restrict__ source,
                                                            const float* __restrict__ T, float* __restrict__ W,
                                                            unsigned* __restrict__ partials, int h, int w, int hc, int wc,
                                                            int mode, long long img_fs) {
     constexpr int P = VIEWS - 1;
     const long long frame = blockIdx.y;
-#pragma unroll
-    for (int k = 0; k < VIEWS; ++k)
-        rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + frame * img_fs);
-    lb_warp_tile<VIEWS, U8>(rv, source + frame * (VIEWS * SS_NV * 2), T + frame * (VIEWS * 2 * SS_NT),
-                            W + frame * (VIEWS * 4) * ((long long)hc * wc),
-                            partials + ((frame * gridDim.x + blockIdx.x) * 4) * (P * LBC_PW), blockIdx.x, h, w, hc, wc, mode);
-}
-
-// the same with exposure gains [frames][VIEWS][3]
-template <int VIEWS, bool U8>
-__global__ __launch_bounds__(256) void lb_clip_warp_kernel(GainViews rv, const float* __restrict__ source,
-                                                           const float* __restrict__ T, float* __restrict__ W,
-                                                           unsigned* __restrict__ partials, int h, int w, int hc, int wc,
-                                                           int mode, long long img_fs) {
-    constexpr int P = VIEWS - 1;
-    const long long frame = blockIdx.y;
-#pragma unroll
-    for (int k = 0; k < VIEWS; ++k)
-        rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + frame * img_fs);
-    rv.gains += frame * (VIEWS * 3);
+    views_to_frame<VIEWS>(rv, frame, img_fs);
     lb_warp_tile<VIEWS, U8>(rv, source + frame * (VIEWS * SS_NV * 2), T + frame * (VIEWS * 2 * SS_NT),
                             W + frame * (VIEWS * 4) * ((long long)hc * wc),
                             partials + ((frame * gridDim.x + blockIdx.x) * 4) * (P * LBC_PW), blockIdx.x, h, w, hc, wc, mode);
@@ -1939,10 +1830,8 @@ static int render_linear_clip_launch(const void* const* views_base, const float*
     if (!views_base || !source || !T || !out || !ws || frames <= 0 || frames > 65535 || (views != 2 && views != 3) || h <= 1 ||
         w <= 1 || hc < 11 || wc < 11 || wc > 65535 || hc > 65535 || (mode != SS_WARP_NORMAL && mode != SS_WARP_FAST))
         return SS_ERR_ARG;
-    RenderViews rv;
-    for (int i = 0; i < 3; ++i) rv.img[i] = i < views ? static_cast<const float*>(views_base[i]) : nullptr;
-    for (int i = 0; i < views; ++i)
-        if (!rv.img[i]) return SS_ERR_ARG;
+    GainViews gv;
+    if (!views_make(gv, views_base, views, gains)) return SS_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const long long ohw = (long long)hc * wc;
     const int P = views - 1, nbx = ss_cdiv(wc, 64), tiles = nbx * ss_cdiv(hc, 8);
@@ -1955,24 +1844,13 @@ static int render_linear_clip_launch(const void* const* views_base, const float*
     unsigned* partials = reinterpret_cast<unsigned*>(scalars + (long long)frames * P * 16);
     const long long img_fs = u8 ? 3ll * h * w : 12ll * h * w;
     const dim3 ga(tiles, frames);
-    if (with_gains) {
-        GainViews gv;
-        for (int i = 0; i < 3; ++i) gv.img[i] = rv.img[i];
-        gv.gains = gains;
-        if (views == 2) {
-            if (u8) lb_clip_warp_kernel<2, true><<<ga, dim3(256), 0, st>>>(gv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
-            else lb_clip_warp_kernel<2, false><<<ga, dim3(256), 0, st>>>(gv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
-        } else {
-            if (u8) lb_clip_warp_kernel<3, true><<<ga, dim3(256), 0, st>>>(gv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
-            else lb_clip_warp_kernel<3, false><<<ga, dim3(256), 0, st>>>(gv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
-        }
-    } else if (views == 2) {
-        if (u8) hipLaunchKernelGGL((lb_clip_warp_kernel<2, true>), ga, dim3(256), 0, st, rv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
-        else hipLaunchKernelGGL((lb_clip_warp_kernel<2, false>), ga, dim3(256), 0, st, rv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
-    } else {
-        if (u8) hipLaunchKernelGGL((lb_clip_warp_kernel<3, true>), ga, dim3(256), 0, st, rv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
-        else hipLaunchKernelGGL((lb_clip_warp_kernel<3, false>), ga, dim3(256), 0, st, rv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
-    }
+    auto warp = [&](auto rv) {
+        with_views(views, u8, [&](auto V, auto U8) {
+            lb_clip_warp_kernel<decltype(V)::value, decltype(U8)::value>
+                <<<ga, dim3(256), 0, st>>>(rv, source, T, W, partials, h, w, hc, wc, mode, img_fs);
+        });
+    };
+    if (with_gains) warp(gv); else warp(RenderViews(gv));
     hipLaunchKernelGGL(lb_clip_reduce_kernel, dim3(frames * P), dim3(256), 0, st, (const unsigned*)partials, scalars, tiles, nbx, P);
     const Gauss21 g = lb_gauss();
     const dim3 gc(ss_cdiv(wc, LBC_T), ss_cdiv(hc, LBC_T), frames);
@@ -1987,32 +1865,25 @@ static int render_linear_clip_launch(const void* const* views_base, const float*
     a.m1a = W + 3 * ohw; a.m1b = nullptr; a.m2 = W + 7 * ohw;
     a.mask1_out = mask1_out; a.mask1_fs = P * ohw;
     a.scalars = scalars; a.sc_fs = P * 16;
+    auto blend = [&](bool second_pass, bool u8out) {      // a's pass: the rolling form, or the 64 x 64-tile one
+        with_flags(second_pass, u8out, [&](auto UNION, auto U8OUT) {
+            if (rolling) lb_clip_blend_rows_kernel<decltype(UNION)::value, decltype(U8OUT)::value><<<gr, dim3(64), 0, st>>>(a, hc, wc, rs, g);
+            else lb_clip_blend_kernel<decltype(UNION)::value, decltype(U8OUT)::value><<<gc, dim3(256), 0, st>>>(a, hc, wc, g);
+        });
+    };
     if (views == 2) {
         a.out = static_cast<float*>(out);
-        if (rolling) {
-            if (u8) hipLaunchKernelGGL((lb_clip_blend_rows_kernel<false, true>), gr, dim3(64), 0, st, a, hc, wc, rs, g);
-            else hipLaunchKernelGGL((lb_clip_blend_rows_kernel<false, false>), gr, dim3(64), 0, st, a, hc, wc, rs, g);
-        } else {
-            if (u8) hipLaunchKernelGGL((lb_clip_blend_kernel<false, true>), gc, dim3(256), 0, st, a, hc, wc, g);
-            else hipLaunchKernelGGL((lb_clip_blend_kernel<false, false>), gc, dim3(256), 0, st, a, hc, wc, g);
-        }
+        blend(false, u8);
     } else {
         a.out = F;
-        if (rolling) hipLaunchKernelGGL((lb_clip_blend_rows_kernel<false, false>), gr, dim3(64), 0, st, a, hc, wc, rs, g);
-        else hipLaunchKernelGGL((lb_clip_blend_kernel<false, false>), gc, dim3(256), 0, st, a, hc, wc, g);
+        blend(false, false);
         a.ref = F; a.ref_fs = 3 * ohw;
         a.tgt = W + 8 * ohw;
         a.m1b = W + 7 * ohw; a.m2 = W + 11 * ohw;
         a.mask1_out = mask1_out ? mask1_out + ohw : nullptr;
         a.scalars = scalars + 16;
         a.out = static_cast<float*>(out);
-        if (rolling) {
-            if (u8) hipLaunchKernelGGL((lb_clip_blend_rows_kernel<true, true>), gr, dim3(64), 0, st, a, hc, wc, rs, g);
-            else hipLaunchKernelGGL((lb_clip_blend_rows_kernel<true, false>), gr, dim3(64), 0, st, a, hc, wc, rs, g);
-        } else {
-            if (u8) hipLaunchKernelGGL((lb_clip_blend_kernel<true, true>), gc, dim3(256), 0, st, a, hc, wc, g);
-            else hipLaunchKernelGGL((lb_clip_blend_kernel<true, false>), gc, dim3(256), 0, st, a, hc, wc, g);
-        }
+        blend(true, u8);
     }
     return ss_launch_status();
 }
@@ -2091,41 +1962,22 @@ extern "C" long long ss_linear_frames_workspace_floats(int frames, int views, co
     return total;
 }
 
-template <int VIEWS, bool U8>
-__global__ __launch_bounds__(256) void lb_frames_warp_kernel(RenderViews rv, const float* __restrict__ source,
+template <int VIEWS, bool U8, typename Views>
+__global__ __launch_bounds__(256) void lb_frames_warp_kernel(Views rv, const float* __restrict__ source,
                                                              const float* __restrict__ T, float* __restrict__ ws,
                                                              unsigned* __restrict__ partials, int h, int w, int mode,
                                                              long long img_fs, LbFrameTab t) {
     constexpr int P = VIEWS - 1;
     const int f = lb_frame_of(t.tile0, t.n, blockIdx.x);
     const unsigned tile = blockIdx.x - t.tile0[f];
-#pragma unroll
-    for (int k = 0; k < VIEWS; ++k)
-        rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + (long long)f * img_fs);
+    views_to_frame<VIEWS>(rv, f, img_fs);
     lb_warp_tile<VIEWS, U8>(rv, source + (long long)f * (VIEWS * SS_NV * 2), T + (long long)f * (VIEWS * 2 * SS_NT),
                             ws + t.w_off[f], partials + t.part_off[f] + ((long long)tile * 4) * (P * LBC_PW), tile, h, w,
                             (int)t.hc[f], (int)t.wc[f], mode);
 }
 
-// the same with exposure gains [frames][VIEWS][3]
-template <int VIEWS, bool U8>
-__global__ __launch_bounds__(256) void lb_frames_warp_kernel(GainViews rv, const float* __restrict__ source,
-                                                             const float* __restrict__ T, float* __restrict__ ws,
-                                                             unsigned* __restrict__ partials, int h, int w, int mode,
-                                                             long long img_fs, LbFrameTab t) {
-    constexpr int P = VIEWS - 1;
-    const int f = lb_frame_of(t.tile0, t.n, blockIdx.x);
-    const unsigned tile = blockIdx.x - t.tile0[f];
-#pragma unroll
-    for (int k = 0; k < VIEWS; ++k)
-        rv.img[k] = reinterpret_cast<const float*>(reinterpret_cast<const char*>(rv.img[k]) + (long long)f * img_fs);
-    rv.gains += (long long)f * (VIEWS * 3);
-    lb_warp_tile<VIEWS, U8>(rv, source + (long long)f * (VIEWS * SS_NV * 2), T + (long long)f * (VIEWS * 2 * SS_NT),
-                            ws + t.w_off[f], partials + t.part_off[f] + ((long long)tile * 4) * (P * LBC_PW), tile, h, w,
-                            (int)t.hc[f], (int)t.wc[f], mode);
-}
-
-// the same from decoded NV12 frames (frame f of view k at y[k] / uv[k] + f * fs[k])
+// the same from decoded NV12 frames (frame f of view k at y[k] / uv[k] + f * fs[k]); an overload of its own: the descriptor carries
+// its frame strides, so the kernel has no img_fs argument (with one, its instruction stream changes: LAB_NOTES.md, "Source-only changes")
 template <int VIEWS>
 __global__ __launch_bounds__(256) void lb_frames_warp_kernel(Nv12Views nv, const float* __restrict__ source,
                                                              const float* __restrict__ T, float* __restrict__ ws,
@@ -2133,8 +1985,7 @@ __global__ __launch_bounds__(256) void lb_frames_warp_kernel(Nv12Views nv, const
     constexpr int P = VIEWS - 1;
     const int f = lb_frame_of(t.tile0, t.n, blockIdx.x);
     const unsigned tile = blockIdx.x - t.tile0[f];
-#pragma unroll
-    for (int k = 0; k < VIEWS; ++k) { nv.y[k] += (long long)f * nv.fs[k]; nv.uv[k] += (long long)f * nv.fs[k]; }
+    views_to_frame<VIEWS>(nv, f);
     lb_warp_tile<VIEWS, true>(nv, source + (long long)f * (VIEWS * SS_NV * 2), T + (long long)f * (VIEWS * 2 * SS_NT),
                               ws + t.w_off[f], partials + t.part_off[f] + ((long long)tile * 4) * (P * LBC_PW), tile, h, w,
                               (int)t.hc[f], (int)t.wc[f], mode);
@@ -2188,10 +2039,8 @@ static int render_linear_frames_launch(const void* const* views_base, const floa
         h <= 1 || w <= 1 || (mode != SS_WARP_NORMAL && mode != SS_WARP_FAST))
         return SS_ERR_ARG;
     if (reinterpret_cast<unsigned long long>(ws) & 7ull) return SS_ERR_ARG;
-    RenderViews rv;
-    for (int i = 0; i < 3; ++i) rv.img[i] = i < views && !nv12 ? static_cast<const float*>(views_base[i]) : nullptr;
-    for (int i = 0; i < views; ++i)
-        if (!rv.img[i] && !nv12) return SS_ERR_ARG;
+    GainViews gv = {};
+    if (!nv12 && !views_make(gv, views_base, views, gains)) return SS_ERR_ARG;
     const int P = views - 1;
     // rolling blend only (the 64 x 64-tile form of ss_linear_clip_set_rows(r < 0) does not exist here: default strip height)
     const int rs = g_lb_rows > 0 ? g_lb_rows : 96;
@@ -2223,37 +2072,29 @@ static int render_linear_frames_launch(const void* const* views_base, const floa
     hipStream_t st = (hipStream_t)stream;
     const long long img_fs = u8 ? 3ll * h * w : 12ll * h * w;
     const dim3 ga(t.tile0[frames]), gr(t.strip0[frames]);
-    if (nv12) {
-        if (views == 2) lb_frames_warp_kernel<2><<<ga, dim3(256), 0, st>>>(*nv12, source, T, ws, partials, h, w, mode, t);
-        else lb_frames_warp_kernel<3><<<ga, dim3(256), 0, st>>>(*nv12, source, T, ws, partials, h, w, mode, t);
-    } else if (with_gains) {
-        GainViews gv;
-        for (int i = 0; i < 3; ++i) gv.img[i] = rv.img[i];
-        gv.gains = gains;
-        if (views == 2) {
-            if (u8) lb_frames_warp_kernel<2, true><<<ga, dim3(256), 0, st>>>(gv, source, T, ws, partials, h, w, mode, img_fs, t);
-            else lb_frames_warp_kernel<2, false><<<ga, dim3(256), 0, st>>>(gv, source, T, ws, partials, h, w, mode, img_fs, t);
-        } else {
-            if (u8) lb_frames_warp_kernel<3, true><<<ga, dim3(256), 0, st>>>(gv, source, T, ws, partials, h, w, mode, img_fs, t);
-            else lb_frames_warp_kernel<3, false><<<ga, dim3(256), 0, st>>>(gv, source, T, ws, partials, h, w, mode, img_fs, t);
-        }
-    } else if (views == 2) {
-        if (u8) hipLaunchKernelGGL((lb_frames_warp_kernel<2, true>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
-        else hipLaunchKernelGGL((lb_frames_warp_kernel<2, false>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
-    } else {
-        if (u8) hipLaunchKernelGGL((lb_frames_warp_kernel<3, true>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
-        else hipLaunchKernelGGL((lb_frames_warp_kernel<3, false>), ga, dim3(256), 0, st, rv, source, T, ws, partials, h, w, mode, img_fs, t);
-    }
+    auto warp = [&](auto rv) {
+        with_views(views, u8, [&](auto V, auto U8) {
+            if constexpr (std::is_same<decltype(rv), Nv12Views>::value)
+                lb_frames_warp_kernel<decltype(V)::value><<<ga, dim3(256), 0, st>>>(rv, source, T, ws, partials, h, w, mode, t);
+            else
+                lb_frames_warp_kernel<decltype(V)::value, decltype(U8)::value>
+                    <<<ga, dim3(256), 0, st>>>(rv, source, T, ws, partials, h, w, mode, img_fs, t);
+        });
+    };
+    if (nv12) warp(*nv12); else if (with_gains) warp(gv); else warp(RenderViews(gv));
     hipLaunchKernelGGL(lb_frames_reduce_kernel, dim3(frames * P), dim3(256), 0, st, (const unsigned*)partials, scalars, P, t);
     const Gauss21 g = lb_gauss();
     const unsigned long long* sc = scalars;
+    auto blend = [&](bool second_pass, bool u8out) {
+        with_flags(second_pass, u8out, [&](auto UNION, auto U8OUT) {
+            lb_frames_blend_rows_kernel<decltype(UNION)::value, decltype(U8OUT)::value><<<gr, dim3(64), 0, st>>>(ws, sc, views, rs, g, t);
+        });
+    };
     if (views == 2) {
-        if (u8) hipLaunchKernelGGL((lb_frames_blend_rows_kernel<false, true>), gr, dim3(64), 0, st, ws, sc, views, rs, g, t);
-        else hipLaunchKernelGGL((lb_frames_blend_rows_kernel<false, false>), gr, dim3(64), 0, st, ws, sc, views, rs, g, t);
+        blend(false, u8);
     } else {
-        hipLaunchKernelGGL((lb_frames_blend_rows_kernel<false, false>), gr, dim3(64), 0, st, ws, sc, views, rs, g, t);
-        if (u8) hipLaunchKernelGGL((lb_frames_blend_rows_kernel<true, true>), gr, dim3(64), 0, st, ws, sc, views, rs, g, t);
-        else hipLaunchKernelGGL((lb_frames_blend_rows_kernel<true, false>), gr, dim3(64), 0, st, ws, sc, views, rs, g, t);
+        blend(false, false);
+        blend(true, u8);
     }
     return ss_launch_status();
 }

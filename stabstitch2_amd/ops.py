@@ -919,26 +919,44 @@ def _gains(gains, n, v):
     return H.dptr(gains)
 
 
+def _render_average(views, source, T, hc, wc, mode, out, footprint, gains, u8, clip):
+    """The four render_average* below, and with gains= their _gains entries.  u8: decoded uint8 frames [..,h,w,3] -> uint8 [..,hc,wc,3]
+    instead of fp32 planes [..,3,h,w] -> [..,3,hc,wc]; clip: a leading frame axis n on views, source, T, footprint and out."""
+    v = len(views)
+    dt = torch.uint8 if u8 else torch.float32
+    if not u8 and not clip:
+        views = [_f(i) for i in views]
+    h, w = views[0].shape[-3:-1] if u8 else views[0].shape[-2:]
+    n = views[0].shape[0] if clip else 1
+    if clip:
+        assert all(tuple(t.shape) == ((n, h, w, 3) if u8 else (n, 3, h, w)) for t in views) and source.shape[0] == n and T.shape[0] == n
+    arr = H.ptr_array(views, dtype=dt)
+    shape = ((n,) if clip else ()) + ((hc, wc, 3) if u8 else (3, hc, wc))
+    if out is None:
+        out = torch.empty(shape, device=views[0].device, dtype=dt)
+    assert not clip or tuple(out.shape) == shape
+    if clip:                             # the footprint's size: one row of the clip's [n, row] block
+        fp, fpn = H.dptr(footprint, True), (0 if footprint is None else footprint.shape[-1])
+    else:                                # all of what the single frame was handed
+        fp, fpn = _fp_args(footprint)
+    name = 'ss_render_average' + ('_clip' if clip else '') + ('_u8' if u8 else '')
+    outp = _u8ptr(out) if u8 else H.dptr(out)
+    frames = (n,) if clip else ()        # the clip entries take the frame count in front of the view count
+    args = (arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, outp) + frames + (v, h, w, hc, wc)
+    if gains is not None:                # exposure gains [n,V,3] (exposure_update): sampled values scaled and clamped to 255;
+        H.call(name + '_gains', *args, MODES[mode], _gains(gains, n, v), H.stream())      # (these entries have no folded variant)
+    else:
+        H.call(name, *args, _avg_mode(mode), H.stream())
+    return out
+
+
 def render_average(imgs, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
     """imgs: list of 2|3 device tensors [1,3,h,w] / [3,h,w]; source [V,63,2]; T [V,2,66] -> [3,hc,wc].
     footprint: this frame's row of `render_footprints` (views that cannot reach a tile are skipped there and count as
     exactly 0 -- a deliberate deviation from the reference, whose clamped sampler returns a rounding residue of up to
     ~1e-2 grey levels outside a view's image; the skip test samples each 64 x 8 tile at six points and is not a proof),
     or None (every view evaluated everywhere: the reference's arithmetic at every pixel)."""
-    v = len(imgs)
-    imgs = [_f(i) for i in imgs]
-    h, w = imgs[0].shape[-2:]
-    arr = H.ptr_array(imgs)
-    if out is None:
-        out = torch.empty((3, hc, wc), device=imgs[0].device, dtype=torch.float32)
-    fp, fpn = _fp_args(footprint)
-    if gains is not None:                # exposure gains [V,3] (exposure_update): sampled values scaled and clamped to 255
-        H.call('ss_render_average_gains', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, H.dptr(out), v, h, w, hc, wc,
-               MODES[mode], _gains(gains, 1, v), H.stream())
-        return out
-    H.call('ss_render_average', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, H.dptr(out), v, h, w, hc, wc,
-           _avg_mode(mode), H.stream())
-    return out
+    return _render_average(imgs, source, T, hc, wc, mode, out, footprint, gains, u8=False, clip=False)
 
 
 def render_average_u8(frames, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
@@ -946,58 +964,18 @@ def render_average_u8(frames, source, T, hc, wc, mode='NORMAL', out=None, footpr
     tensors [h,w,3] uint8 (cv2 channel order); -> uint8 [hc,wc,3] = `.astype(np.uint8)` of the fused values.  Equal,
     bit for bit, to ingest (uint8 -> fp32 planes) + render_average + canvas_to_u8; the fp32 planes and canvas are never
     written."""
-    v = len(frames)
-    h, w = frames[0].shape[0], frames[0].shape[1]
-    arr = H.ptr_array(frames, dtype=torch.uint8)
-    if out is None:
-        out = torch.empty((hc, wc, 3), device=frames[0].device, dtype=torch.uint8)
-    fp, fpn = _fp_args(footprint)
-    if gains is not None:
-        H.call('ss_render_average_u8_gains', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, _u8ptr(out), v, h, w, hc, wc,
-               MODES[mode], _gains(gains, 1, v), H.stream())
-        return out
-    H.call('ss_render_average_u8', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, _u8ptr(out), v, h, w, hc, wc,
-           _avg_mode(mode), H.stream())
-    return out
+    return _render_average(frames, source, T, hc, wc, mode, out, footprint, gains, u8=True, clip=False)
 
 
 def render_average_clip(views, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
     """A whole clip in one launch: views = list of 2|3 contiguous device tensors [n,3,h,w]; source [n,V,63,2];
     T [n,V,2,66]; footprint [n, ss_render_footprint_floats] | None -> [n,3,hc,wc].  Bit-identical to n render_average calls."""
-    v = len(views)
-    n, _, h, w = views[0].shape
-    assert all(tuple(t.shape) == (n, 3, h, w) for t in views) and source.shape[0] == n and T.shape[0] == n
-    arr = H.ptr_array(views)
-    if out is None:
-        out = torch.empty((n, 3, hc, wc), device=views[0].device, dtype=torch.float32)
-    assert tuple(out.shape) == (n, 3, hc, wc)
-    fp, fpn = H.dptr(footprint, True), (0 if footprint is None else footprint.shape[-1])
-    if gains is not None:
-        H.call('ss_render_average_clip_gains', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, H.dptr(out), n, v, h, w, hc, wc,
-               MODES[mode], _gains(gains, n, v), H.stream())
-        return out
-    H.call('ss_render_average_clip', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, H.dptr(out), n, v, h, w, hc, wc,
-           _avg_mode(mode), H.stream())
-    return out
+    return _render_average(views, source, T, hc, wc, mode, out, footprint, gains, u8=False, clip=True)
 
 
 def render_average_clip_u8(views, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
     """The same from decoded uint8 clips: views = list of 2|3 contiguous device tensors [n,h,w,3] uint8 -> uint8 [n,hc,wc,3]."""
-    v = len(views)
-    n, h, w, _ = views[0].shape
-    assert all(tuple(t.shape) == (n, h, w, 3) for t in views) and source.shape[0] == n and T.shape[0] == n
-    arr = H.ptr_array(views, dtype=torch.uint8)
-    if out is None:
-        out = torch.empty((n, hc, wc, 3), device=views[0].device, dtype=torch.uint8)
-    assert tuple(out.shape) == (n, hc, wc, 3)
-    fp, fpn = H.dptr(footprint, True), (0 if footprint is None else footprint.shape[-1])
-    if gains is not None:
-        H.call('ss_render_average_clip_u8_gains', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, _u8ptr(out), n, v, h, w, hc, wc,
-               MODES[mode], _gains(gains, n, v), H.stream())
-        return out
-    H.call('ss_render_average_clip_u8', arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, _u8ptr(out), n, v, h, w, hc, wc,
-           _avg_mode(mode), H.stream())
-    return out
+    return _render_average(views, source, T, hc, wc, mode, out, footprint, gains, u8=True, clip=True)
 
 
 def tps_warp_views(imgs, source, T, hc, wc, mode='NORMAL'):
@@ -1203,13 +1181,10 @@ def render_linear_clip(views, source, T, hc, wc, mode='NORMAL', out=None, want_m
     assert tuple(out.shape) == shape and out.dtype == views[0].dtype
     ws = torch.empty(int(H.lib().ss_linear_clip_workspace_floats(n, v, hc, wc)), device=dev, dtype=torch.float32)
     mk = torch.empty((n, v - 1, hc, wc), device=dev, dtype=torch.float32) if want_masks else None
-    if gains is not None:                # exposure gains [n,V,3]: the colour planes scaled and clamped, the masks untouched
-        H.call('ss_render_linear_clip_u8_gains' if u8 else 'ss_render_linear_clip_gains', arr, H.dptr(_f(source)), H.dptr(T),
-               _u8ptr(out) if u8 else H.dptr(out), H.dptr(mk, True), n, v, h, w, hc, wc, MODES[mode], H.dptr(ws),
-               _gains(gains, n, v), H.stream())
-        return (out, mk) if want_masks else out
-    H.call('ss_render_linear_clip_u8' if u8 else 'ss_render_linear_clip', arr, H.dptr(_f(source)), H.dptr(T),
-           _u8ptr(out) if u8 else H.dptr(out), H.dptr(mk, True), n, v, h, w, hc, wc, MODES[mode], H.dptr(ws), H.stream())
+    # gains: exposure gains [n,V,3] -- the colour planes scaled and clamped, the masks untouched
+    H.call('ss_render_linear_clip' + ('_u8' if u8 else '') + ('' if gains is None else '_gains'), arr, H.dptr(_f(source)), H.dptr(T),
+           _u8ptr(out) if u8 else H.dptr(out), H.dptr(mk, True), n, v, h, w, hc, wc, MODES[mode], H.dptr(ws),
+           *(() if gains is None else (_gains(gains, n, v),)), H.stream())
     return (out, mk) if want_masks else out
 
 
@@ -1250,13 +1225,9 @@ def render_linear_frames(views, source, T, sizes, mode='NORMAL', outs=None, ws=N
         ws = linear_frames_workspace(sizes, v, dev)
     hcs = (ctypes.c_int * n)(*[s[0] for s in sizes])
     wcs = (ctypes.c_int * n)(*[s[1] for s in sizes])
-    if gains is not None:
-        H.call('ss_render_linear_frames_u8_gains' if u8 else 'ss_render_linear_frames_gains', H.ptr_array(views, dtype=dt),
-               H.dptr(_f(source)), H.dptr(T), H.ptr_array(outs, dtype=dt), n, v, h, w, hcs, wcs, MODES[mode], H.dptr(ws),
-               _gains(gains, n, v), H.stream())
-        return list(outs)
-    H.call('ss_render_linear_frames_u8' if u8 else 'ss_render_linear_frames', H.ptr_array(views, dtype=dt), H.dptr(_f(source)),
-           H.dptr(T), H.ptr_array(outs, dtype=dt), n, v, h, w, hcs, wcs, MODES[mode], H.dptr(ws), H.stream())
+    H.call('ss_render_linear_frames' + ('_u8' if u8 else '') + ('' if gains is None else '_gains'), H.ptr_array(views, dtype=dt),
+           H.dptr(_f(source)), H.dptr(T), H.ptr_array(outs, dtype=dt), n, v, h, w, hcs, wcs, MODES[mode], H.dptr(ws),
+           *(() if gains is None else (_gains(gains, n, v),)), H.stream())
     return list(outs)
 
 

@@ -5,6 +5,7 @@ here in numpy fp32 -- one operation after the other, as the __f*_rn intrinsics r
 boxes and extents (tests/test_gpu_viewport.py holds the kernels to this restatement bit for bit); and the kernels the library had
 before the refit arrived as new instantiations of three of them keep their machine code."""
 import ctypes
+import functools
 import os
 import re
 import sys
@@ -245,24 +246,52 @@ def test_the_three_refusals_leave_every_output_equal_to_its_input():
 
 
 # ------------------------------------------------------------------------------------------------ the old kernels keep their code
+def norm(name):
+    """A demangled kernel name as the listings compare it: without the leading `void `, and with three spellings undone that a
+    source-only change gives a kernel whose machine code stays.  A flag template whose flag = 0 form is the old plain function: `<0>`
+    dropped.  A kernel that became a template on its descriptor (the type of its first parameter): the trailing `, XxxViews`
+    template argument dropped when it equals that type.  render_average_kernel's GainViews form, once a template of its own
+    without the FOLD flag and now an instantiation of the common one: its `, false` for FOLD dropped."""
+    name = re.sub(r'^(\w+)<0>\(', r'\1(', re.sub(r'^void ', '', name))
+    name = re.sub(r'^(\w+<[^()]*?), (\w+Views)>\(\2([,)])', r'\1>(\2\3', name)
+    return re.sub(r'^(render_average_kernel<\d, \w+), false>\(GainViews,', r'\1>(GainViews,', name)
+
+
+@functools.lru_cache(maxsize=None)
+def built_digests():
+    """tools/kernel_resources.py --digest-masked of the built library, by normalised name (disassembled once for both listings)."""
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import kernel_resources as KR
+    from stabstitch2_amd import _hip
+    return {norm(k): v for k, v in KR.digests(_hip.LIB_PATH, mask_kernarg_offsets=True).items()}
+
+
+def check_listing(listing, count):
+    """The built library against a committed listing of `count` kernels: every kernel of the listing is still in the library, under
+    its normalised name, with the same instruction stream."""
+    parent = {}
+    for ln in open(os.path.join(ROOT, 'tests', 'golden', listing)):
+        digest, name = ln.rstrip('\n').split('  ', 1)
+        parent[norm(name)] = digest
+    assert len(parent) == count
+    have = built_digests()
+    assert not sorted(set(parent) - set(have)), 'kernels that left the library'
+    changed = sorted(k for k in parent if have[k] != parent[k])
+    assert not changed, 'kernels whose machine code changed: %s' % changed
+
+
 def test_kernels_from_before_the_refit_keep_their_machine_code(built_lib):
     """tools/kernel_resources.py --digest-masked on the built library against the listing taken from the library before the refit
     (tests/golden/viewport_parent_isa_digest.txt, same compiler and flags): every kernel instantiation that library had is still
     there with the same instruction stream.  The refit rides on canvas_watch_kernel, canvas_watch_frames_kernel and
     render_lattice_kernel as a compile-time flag; their flag = 0 instantiations are the kernels as they were (a name that gained
     `<0>` is the same kernel).  A later change that edits a kernel on purpose regenerates the listing with that command."""
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import kernel_resources as KR
-    from stabstitch2_amd import _hip
+    check_listing('viewport_parent_isa_digest.txt', 144)
 
-    def norm(name):
-        return re.sub(r'^(\w+)<0>\(', r'\1(', re.sub(r'^void ', '', name))
-    parent = {}
-    for ln in open(os.path.join(ROOT, 'tests', 'golden', 'viewport_parent_isa_digest.txt')):
-        digest, name = ln.rstrip('\n').split('  ', 1)
-        parent[norm(name)] = digest
-    assert len(parent) == 144
-    have = {norm(k): v for k, v in KR.digests(_hip.LIB_PATH, mask_kernarg_offsets=True).items()}
-    assert not sorted(set(parent) - set(have)), 'kernels that left the library'
-    changed = sorted(k for k in parent if have[k] != parent[k])
-    assert not changed, 'kernels whose machine code changed: %s' % changed
+
+def test_kernels_from_before_the_render_unification_keep_their_machine_code(built_lib):
+    """The same against the listing of the library before render.hip's kernel copies were folded into templates on the view
+    descriptor (tests/golden/render_unify_parent_isa_digest.txt: all 175 kernels of that library, the NV12 and exposure kernels the
+    listing above predates among them).  The listing is the PARENT's: a source-only change of the kernels is accepted when this
+    passes unedited (LAB_NOTES.md, "Source-only changes"), and a change that edits a kernel on purpose regenerates it."""
+    check_listing('render_unify_parent_isa_digest.txt', 175)
