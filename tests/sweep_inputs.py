@@ -376,6 +376,38 @@ def kernel_key(name):
     return m.group(1) + ('<%s>' % ','.join(args) if args else '')
 
 
+def split_kernel_name(name):
+    """A demangled kernel name of the code object -> (base name, parameter list without its parentheses); a name that is still
+    mangled, or carries no parameter list, raises ValueError: overloads cannot be told apart without one."""
+    import re
+    m = re.match(r'^(?:void )?([A-Za-z_][A-Za-z_0-9]*)', name)
+    if name.startswith('_Z') or not m or not name.endswith(')'):
+        raise ValueError('not a demangled kernel name with its parameter list: %r' % name)
+    depth = 0
+    for i in range(len(name) - 1, m.end() - 1, -1):                         # the parenthesis that the last one closes
+        depth += {')': 1, '(': -1}.get(name[i], 0)
+        if depth == 0:
+            return m.group(1), name[i + 1:-1]
+    raise ValueError('not a demangled kernel name with its parameter list: %r' % name)
+
+
+def parameter_lists(names):
+    """Demangled kernel names -> {base name: the set of distinct parameter lists the names carry under it}."""
+    lists = {}
+    for n in names:
+        base, params = split_kernel_name(n)
+        lists.setdefault(base, set()).add(params)
+    return lists
+
+
+def overload_key(name, lists):
+    """A demangled kernel name -> its key in library_reach: the base name, followed by the parenthesised parameter list whenever
+    `lists` (parameter_lists of every kernel of the library) holds more than one parameter list under that base name.  Template
+    arguments are dropped: the instantiations of one overload share a key."""
+    base, params = split_kernel_name(name)
+    return base + ('(%s)' % params if len(lists[base]) > 1 else '')
+
+
 # ------------------------------------------------------------------------------------------------ fp32 Winograd, emulated
 def _stage32(mat, d, axis):
     """One transform stage in fp32: out[i] = sum_a mat[i, a] d[a] along `axis`, term by term, every product and sum rounded."""
@@ -874,24 +906,67 @@ STITCH_SHAPES = [(1, 2), (1, 7), (2, 2), (2, 7), (30, 2), (30, 7), (300, 2), (30
 
 # ================================================================================================ the coverage table of the library
 KS, CS, RS_ = 'test_gpu_kernel_sweeps', 'test_gpu_conv_sweeps', 'test_gpu_rest_sweeps'
+SS, NV, EX, VP = 'test_gpu_stream_sweeps', 'test_gpu_nv12', 'test_gpu_exposure', 'test_gpu_viewport'
+SWEEP_MODULES = (KS, CS, RS_, SS, NV, EX, VP)      # the modules whose kernel-level tests compare with numpy or a float64 statement
 LB_CHAIN = ('lb_init_kernel', 'lb_centroid_kernel', 'lb_range_kernel', 'lb_premask_kernel', 'lb_blur_kernel', 'lb_final_kernel')
+
+# Short names of the overloads' keys: alias -> the key overload_key() gives, base name + the parameter list of the code object.  The
+# table below is written with the aliases; tests/test_ref64.py takes the parameter lists from the code objects and never from here,
+# so an alias that matches no kernel of the library shows as a stale row.
+_AVG = 'float const*, float const*, float const*, float*, int, int, int, int, int, long long, long long, long long'
+_CLIP = 'float const*, float const*, float*, unsigned int*, int, int, int, int, int, long long'
+_FRAMES = 'float const*, float const*, float*, unsigned int*, int, int, int, long long, LbFrameTab'
+_LATTICE = 'float const*, float const*, float*, long long, int, int, int, int, int, float, int*, float*'
+OVERLOAD_ALIASES = {
+    'render_average_kernel(RenderViews)': 'render_average_kernel(RenderViews, %s)' % _AVG,
+    'render_average_kernel(GainViews)': 'render_average_kernel(GainViews, %s)' % _AVG,
+    'render_average_kernel(Nv12Views)': 'render_average_kernel(Nv12Views, float const*, float const*, float const*, unsigned char*, '
+                                        'unsigned char*, int, int, int, int, int, int, long long, long long)',
+    'lb_clip_warp_kernel(RenderViews)': 'lb_clip_warp_kernel(RenderViews, %s)' % _CLIP,
+    'lb_clip_warp_kernel(GainViews)': 'lb_clip_warp_kernel(GainViews, %s)' % _CLIP,
+    'lb_frames_warp_kernel(RenderViews)': 'lb_frames_warp_kernel(RenderViews, %s)' % _FRAMES,
+    'lb_frames_warp_kernel(GainViews)': 'lb_frames_warp_kernel(GainViews, %s)' % _FRAMES,
+    'lb_frames_warp_kernel(Nv12Views)': 'lb_frames_warp_kernel(Nv12Views, float const*, float const*, float*, unsigned int*, int, int, '
+                                        'int, LbFrameTab)',
+    'render_lattice_kernel(footprint)': 'render_lattice_kernel(%s)' % _LATTICE,
+    'render_lattice_kernel(footprint, SsCanvasFit)': 'render_lattice_kernel(%s, SsCanvasFit)' % _LATTICE,
+    'canvas_watch_kernel(watch)': 'canvas_watch_kernel(float const*, int, float, int*, float*)',
+    'canvas_watch_kernel(watch, SsCanvasFit)': 'canvas_watch_kernel(float const*, int, float, int*, float*, SsCanvasFit)',
+    'canvas_watch_frames_kernel(watch)': 'canvas_watch_frames_kernel(float const*, int, int, float, int*, float*)',
+    'canvas_watch_frames_kernel(watch, SsCanvasFit)': 'canvas_watch_frames_kernel(float const*, int, int, float, int*, float*, SsCanvasFit)',
+    'ingest_hr1_kernel(bgr)': 'ingest_hr1_kernel(unsigned char const*, float*, long long, int)',
+    'ingest_hr1_kernel(y, uv)': 'ingest_hr1_kernel(unsigned char const*, unsigned char const*, int, long long, float*, int, int)',
+    'ingest_lr_kernel(bgr)': 'ingest_lr_kernel(unsigned char const*, float*, int, int, int, int, int, double, double)',
+    'ingest_lr_kernel(y, uv)': 'ingest_lr_kernel(unsigned char const*, unsigned char const*, int, long long, float*, int, int, int, int, '
+                               'double, double)',
+    'canvas_u8x1_kernel(fp32)': 'canvas_u8x1_kernel(float const*, unsigned char*, long long, int)',
+}
+AVG, AVG_GAINS, AVG_NV12 = ('render_average_kernel(%s)' % v for v in ('RenderViews', 'GainViews', 'Nv12Views'))
+CAST1 = 'canvas_u8x1_kernel(fp32)'
+BGR_TO_NV12 = 'canvas_u8x1_kernel(unsigned char const*, unsigned char*, unsigned char*, int, long long, int, int)'
+EXPOSURE = 'render_lattice_kernel(ExposureArgs)'
 
 
 def library_reach():
-    """Every kernel of the built library by its base name (all instantiations of a template share an entry; the convolution engine's
-    instantiations are told apart by reach_table above) -> (kind, tests, held_to):
-      'fp64'      the sweep tests that compare it with a statement of tests/ref64.py
-      'identity'  the test that holds it bit for bit to the kernels `held_to`, every one of them 'fp64' or 'identity' in turn
+    """Every kernel of the built library by its overload key (overload_key above) -> (kind, tests, held_to).  The key is the base
+    name where the library carries one parameter list under it, and base name + parameter list where it carries several: kernels
+    added as overloads of an existing name (the exposure estimator under the footprint sampler's, BGR -> NV12 under the byte cast's,
+    the NV12, gain and refit forms of the renders and watchers) have rows of their own.  All template instantiations of one
+    parameter list share an entry (the convolution engine's are told apart by reach_table above); rows are written with the short
+    names of OVERLOAD_ALIASES and returned under the full keys.
+      'fp64'      the sweep tests that compare it with a statement of tests/ref64.py or tests/exposure_ref.py
+      'identity'  the test that holds it bit for bit to the kernels `held_to`, every one of them 'fp64', 'exact' or 'identity' in turn
       'exact'     copy, permute, byte and min / max kernels: the test that holds them bit for bit to numpy
     Kernels that no call of the C ABI launches are in UNREACHABLE.  tests/test_ref64.py holds the table to the code objects of the
-    built library (nothing missing, nothing stale), follows every identity chain to an 'fp64' end and checks that the cited tests
-    exist."""
+    built library (nothing missing, nothing stale, the parameter lists taken from the demangled names), follows every identity
+    chain to an 'fp64' or 'exact' end and checks that the cited tests exist."""
     t = {}
+    full = lambda n: OVERLOAD_ALIASES.get(n, n)
 
     def add(kind, names, tests, held_to=()):
-        for n in names.split():
-            assert n not in t, n
-            t[n] = (kind, tuple(tests), tuple(held_to))
+        for n in (names.split() if isinstance(names, str) else names):      # (a list where a key holds blanks)
+            assert full(n) not in t, n
+            t[full(n)] = (kind, tuple(tests), tuple(full(k) for k in held_to))
     # ---- the two earlier sweeps
     add('fp64', 'cost_volume_kernel', [KS + '::test_cost_volume_against_fp64', KS + '::test_cost_volume_shifted_and_chain_against_fp64'])
     add('fp64', 'ccl_softmax_kernel', [KS + '::test_ccl_against_fp64'])
@@ -902,8 +977,8 @@ def library_reach():
     add('fp64', 'tsm_prepare_kernel tsm_finish_kernel tsm_fused_kernel', [KS + '::test_tsmotion_against_fp64'])
     add('fp64', 'tps_warp_kernel', [KS + '::test_tps_dense_warp_against_fp64'])
     add('fp64', 'tps_warp_views_kernel', [KS + '::test_tps_warp_views_against_fp64'])
-    add('identity', 'render_average_kernel', [KS + '::test_fused_render_equals_formula_on_per_view_warps'], ['tps_warp_kernel', 'canvas_u8x1_kernel', 'canvas_u8x4_kernel'])
-    add('identity', 'render_lattice_kernel render_order_kernel', ['test_gpu_parity::test_render_footprint_skipping'], ['render_average_kernel'])
+    add('identity', [AVG], [KS + '::test_fused_render_equals_formula_on_per_view_warps'], ['tps_warp_kernel', CAST1, 'canvas_u8x4_kernel'])
+    add('identity', ['render_lattice_kernel(footprint)', 'render_order_kernel'], ['test_gpu_parity::test_render_footprint_skipping'], [AVG])
     add('fp64', 'psnr_ssim_kernel psnr_ssim_finish_kernel', [KS + '::test_psnr_ssim_against_fp64'])
     add('fp64', 'stability_kernel distortion_kernel max_reduce_kernel', [KS + '::test_metric_scores_against_fp64_and_refusals'])
     add('fp64', 'linear_kernel linear_grouped_kernel', [KS + '::test_linear_against_fp64'])
@@ -914,16 +989,17 @@ def library_reach():
     add('fp64', 'conv_wino43p_kernel wino43_pack_kernel', [CS + '::test_winograd_f4_against_fp64'])
     # ---- LINEAR fusion
     add('fp64', ' '.join(LB_CHAIN), [RS_ + '::test_linear_blend_against_fp64', RS_ + '::test_linear_blend_three_view_chain_against_fp64'])
-    add('identity', 'lb_clip_warp_kernel lb_clip_reduce_kernel lb_clip_blend_kernel lb_clip_blend_rows_kernel lb_frames_warp_kernel '
-        'lb_frames_reduce_kernel lb_frames_blend_rows_kernel', [RS_ + '::test_linear_renderers_equal_per_frame_chain'],
-        LB_CHAIN + ('tps_warp_views_kernel', 'mask_union_kernel', 'canvas_u8x1_kernel', 'canvas_u8x4_kernel'))
+    add('identity', ['lb_clip_warp_kernel(RenderViews)', 'lb_clip_reduce_kernel', 'lb_clip_blend_kernel', 'lb_clip_blend_rows_kernel',
+                     'lb_frames_warp_kernel(RenderViews)', 'lb_frames_reduce_kernel', 'lb_frames_blend_rows_kernel'],
+        [RS_ + '::test_linear_renderers_equal_per_frame_chain'],
+        LB_CHAIN + ('tps_warp_views_kernel', 'mask_union_kernel', CAST1, 'canvas_u8x4_kernel'))
     # ---- mesh geometry
     add('fp64', 'tensor_dlt_kernel spatial_decompose_kernel spatial_meshes_kernel', [RS_ + '::test_dlt_decompose_meshes_against_fp64'])
     add('fp64', 'h2mesh_kernel', [RS_ + '::test_h2mesh_against_fp64'])
     add('exact', 'mesh_bbox_kernel', [RS_ + '::test_mesh_bbox_bit_exact'])
     add('fp64', 'mesh_normalize_kernel mesh_normalize_views_kernel stream_normalize_watch_kernel', [RS_ + '::test_canvas_normalize_kernels_bit_exact'])
     add('fp64', 'three_view_align_kernel three_view_normalize_kernel three_view_finish_kernel', [RS_ + '::test_three_view_glue_kernels'])
-    add('exact', 'canvas_watch_kernel canvas_watch_frames_kernel', [RS_ + '::test_canvas_watchers_against_the_documented_update'])
+    add('exact', ['canvas_watch_kernel(watch)', 'canvas_watch_frames_kernel(watch)'], [RS_ + '::test_canvas_watchers_against_the_documented_update'])
     add('identity', 'three_view_splines_kernel', ['test_gpu_round6::test_three_view_splines_equal_the_seven_launches'],
         ['three_view_align_kernel', 'three_view_normalize_kernel', 'tps_solve_kernel', 'tps_points_kernel', 'three_view_finish_kernel',
          'stream_normalize_watch_kernel'])
@@ -935,8 +1011,22 @@ def library_reach():
     add('exact', 'window_push_kernel', [RS_ + '::test_window_push_bit_exact'])
     add('exact', 'window_advance_kernel', [RS_ + '::test_window_advance_bit_exact'])
     # ---- byte and layout kernels
-    add('exact', 'ingest_hr4_kernel ingest_hr1_kernel ingest_lr_kernel', [RS_ + '::test_ingest_u8_paths_bit_exact'])
-    add('exact', 'canvas_u8x4_kernel canvas_u8x1_kernel', [RS_ + '::test_canvas_to_u8_paths_and_edge_values'])
+    add('exact', ['ingest_hr4_kernel', 'ingest_hr1_kernel(bgr)', 'ingest_lr_kernel(bgr)'], [RS_ + '::test_ingest_u8_paths_bit_exact'])
+    add('exact', ['canvas_u8x4_kernel', CAST1], [RS_ + '::test_canvas_to_u8_paths_and_edge_values'])
     add('exact', 'nchw_to_nhwc_kernel nchw_to_nhwc4_kernel nhwc_to_nchw_kernel', [RS_ + '::test_layout_kernels_bit_exact'])
     add('exact', 'affine_kernel mask_union_kernel fill_kernel', [RS_ + '::test_elementwise_helpers_bit_exact'])
+    # ---- the overloads of the streaming features: viewport refit, NV12 in and out, exposure gains
+    add('exact', ['canvas_watch_kernel(watch, SsCanvasFit)', 'canvas_watch_frames_kernel(watch, SsCanvasFit)',
+                  'render_lattice_kernel(footprint, SsCanvasFit)'], [VP + '::test_fit_kernels_equal_the_restatement_bit_for_bit'])
+    add('exact', ['ingest_hr1_kernel(y, uv)', 'ingest_lr_kernel(y, uv)'], [SS + '::test_ingest_nv12_paths_bit_exact'])
+    add('exact', [BGR_TO_NV12], [NV + '::test_bgr_to_nv12_equals_numpy', SS + '::test_bgr_to_nv12_into_strided_frames'])
+    add('fp64', [EXPOSURE], [EX + '::test_statistics_targets_and_smoothing', SS + '::test_exposure_beyond_one_wave_and_one_trip'])
+    add('identity', [AVG_NV12], [NV + '::test_render_average_nv12_equals_the_u8_render_and_its_nv12',
+                                 SS + '::test_render_average_nv12_at_the_tile_edges'], [AVG, BGR_TO_NV12])
+    add('identity', ['lb_frames_warp_kernel(Nv12Views)'], [NV + '::test_render_linear_frames_nv12_equals_the_u8_render'],
+        ['lb_frames_warp_kernel(RenderViews)'])
+    gains = [EX + '::test_gain_renders_reduce_to_the_plain_renders', EX + '::test_general_gains_equal_the_per_frame_chains']
+    add('identity', [AVG_GAINS], gains, [AVG, 'tps_warp_kernel', CAST1, 'canvas_u8x4_kernel'])
+    add('identity', ['lb_clip_warp_kernel(GainViews)'], gains, ['lb_clip_warp_kernel(RenderViews)', 'tps_warp_views_kernel'])
+    add('identity', ['lb_frames_warp_kernel(GainViews)'], gains, ['lb_frames_warp_kernel(RenderViews)', 'tps_warp_views_kernel'])
     return t

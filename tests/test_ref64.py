@@ -789,18 +789,27 @@ def test_watch_frames_are_what_the_sweep_says():
 
 # ------------------------------------------------------------------------------------------------ the coverage table of the library
 def test_library_reach_covers_every_kernel_of_the_library():
-    """sweep_inputs.library_reach against the gfx950 code objects of the built library: every kernel the library carries is held to a
-    float64 statement ('fp64'), bit for bit to numpy ('exact'), bit for bit to kernels that are ('identity', every chain followed to
-    its end), or listed as unreachable from the C ABI with the reason; the table names nothing the library lacks, and every test it
-    cites exists in the module it names."""
+    """sweep_inputs.library_reach against the gfx950 code objects of the built library, keyed by overload: a kernel's key is its base
+    name, followed by its parameter list wherever the library carries more than one parameter list under that name (taken from the
+    demangled names of the code objects, never from the table's aliases), so a kernel added as an overload of a covered name needs
+    a row of its own.  Every kernel the library carries is held to a float64 statement ('fp64'), bit for bit to numpy ('exact'),
+    bit for bit to kernels that are ('identity', every chain followed to its end), or listed as unreachable from the C ABI with the
+    reason; the table names nothing the library lacks, and every test it cites exists in the module it names.  Names that come back
+    mangled (no llvm-cxxfilt, no c++filt) fail the test: base names alone cannot tell overloads apart."""
     import re
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, os.path.join(os.path.dirname(here), 'tools'))
     import kernel_resources as KR
     from stabstitch2_amd import _hip as H
-    have = {G.kernel_key(k).split('<')[0] for k in KR.kernels(H.LIB_PATH)}
-    assert len(have) >= 70, sorted(have)
+    names = sorted(KR.kernels(H.LIB_PATH))
+    mangled = [n for n in names if n.startswith('_Z') or '(' not in n]
+    assert not mangled, ('the kernel names came back without their parameter lists (neither llvm-cxxfilt nor c++filt demangled '
+                         'them): overloads cannot be told apart, e.g. %s' % mangled[:3])
+    lists = G.parameter_lists(names)
+    have = {G.overload_key(n, lists) for n in names}
+    assert {k.split('(')[0] for k in have} == {G.kernel_key(n).split('<')[0] for n in names}
+    assert len(have) >= 82, sorted(have)               # the floor of 70 under base names, raised by the 12 keys the overloads add
     table = G.library_reach()
     unreachable = {k.split('<')[0] for k in G.UNREACHABLE}
     assert not set(table) & unreachable
@@ -818,7 +827,7 @@ def test_library_reach_covers_every_kernel_of_the_library():
                 defined[mod] = set(re.findall(r'^def (test_\w+)\(', open(os.path.join(here, mod + '.py')).read(), re.M))
             assert name in defined[mod], 'the coverage table cites %s, which %s.py does not define' % (tid, mod)
             if kind != 'identity':
-                assert mod in (G.KS, G.CS, G.RS_), (kernel, tid)
+                assert mod in G.SWEEP_MODULES, (kernel, tid)
 
     def ends_rooted(kernel, seen=()):
         kind, _, held_to = table[kernel]
