@@ -39,6 +39,17 @@ extern "C" {
 #define SS_WARP_EPS_FOLD 16      /* OR-ed into `mode` of the fused AVERAGE renders (ss_render_average*): the radial term as
                                   * a log(a), a = dx^2 + (dy^2 + 1e-6), instead of the reference's d2 log(d2 + 1e-6)
                                   * (utils/torch_tps_transform.py:108-137): ~1e-3 px at 720p, ~7 % of the kernel.  Opt-in. */
+#define SS_FUSE_FEATHER 32       /* OR-ed into `mode` of every ss_render_average* entry (single, _u8, _nv12, _clip, _clip_u8 and the
+                                  * four _gains): FEATHER fusion instead of AVERAGE.  Not the reference's: the border-distance
+                                  * weights of panorama tools.  Per canvas pixel, with view v's normalised sampling coordinate
+                                  * (xn_v, yn_v) and its sampled channels c_v (the render's own sampler, NORMAL or FAST, after
+                                  * fminf(g c, 255) where gains are given), all in fp32, one rounding per operation, no fma:
+                                  *     w_v = fmaxf(fminf(1 - |xn_v|, 1 - |yn_v|), 0)      (0 for a view the footprint skips --
+                                  *           exact: a skipped tile lies outside the image, so footprint == NULL bit for bit)
+                                  *     num = ((w_0 c_0) + (w_1 c_1)) [+ (w_2 c_2)],  den = (w_0 + w_1) [+ w_2]
+                                  *     out = den > 0 ? num / den : 0                        (IEEE division)
+                                  * Three views are fused at once, symmetrically, not chained.  The uint8 and NV12 sinks are
+                                  * AVERAGE's; a pixel no view reaches is 0 (black in NV12).  With SS_WARP_EPS_FOLD: SS_ERR_ARG. */
 
 SS_API int ss_version(void);
 SS_API const char* ss_error_string(int code);

@@ -17,6 +17,9 @@ c_f = ctypes.c_float
 c_ll = ctypes.c_longlong
 c_st = ctypes.c_void_p        # hipStream_t
 
+# the bits of the renders' `mode` argument, as the header defines them
+MODE_FLAGS = {'SS_WARP_NORMAL': 0, 'SS_WARP_FAST': 1, 'SS_WARP_EPS_FOLD': 16, 'SS_FUSE_FEATHER': 32}
+
 # name -> (restype, argtypes); mirrors include/stabstitch_hip.h one to one
 SIGNATURES = {
     'ss_version': (c_i, []),

@@ -677,19 +677,117 @@ __global__ __launch_bounds__(256) void render_average_kernel(Views rv, const flo
     }
 }
 
+// ---- FEATHER fusion (SS_FUSE_FEATHER; not the reference's -- the border-distance weights of panorama tools) ----------
+// Per canvas pixel, with view v's normalised sampling coordinate (xn_v, yn_v) and its sampled channels c_v (the samplers above,
+// after apply_gains where gains are given), fp32, one rounding per operation:
+//     w_v = fmaxf(fminf(1 - |xn_v|, 1 - |yn_v|), 0);   num = sum_v w_v c_v,  den = sum_v w_v  (in the order of the views);
+//     out = den > 0 ? num / den : 0
+// A view the footprint skips has w_v = 0: exact, since a skipped tile lies outside the image, where 1 - |xn| < 0 -- the render with
+// a footprint equals the render without one.  All views at once and symmetric in them, where AVERAGE chains ((1 (+) 2) (+) 3).
+// The fused render "with another fusion formula": a second template of the same name under the same parameter lists, told apart
+// by a leading tag type, so that the AVERAGE instantiations keep their names and their machine code.  The new kernels have no
+// machine code to keep: they share one device body (feather_rows), and sums are accumulated view by view -- 2 x (3 + 1) live
+// values instead of the 2 x 3 x VIEWS samples the chained fusion holds.
+struct FeatherFuse {};
+__device__ __forceinline__ float feather_weight(float xn, float yn) {
+    return fmaxf(fminf(__fsub_rn(1.f, fabsf(xn)), __fsub_rn(1.f, fabsf(yn))), 0.f);
+}
+// both rows of a lane (tps_eval_rows) through every view of `mask`: sample(k, xn, yn, v) fills view k's three channels
+template <int VIEWS, typename Sample>
+__device__ __forceinline__ void feather_rows(unsigned mask, const float* __restrict__ source, const float* __restrict__ T,
+                                             ss_f2 (*tab)[64], int lx, float gx, float gya, float gyb, Sample&& sample,
+                                             float (&fa)[3], float (&fb)[3]) {
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k)
+        if (mask & (1u << k)) tps_rows_table(source + k * SS_NV * 2, gya, gyb, lx, tab[k]);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // same wave reads it back: ordering only, no barrier
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    float na[3] = {0.f, 0.f, 0.f}, nb[3] = {0.f, 0.f, 0.f}, da = 0.f, db = 0.f;
+#pragma unroll
+    for (int k = 0; k < VIEWS; ++k) {
+        if (mask & (1u << k)) {
+            ss_f2 px, py;
+            tps_eval_rows(source + k * SS_NV * 2, T + k * 2 * SS_NT, tab[k], gx, gya, gyb, px, py);
+            float va[3], vb[3];
+            sample(k, px.x, py.x, va);
+            sample(k, px.y, py.y, vb);
+            const float wa = feather_weight(px.x, py.x), wb = feather_weight(px.y, py.y);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                na[ch] = __fadd_rn(na[ch], __fmul_rn(wa, va[ch]));
+                nb[ch] = __fadd_rn(nb[ch], __fmul_rn(wb, vb[ch]));
+            }
+            da = __fadd_rn(da, wa);
+            db = __fadd_rn(db, wb);
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        fa[ch] = da > 0.f ? __fdiv_rn(na[ch], da) : 0.f;
+        fb[ch] = db > 0.f ? __fdiv_rn(nb[ch], db) : 0.f;
+    }
+}
+
+// render_average_kernel<VIEWS, U8> with the FEATHER fuse: the same rows per wave, the same sinks
+template <typename FUSE, int VIEWS, bool U8, typename Views>
+__global__ __launch_bounds__(256) void render_average_kernel(Views rv, const float* __restrict__ source,
+                                                             const float* __restrict__ T, const float* __restrict__ fp,
+                                                             float* __restrict__ out, int h, int w, int hc, int wc,
+                                                             int mode, long long img_fs, long long out_fs,
+                                                             long long fp_fs) {
+    static_assert(std::is_same<FUSE, FeatherFuse>::value, "the fusion tags: FeatherFuse");
+    {
+        const long long frame = blockIdx.y;
+        source += frame * (VIEWS * SS_NV * 2);
+        T += frame * (VIEWS * 2 * SS_NT);
+        if (fp) fp += frame * fp_fs;
+        out = reinterpret_cast<float*>(reinterpret_cast<char*>(out) + frame * out_fs);
+        views_to_frame<VIEWS>(rv, frame, img_fs);
+    }
+    unsigned char* const out8 = reinterpret_cast<unsigned char*>(out);
+    const int lx = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long hw = (long long)h * w, ohw = (long long)hc * wc;
+    int tbx, tby;
+    const unsigned mask = render_tile<VIEWS>(fp, hc, wc, tbx, tby);
+    const int x = tbx * 64 + lx;
+    const int ya = tby * 8 + wv, yb = ya + 4;
+    if (tbx * 64 >= wc || ya >= hc) return;       // (whole waves only: the lanes past the canvas edge still help build the table)
+    const float gx = linspace_at(-1.f, 1.f, wc, min(x, wc - 1));
+    const float gya = linspace_at(-1.f, 1.f, hc, ya), gyb = linspace_at(-1.f, 1.f, hc, min(yb, hc - 1));
+    __shared__ ss_f2 dytab[4][VIEWS][64];
+    float fa[3], fb[3];
+    feather_rows<VIEWS>(mask, source, T, dytab[wv], lx, gx, gya, gyb, [&](int k, float xn, float yn, float (&v)[3]) {
+        if (U8) sample3_u8(reinterpret_cast<const unsigned char*>(rv.img[k]), xn, yn, w, h, mode, v);
+        else sample3(rv.img[k], xn, yn, w, h, hw, mode, v);
+        if constexpr (std::is_same<Views, GainViews>::value) apply_gains(rv.gains + k * 3, v);
+    }, fa, fb);
+    if (x >= wc) return;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        if (U8) {
+            out8[((long long)ya * wc + x) * 3 + ch] = render_to_u8(fa[ch]);
+            if (yb < hc) out8[((long long)yb * wc + x) * 3 + ch] = render_to_u8(fb[ch]);
+        } else {
+            out[ch * ohw + (long long)ya * wc + x] = fa[ch];
+            if (yb < hc) out[ch * ohw + (long long)yb * wc + x] = fb[ch];
+        }
+    }
+}
+
 static int render_average_launch(const void* const* imgs, const float* source, const float* T, const float* footprint,
                                  long long footprint_floats, void* out, int frames, long long img_fs, long long out_fs,
                                  int views, int h, int w, int hc, int wc, int mode, void* stream, bool u8,
                                  const float* gains = nullptr, bool with_gains = false) {
     if (with_gains && (!gains || (mode & SS_WARP_EPS_FOLD))) return SS_ERR_ARG;       // (the gain forms have no folded variant)
+    if ((mode & SS_FUSE_FEATHER) && (mode & SS_WARP_EPS_FOLD)) return SS_ERR_ARG;     // (nor has FEATHER)
     if (!imgs || !source || !T || !out || frames <= 0 || (views != 2 && views != 3) || h <= 1 || w <= 1 || hc <= 1 ||
-        wc <= 1 || ((mode & 0xEF) != SS_WARP_NORMAL && (mode & 0xEF) != SS_WARP_FAST))
+        wc <= 1 || ((mode & 0xCF) != SS_WARP_NORMAL && (mode & 0xCF) != SS_WARP_FAST))
         return SS_ERR_ARG;
 #ifndef SS_TUNING
     if (mode >> 8) return SS_ERR_ARG;
 #endif
-    const bool fold = (mode & SS_WARP_EPS_FOLD) != 0;
-    mode &= ~SS_WARP_EPS_FOLD;
+    const bool fold = (mode & SS_WARP_EPS_FOLD) != 0, feather = (mode & SS_FUSE_FEATHER) != 0;
+    mode &= ~(SS_WARP_EPS_FOLD | SS_FUSE_FEATHER);
     // a footprint row is only meaningful for the (views, canvas) it was built for: the kernel indexes its lattice and tile
     // order with this geometry, so a row of another size is an argument error, not an out-of-bounds read
     const long long fp_fs = ss_render_footprint_floats(views, hc, wc);
@@ -714,8 +812,14 @@ static int render_average_launch(const void* const* imgs, const float* source, c
                 render_average_kernel<decltype(V)::value, decltype(U8)::value, decltype(FOLD)::value>
                     <<<g, dim3(256), 0, st>>>(rv, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
             };
+            auto feather_launch = [&](auto rv) {
+                render_average_kernel<FeatherFuse, decltype(V)::value, decltype(U8)::value>
+                    <<<g, dim3(256), 0, st>>>(rv, s_, t_, p_, o, h, w, hc, wc, mode, img_fs, out_fs, fp_fs);
+            };
             // (fold: opt-in, the reference's + 1e-6 folded into the row table -- not its arithmetic; see device_math.h)
-            if (with_gains) launch(r, std::false_type{});
+            if (feather && with_gains) feather_launch(r);
+            else if (feather) feather_launch(RenderViews(r));
+            else if (with_gains) launch(r, std::false_type{});
             else if (fold) launch(RenderViews(r), std::true_type{});
             else launch(RenderViews(r), std::false_type{});
         });
@@ -820,6 +924,63 @@ __global__ __launch_bounds__(256) void render_average_kernel(Nv12Views nv, const
     }
 }
 
+// render_average_kernel<VIEWS, NV12OUT> with the FEATHER fuse: the same rows per wave (2 w, 2 w + 1), the same sinks
+template <typename FUSE, int VIEWS, bool NV12OUT>
+__global__ __launch_bounds__(256) void render_average_kernel(Nv12Views nv, const float* __restrict__ source,
+                                                             const float* __restrict__ T, const float* __restrict__ fp,
+                                                             unsigned char* __restrict__ out8, unsigned char* __restrict__ out_uv,
+                                                             int out_pitch, int h, int w, int hc, int wc, int mode, long long out_fs,
+                                                             long long fp_fs) {
+    static_assert(std::is_same<FUSE, FeatherFuse>::value, "the fusion tags: FeatherFuse");
+    {
+        const long long frame = blockIdx.y;
+        source += frame * (VIEWS * SS_NV * 2);
+        T += frame * (VIEWS * 2 * SS_NT);
+        if (fp) fp += frame * fp_fs;
+        out8 += frame * out_fs;
+        if (NV12OUT) out_uv += frame * out_fs;
+        views_to_frame<VIEWS>(nv, frame);
+    }
+    const int lx = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int tbx, tby;
+    const unsigned mask = render_tile<VIEWS>(fp, hc, wc, tbx, tby);
+    const int x = tbx * 64 + lx;
+    const int ya = tby * 8 + 2 * wv, yb = ya + 1;
+    if (tbx * 64 >= wc || ya >= hc) return;       // (whole waves only: the lanes past the canvas edge still help build the table)
+    const bool xin = x < wc, rowb = yb < hc;
+    const float gx = linspace_at(-1.f, 1.f, wc, min(x, wc - 1));
+    const float gya = linspace_at(-1.f, 1.f, hc, ya), gyb = linspace_at(-1.f, 1.f, hc, min(yb, hc - 1));
+    __shared__ ss_f2 dytab[4][VIEWS][64];
+    float fa[3], fb[3];
+    feather_rows<VIEWS>(mask, source, T, dytab[wv], lx, gx, gya, gyb, [&](int k, float xn, float yn, float (&v)[3]) {
+        sample3_nv12(nv.y[k], nv.uv[k], nv.pitch[k], xn, yn, w, h, mode, v);
+    }, fa, fb);
+    unsigned char ba[3], bb[3];       // the video frame's B, G, R bytes at (x, ya) and (x, yb)
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) { ba[ch] = render_to_u8(fa[ch]); bb[ch] = render_to_u8(fb[ch]); }
+    if (!NV12OUT) {
+        if (!xin) return;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            out8[((long long)ya * wc + x) * 3 + ch] = ba[ch];
+            if (rowb) out8[((long long)yb * wc + x) * 3 + ch] = bb[ch];
+        }
+    } else {
+        // (hc and wc are even: rowb holds, and the two lanes of a block are inside the canvas together)
+        int s[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const int own = (int)ba[ch] + (int)bb[ch];
+            s[ch] = own + __shfl_xor(own, 1, 64);
+        }
+        if (!xin) return;
+        out8[(long long)ya * out_pitch + x] = bgr_to_y(ba[0], ba[1], ba[2]);
+        out8[(long long)yb * out_pitch + x] = bgr_to_y(bb[0], bb[1], bb[2]);
+        if (!(lx & 1))
+            *reinterpret_cast<unsigned short*>(out_uv + (long long)(ya >> 1) * out_pitch + x) = bgr4_to_uv(s[0], s[1], s[2]);
+    }
+}
+
 // NV12 views of an entry point -> the kernels' descriptor; false: a surface the NV12 routes refuse (nv12.h)
 static bool nv12_views_make(Nv12Views& nv, const unsigned char* const* y, const unsigned char* const* uv, const int* pitch,
                             const long long* frame_stride, int views, int h, int w) {
@@ -840,9 +1001,10 @@ extern "C" int ss_render_average_nv12(const unsigned char* const* y, const unsig
                                       const float* source, const float* T, const float* footprint, long long footprint_floats,
                                       unsigned char* out, unsigned char* out_uv, int out_pitch, int out_format, int views, int h,
                                       int w, int hc, int wc, int mode, void* stream) {
-    if (!source || !T || !out || (views != 2 && views != 3) || hc <= 1 || wc <= 1 || (mode != SS_WARP_NORMAL && mode != SS_WARP_FAST) ||
-        (out_format != 0 && out_format != 1))
+    if (!source || !T || !out || (views != 2 && views != 3) || hc <= 1 || wc <= 1 || ((mode & ~SS_FUSE_FEATHER) != SS_WARP_NORMAL && (mode & ~SS_FUSE_FEATHER) != SS_WARP_FAST) || (out_format != 0 && out_format != 1))
         return SS_ERR_ARG;
+    const bool feather = (mode & SS_FUSE_FEATHER) != 0;
+    mode &= ~SS_FUSE_FEATHER;
     Nv12Views nv;
     if (!nv12_views_make(nv, y, uv, pitch, nullptr, views, h, w)) return SS_ERR_ARG;
     if (out_format == 1 && (!out_uv || (hc & 1) || (wc & 1) || (out_pitch & 1) || out_pitch < wc ||
@@ -853,8 +1015,12 @@ extern "C" int ss_render_average_nv12(const unsigned char* const* y, const unsig
     hipStream_t st = (hipStream_t)stream;
     const dim3 g(ss_cdiv(wc, 64) * ss_cdiv(hc, 8), 1, 1);
     with_views(views, out_format == 1, [&](auto V, auto NV12OUT) {
-        render_average_kernel<decltype(V)::value, decltype(NV12OUT)::value>
-            <<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
+        if (feather)
+            render_average_kernel<FeatherFuse, decltype(V)::value, decltype(NV12OUT)::value>
+                <<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
+        else
+            render_average_kernel<decltype(V)::value, decltype(NV12OUT)::value>
+                <<<g, dim3(256), 0, st>>>(nv, source, T, footprint, out, out_uv, out_pitch, h, w, hc, wc, mode, 0ll, fp_fs);
     });
     return ss_launch_status();
 }

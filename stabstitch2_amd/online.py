@@ -414,9 +414,14 @@ class _Stitcher:
         self.h, self.w = height, width
         self.margin = margin
         self.warp_mode, self.fusion_mode = warp_mode, fusion_mode
+        # AVERAGE | FEATHER: the fused single-launch render (ops.render_average*, the formula its `fusion`) -- the direct render, the
+        # uint8 steady state, footprint skipping, NV12 written by the render and the batch renders all ask this, not the mode's name
+        self._fused = ops.fused_render(fusion_mode)
+        if fusion_mode == 'FEATHER' and ops.RENDER_EPS_FOLD:
+            raise ValueError('SS_RENDER_EPS_FOLD has no FEATHER form')
         self.use_graph = use_graph
         self.meshes_only = bool(meshes_only)
-        direct = fusion_mode == 'AVERAGE' or (fusion_mode == 'LINEAR' and DIRECT_LINEAR and self._LINEAR_DIRECT)
+        direct = self._fused or (fusion_mode == 'LINEAR' and DIRECT_LINEAR and self._LINEAR_DIRECT)
         self._direct_render = bool(DIRECT_RENDER and use_graph and direct and not self.meshes_only)
         self._lin_ws = {}                # direct LINEAR render: chunk -> ((canvas sizes, views), workspace), re-made when a canvas changes
         # overflow of the fixed canvas(es), and the device-side refit of their boxes; meshes_only: never started
@@ -594,7 +599,7 @@ class _Stitcher:
         imgs [1,3,H,W] (written to `out` if given; out=_DEFER: splines and footprint left in self._deferred for the push's render).
         watch = (guard, watch_i [1,4], watch_f [1,4]): the overflow watcher has not seen `src` yet; fit (grow='refit'): the
         ops.CanvasFit of this canvas -- the launch that carries the watcher re-fixes the box behind it."""
-        skip = self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE
+        skip = self._fused and pipeline.SKIP_OUTSIDE
         if watch is not None and not (skip or self.exposure is not None):
             ops.canvas_watch(src[None], watch[1], watch[2], watch[0], fit=fit)   # no footprint launch to carry it
             watch = None
@@ -607,7 +612,7 @@ class _Stitcher:
             else:
                 shp = (1, 3, self.h, self.w)
                 gains = self._exposure_gains([f.reshape(shp) for f in imgs], efp)
-        if self.fusion_mode == 'AVERAGE':
+        if self._fused:
             fp = None
             if efp is not None:
                 fp = efp[0] if skip else None
@@ -617,7 +622,8 @@ class _Stitcher:
             if out is _DEFER:
                 self._deferred = (src, T, fp)
                 return None
-            return ops.render_average(imgs, src, T, self.hc, self.wc, self.warp_mode, out=out, footprint=fp, gains=gains)
+            return ops.render_average(imgs, src, T, self.hc, self.wc, self.warp_mode, out=out, footprint=fp, gains=gains,
+                                      fusion=self.fusion_mode)
         if out is _DEFER:                    # LINEAR: the graph ends with the splines and the watcher
             self._deferred = (src, T, None)
             return None
@@ -648,10 +654,11 @@ class _Stitcher:
             shp = (1, self.h, self.w, 3) if u8 else (1, 3, self.h, self.w)
             return self._render_linear([f.reshape(shp) for f in imgs], src[None], T[None], [(self.hc, self.wc)], gains=gains)
         if u8:                           # uint8 frames in, the uint8 video frame out: no fp32 frame planes, no fp32 canvas
-            return [ops.render_average_u8(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp, gains=gains)]
+            return [ops.render_average_u8(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp, gains=gains,
+                                          fusion=self.fusion_mode)]
         shp = (1, 3, self.h, self.w)
         return [ops.render_average([f.reshape(shp) for f in imgs], src, T, self.hc, self.wc, self.warp_mode, footprint=fp,
-                                   gains=gains)]
+                                   gains=gains, fusion=self.fusion_mode)]
 
     def _render_direct_nv12(self, deferred, imgs, out):
         """_render_direct from the caller's NV12 frames: AVERAGE writes the requested format itself; LINEAR writes the uint8 frame
@@ -661,15 +668,17 @@ class _Stitcher:
             bgr = self._render_linear([f[None] for f in imgs], src[None], T[None], [(self.hc, self.wc)], nv12=True)
             return [ops.bgr_to_nv12(f) for f in bgr] if out == 'nv12' else bgr
         if out == 'nv12' and not NV12_FUSED_SINK:
-            return [ops.bgr_to_nv12(ops.render_average_nv12(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp))]
-        return [ops.render_average_nv12(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp, out_format=out)]
+            return [ops.bgr_to_nv12(ops.render_average_nv12(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp,
+                                                            fusion=self.fusion_mode))]
+        return [ops.render_average_nv12(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp, out_format=out,
+                                        fusion=self.fusion_mode)]
 
     def _push_nv12(self, imgs, out):
         """push_nv12 of V views (checked): the steady state with the direct render samples the caller's NV12 frames; every other
         configuration, and the window fill, goes ingest_nv12 -> _push -> canvas_to_u8 (-> bgr_to_nv12)."""
         with ops.deterministic(self.deterministic):
             # (the NV12 render has no SS_RENDER_EPS_FOLD form: with that opt-in set the fp32 route keeps the two formats equal)
-            if self._u8_steady() and not (ops.RENDER_EPS_FOLD and self.fusion_mode == 'AVERAGE'):
+            if self._u8_steady() and not (ops.RENDER_EPS_FOLD and self._fused):
                 return self._push_static(nv12=(imgs, out))
             v = len(imgs)
             hr = torch.empty((v, 3, self.h, self.w), device=self.dev)
@@ -789,9 +798,9 @@ class _Stitcher:
         views = [f.contiguous() for f in imgs]
         # exposure: the k frames' gains in one update (stream order, bit-identical to k single-frame updates)
         gains = None if self.exposure is None else self._exposure_gains(views, deferred[3])
-        if self.fusion_mode == 'AVERAGE':
+        if self._fused:
             render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
-            out = render(views, src, T, self.hc, self.wc, self.warp_mode, footprint=fp, gains=gains)
+            out = render(views, src, T, self.hc, self.wc, self.warp_mode, footprint=fp, gains=gains, fusion=self.fusion_mode)
         else:
             out = ops.render_linear_clip(views, src, T, self.hc, self.wc, self.warp_mode, gains=gains)
         return list(out.unbind(0))
@@ -1090,7 +1099,7 @@ class OnlineStitcher(_Stitcher):
         guard, wi, wf = self.watch.args()
         ops.canvas_watch_frames(src, wi, wf, guard, fit=self.watch.fit_args())
         fp = efp = None
-        skip = self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE
+        skip = self._fused and pipeline.SKIP_OUTSIDE
         if skip or self.exposure is not None:        # (exposure: the lattice is the estimator's sample set whatever the fusion is)
             efp = ops.render_footprints(src, T, self.h, self.w, self.hc, self.wc)
             fp = efp if skip else None
@@ -1556,7 +1565,7 @@ class MultiOnlineStitcher(_Stitcher):
         # the render stream by stream
         src, T = ops.stream_splines([m1[0, -1], m2[0, -1]], WINDOW * e, st['bboxes'], self.single[0].nrigid, self.h, self.w)
         watch = None
-        if self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE:
+        if self._fused and pipeline.SKIP_OUTSIDE:
             watch = self.watch.args()
         else:
             ops.canvas_watch(src, self.watch.wi, self.watch.wf, self.watch.guard, fit=self.watch.fit_args())
@@ -1566,13 +1575,13 @@ class MultiOnlineStitcher(_Stitcher):
         if out_all is not None:
             # all streams render onto canvases of ONE size (e.g. the caller fixed them): the S current frames are a clip
             hc, wc = self.single[0].hc, self.single[0].wc
-            if self.fusion_mode == 'AVERAGE':
+            if self._fused:
                 fp = (ops.render_footprints(src, T, self.h, self.w, hc, wc, watch=watch, fit=self.watch.fit_args())
                       if pipeline.SKIP_OUTSIDE else None)
                 if defer:
                     self._deferred = (src, T, fp)
                     return
-                ops.render_average_clip([hr1, hr2], src, T, hc, wc, self.warp_mode, out=out_all, footprint=fp)
+                ops.render_average_clip([hr1, hr2], src, T, hc, wc, self.warp_mode, out=out_all, footprint=fp, fusion=self.fusion_mode)
             else:
                 ops.render_linear_clip([hr1, hr2], src, T, hc, wc, self.warp_mode, out=out_all)
             return
@@ -1598,13 +1607,15 @@ class MultiOnlineStitcher(_Stitcher):
             src, T, fp = deferred
             one = self.single[0]
             render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
-            frames = render([f.contiguous() for f in imgs], src, T, one.hc, one.wc, self.warp_mode, footprint=fp)
+            frames = render([f.contiguous() for f in imgs], src, T, one.hc, one.wc, self.warp_mode, footprint=fp,
+                            fusion=self.fusion_mode)
             return [[frames[s]] for s in range(S)]
         render = ops.render_average_u8 if u8 else ops.render_average          # (uint8 frames [H,W,3], fp32 ones [1,3,H,W])
         res = []
         for s, one in enumerate(self.single):
             src, T, fp = deferred[s]
-            res.append([render([f[s] if u8 else f[s:s + 1] for f in imgs], src, T, one.hc, one.wc, self.warp_mode, footprint=fp)])
+            res.append([render([f[s] if u8 else f[s:s + 1] for f in imgs], src, T, one.hc, one.wc, self.warp_mode, footprint=fp,
+                               fusion=self.fusion_mode)])
         return res
 
     @torch.no_grad()
@@ -1949,7 +1960,7 @@ class ThreeViewOnlineStitcher(_Stitcher):
         guard, wi, wf = self.watch.args()
         ops.canvas_watch_frames(src, wi, wf, guard, fit=self.watch.fit_args())
         fp = None
-        if self.fusion_mode == 'AVERAGE' and pipeline.SKIP_OUTSIDE:
+        if self._fused and pipeline.SKIP_OUTSIDE:
             fp = ops.render_footprints(src, T, self.h, self.w, self.hc, self.wc)
         B['deferred'] = (src, T, fp)
 

@@ -818,8 +818,28 @@ MODES = {'NORMAL': 0, 'FAST': 1}
 RENDER_EPS_FOLD = os.environ.get('SS_RENDER_EPS_FOLD', '0') == '1'
 
 
-def _avg_mode(mode):
-    return MODES[mode] | (16 if RENDER_EPS_FOLD else 0)
+FUSIONS = {'AVERAGE': 0, 'FEATHER': H.MODE_FLAGS['SS_FUSE_FEATHER']}      # the fused single-launch render's fusion formulas (SS_FUSE_FEATHER)
+
+
+def fused_render(fusion_mode):
+    """Whether a fusion mode is one of the fused single-launch render's (ss_render_average*): what the clip and streaming paths ask
+    where they choose between that render and the LINEAR chain."""
+    return fusion_mode in FUSIONS
+
+
+def _fusion_bit(fusion):
+    """fusion= of the render_average* forms -> its bit of `mode`.  FEATHER: every view weighted by its distance to its own image
+    border, w = max(min(1 - |xn|, 1 - |yn|), 0), all views at once (include/stabstitch_hip.h, SS_FUSE_FEATHER); it has no folded
+    variant."""
+    if fusion not in FUSIONS:
+        raise ValueError("fusion must be 'AVERAGE' or 'FEATHER', got %r" % (fusion,))
+    if FUSIONS[fusion] and RENDER_EPS_FOLD:
+        raise ValueError('SS_RENDER_EPS_FOLD has no FEATHER form')
+    return FUSIONS[fusion]
+
+
+def _avg_mode(mode, fusion='AVERAGE'):
+    return MODES[mode] | _fusion_bit(fusion) | (16 if RENDER_EPS_FOLD else 0)
 
 
 def tps_warp(U, source, T, hc, wc, mode='NORMAL', with_mask=False):
@@ -919,10 +939,11 @@ def _gains(gains, n, v):
     return H.dptr(gains)
 
 
-def _render_average(views, source, T, hc, wc, mode, out, footprint, gains, u8, clip):
+def _render_average(views, source, T, hc, wc, mode, out, footprint, gains, u8, clip, fusion='AVERAGE'):
     """The four render_average* below, and with gains= their _gains entries.  u8: decoded uint8 frames [..,h,w,3] -> uint8 [..,hc,wc,3]
     instead of fp32 planes [..,3,h,w] -> [..,3,hc,wc]; clip: a leading frame axis n on views, source, T, footprint and out."""
     v = len(views)
+    fuse = _fusion_bit(fusion)
     dt = torch.uint8 if u8 else torch.float32
     if not u8 and not clip:
         views = [_f(i) for i in views]
@@ -944,38 +965,40 @@ def _render_average(views, source, T, hc, wc, mode, out, footprint, gains, u8, c
     frames = (n,) if clip else ()        # the clip entries take the frame count in front of the view count
     args = (arr, H.dptr(_f(source)), H.dptr(T), fp, fpn, outp) + frames + (v, h, w, hc, wc)
     if gains is not None:                # exposure gains [n,V,3] (exposure_update): sampled values scaled and clamped to 255;
-        H.call(name + '_gains', *args, MODES[mode], _gains(gains, n, v), H.stream())      # (these entries have no folded variant)
+        H.call(name + '_gains', *args, MODES[mode] | fuse, _gains(gains, n, v), H.stream())      # (these entries have no folded variant)
     else:
-        H.call(name, *args, _avg_mode(mode), H.stream())
+        H.call(name, *args, _avg_mode(mode, fusion), H.stream())
     return out
 
 
-def render_average(imgs, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
+def render_average(imgs, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None, fusion='AVERAGE'):
     """imgs: list of 2|3 device tensors [1,3,h,w] / [3,h,w]; source [V,63,2]; T [V,2,66] -> [3,hc,wc].
     footprint: this frame's row of `render_footprints` (views that cannot reach a tile are skipped there and count as
     exactly 0 -- a deliberate deviation from the reference, whose clamped sampler returns a rounding residue of up to
     ~1e-2 grey levels outside a view's image; the skip test samples each 64 x 8 tile at six points and is not a proof),
-    or None (every view evaluated everywhere: the reference's arithmetic at every pixel)."""
-    return _render_average(imgs, source, T, hc, wc, mode, out, footprint, gains, u8=False, clip=False)
+    or None (every view evaluated everywhere: the reference's arithmetic at every pixel).
+    fusion (here and in the _u8, _clip, _clip_u8 and _nv12 forms): 'AVERAGE', the reference's chained a a / (a + b + 1e-6), or
+    'FEATHER', border-distance weights over all views at once (_fusion_bit) -- with it a footprint changes nothing at all."""
+    return _render_average(imgs, source, T, hc, wc, mode, out, footprint, gains, u8=False, clip=False, fusion=fusion)
 
 
-def render_average_u8(frames, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
+def render_average_u8(frames, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None, fusion='AVERAGE'):
     """The fused AVERAGE render straight from decoded uint8 frames to the uint8 video frame: frames = list of 2|3 device
     tensors [h,w,3] uint8 (cv2 channel order); -> uint8 [hc,wc,3] = `.astype(np.uint8)` of the fused values.  Equal,
     bit for bit, to ingest (uint8 -> fp32 planes) + render_average + canvas_to_u8; the fp32 planes and canvas are never
     written."""
-    return _render_average(frames, source, T, hc, wc, mode, out, footprint, gains, u8=True, clip=False)
+    return _render_average(frames, source, T, hc, wc, mode, out, footprint, gains, u8=True, clip=False, fusion=fusion)
 
 
-def render_average_clip(views, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
+def render_average_clip(views, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None, fusion='AVERAGE'):
     """A whole clip in one launch: views = list of 2|3 contiguous device tensors [n,3,h,w]; source [n,V,63,2];
     T [n,V,2,66]; footprint [n, ss_render_footprint_floats] | None -> [n,3,hc,wc].  Bit-identical to n render_average calls."""
-    return _render_average(views, source, T, hc, wc, mode, out, footprint, gains, u8=False, clip=True)
+    return _render_average(views, source, T, hc, wc, mode, out, footprint, gains, u8=False, clip=True, fusion=fusion)
 
 
-def render_average_clip_u8(views, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None):
+def render_average_clip_u8(views, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, gains=None, fusion='AVERAGE'):
     """The same from decoded uint8 clips: views = list of 2|3 contiguous device tensors [n,h,w,3] uint8 -> uint8 [n,hc,wc,3]."""
-    return _render_average(views, source, T, hc, wc, mode, out, footprint, gains, u8=True, clip=True)
+    return _render_average(views, source, T, hc, wc, mode, out, footprint, gains, u8=True, clip=True, fusion=fusion)
 
 
 def tps_warp_views(imgs, source, T, hc, wc, mode='NORMAL'):
@@ -1099,12 +1122,13 @@ def bgr_to_nv12(bgr, out=None):
     return out[0] if single else out
 
 
-def render_average_nv12(frames, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, out_format='bgr'):
+def render_average_nv12(frames, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, out_format='bgr', fusion='AVERAGE'):
     """render_average_u8 from decoded NV12 frames: frames = list of 2|3 NV12 device tensors [H*3/2,W]; out_format 'bgr' -> the uint8
     video frame [hc,wc,3] (byte for byte render_average_u8 of the converted frames), 'nv12' -> that frame as NV12 [hc*3/2,wc]
     (byte for byte bgr_to_nv12 of it; hc, wc even).  Neither the converted frames nor, for 'nv12', the BGR frame are written."""
     if out_format not in ('bgr', 'nv12'):
         raise ValueError("out_format must be 'bgr' or 'nv12'")
+    fuse = _fusion_bit(fusion)
     ys, uvs, pitches, _, h, w = _nv12_views(list(frames))
     dev = frames[0].device
     fp, fpn = _fp_args(footprint)
@@ -1122,7 +1146,7 @@ def render_average_nv12(frames, source, T, hc, wc, mode='NORMAL', out=None, foot
             raise ValueError('render_average_nv12: out must be NV12 [%d,%d], got %s' % (hc // 2 * 3, wc, tuple(out.shape)))
         o_y, o_uv = _nv12_ptr(out), _nv12_ptr(out, hc * o_pitch)
     H.call('ss_render_average_nv12', ys, uvs, pitches, H.dptr(_f(source)), H.dptr(T), fp, fpn, o_y, o_uv, o_pitch,
-           int(out_format == 'nv12'), len(frames), h, w, hc, wc, MODES[mode], H.stream())
+           int(out_format == 'nv12'), len(frames), h, w, hc, wc, MODES[mode] | fuse, H.stream())
     return out
 
 

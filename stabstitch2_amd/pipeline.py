@@ -502,7 +502,7 @@ def _linear_clip(clips, src, T, hc, wc, warp_mode, out):
 def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, prescaled=False, bbox=None,
                   size=None):
     """img_lists: V lists (or tensors [N,3,H,W]) of HR frames (0..255); meshes: V tensors [1,N,7,9,2].
-    -> (frames [N,3,Hc,Wc] device tensor, Hc, Wc).  AVERAGE fusion of clips held as tensors is ONE launch for the whole
+    -> (frames [N,3,Hc,Wc] device tensor, Hc, Wc).  AVERAGE and FEATHER fusion of clips held as tensors is ONE launch for the whole
     clip (ops.render_average_clip); lists of separate frames and LINEAR fusion go frame by frame.
     With SKIP_OUTSIDE (default) a view contributes exactly 0 on canvas tiles it cannot reach, where the reference's
     clamped sampler leaves a rounding residue of <~ 1e-2 grey levels (ops.render_average)."""
@@ -514,18 +514,20 @@ def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', 
     hc, wc, src, T = render_plan(meshes, img_h, img_w, prescaled, bbox, size)
     if out is None or tuple(out.shape) != (n, 3, hc, wc) or not out.is_contiguous():
         out = torch.empty((n, 3, hc, wc), device=dev, dtype=torch.float32)      # (a buffer of another canvas is not reused)
-    fp = ops.render_footprints(src, T, img_h, img_w, hc, wc) if (SKIP_OUTSIDE and fusion_mode == 'AVERAGE') else None
+    fused = ops.fused_render(fusion_mode)                # AVERAGE | FEATHER: the one-launch render, the formula its `fusion`
+    fp = ops.render_footprints(src, T, img_h, img_w, hc, wc) if (SKIP_OUTSIDE and fused) else None
     clips = [_as_clip(x, n) for x in img_lists]
-    if fusion_mode == 'AVERAGE' and all(c is not None for c in clips):
-        ops.render_average_clip(clips, src, T, hc, wc, warp_mode, out=out, footprint=fp)
+    if fused and all(c is not None for c in clips):
+        ops.render_average_clip(clips, src, T, hc, wc, warp_mode, out=out, footprint=fp, fusion=fusion_mode)
         return out, hc, wc
     if fusion_mode == 'LINEAR' and LINEAR_CLIP and all(c is not None for c in clips):
         _linear_clip(clips, src, T, hc, wc, warp_mode, out)
         return out, hc, wc
     for i in range(n):
         imgs = [img_lists[k][i].to(dev, non_blocking=True) for k in range(v)]
-        if fusion_mode == 'AVERAGE':
-            ops.render_average(imgs, src[i], T[i], hc, wc, warp_mode, out=out[i], footprint=None if fp is None else fp[i])
+        if fused:
+            ops.render_average(imgs, src[i], T[i], hc, wc, warp_mode, out=out[i], footprint=None if fp is None else fp[i],
+                               fusion=fusion_mode)
         else:
             w = ops.tps_warp_views(imgs, src[i], T[i], hc, wc, warp_mode)            # [V,4,Hc,Wc]
             if v == 2:
@@ -627,14 +629,14 @@ U8_FUSED = os.environ.get('SS_U8_FUSED', '1') == '1'
 
 
 def _u8_fused(fusion_mode):
-    return U8_FUSED and (fusion_mode == 'AVERAGE' or (fusion_mode == 'LINEAR' and LINEAR_CLIP))
+    return U8_FUSED and (ops.fused_render(fusion_mode) or (fusion_mode == 'LINEAR' and LINEAR_CLIP))
 
 
 @torch.no_grad()
 def render_frames_u8(frame_lists, meshes, warp_mode='NORMAL', out=None, bbox=None, size=None, prescaled=False,
                      fusion_mode='AVERAGE'):
     """frame_lists: V device tensors [N,H,W,3] uint8; meshes: V tensors [1,N,7,9,2] -> (uint8 [N,Hc,Wc,3], Hc, Wc):
-    `render_frames(..., fusion_mode)` followed by `to_video_frames`, fused: one launch for the clip (AVERAGE), three / four
+    `render_frames(..., fusion_mode)` followed by `to_video_frames`, fused: one launch for the clip (AVERAGE, FEATHER), three / four
     (LINEAR: the warped planes are fp32 either way, the blend writes the video frame)."""
     n = meshes[0].shape[1]
     img_h, img_w = frame_lists[0].shape[1], frame_lists[0].shape[2]
@@ -648,7 +650,7 @@ def render_frames_u8(frame_lists, meshes, warp_mode='NORMAL', out=None, bbox=Non
         return out, hc, wc
     fp = ops.render_footprints(src, T, img_h, img_w, hc, wc) if SKIP_OUTSIDE else None
     ops.render_average_clip_u8([f if f.is_contiguous() else f.contiguous() for f in frame_lists], src, T, hc, wc, warp_mode,
-                               out=out, footprint=fp)
+                               out=out, footprint=fp, fusion=fusion_mode)
     return out, hc, wc
 
 
