@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build libstabstitch_hip.so for gfx950 (MI355X) in-tree.
 #   stabstitch2_amd/csrc/build.sh           -> stabstitch2_amd/libstabstitch_hip.so         (the product)
+#                                              stabstitch2_amd/libstabstitch_blend.so       (MULTIBAND fusion, blend.hip)
 #   stabstitch2_amd/csrc/build.sh tuning    -> tools/libstabstitch_hip_tuning.so            (-DSS_TUNING: adds the
 #       ss_debug_set / ss_debug_ptr knobs, the per-workgroup s_memtime stamps of tools/diag_*.py and the comparison kernels
 #       that tests and tools/ab_*.py measure the product against; concluded experiments are not kept in it: LAB_NOTES.md,
@@ -21,3 +22,9 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
     "$HERE/frameio.hip" "$HERE/stem.hip" "$HERE/wino43.hip" \
     -o "$OUT"
 echo "built $OUT"
+if [ "$1" != "tuning" ]; then
+    # MULTIBAND fusion: a library of its own (include/stabstitch_blend.h), so that the surface of libstabstitch_hip.so stays as it is
+    BLEND="$HERE/../libstabstitch_blend.so"
+    "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden "$HERE/blend.hip" -o "$BLEND"
+    echo "built $BLEND"
+fi

@@ -382,10 +382,22 @@ class _Stitcher:
     and the window-fill push; one with S canvases also _regrown / _render_direct / overflow_report."""
     _U8_STEADY = True        # push_u8 in the steady state: the resize writes the graph's LR inputs, the render samples the uint8 frames
     _LINEAR_DIRECT = True    # may LINEAR fusion take the direct render (DIRECT_LINEAR)?  Not with two pushes in flight (_TwoInFlight)
+    _MULTIBAND = False       # does the class render MULTIBAND fusion?  (one canvas, one push in flight: the two plain stitchers)
 
     def __init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only=False, canvases=1,
-                 viewport=None, zoom_limit=2.0, exposure=None):
+                 viewport=None, zoom_limit=2.0, exposure=None, bands=None):
         self.exposure = _exposure_params(exposure, meshes_only)      # None: no launch, buffer or graph node of it exists
+        # MULTIBAND (ops.render_multiband: the existing warp + the pyramid blend): always launched by the push or the batch, on
+        # the caller's frames, behind a graph that ends with the splines and the watcher -- as the direct LINEAR render is
+        self.bands = None
+        if fusion_mode == 'MULTIBAND':
+            if self.exposure is not None:
+                raise ValueError("exposure= has no fusion_mode='MULTIBAND' form: the warp it uses takes no gains")
+            if not meshes_only and not self._MULTIBAND:
+                raise ValueError("%s has no fusion_mode='MULTIBAND': OnlineStitcher and ThreeViewOnlineStitcher do" % type(self).__name__)
+            self.bands = ops.check_bands(ops.MULTIBAND_BANDS if bands is None else bands)
+        elif bands is not None:
+            raise ValueError("bands= belongs to fusion_mode='MULTIBAND', got %r" % (fusion_mode,))
         if grow not in ('never', 'recapture', 'refit'):
             raise ValueError("grow must be 'never', 'recapture' or 'refit'")
         if viewport is not None:
@@ -421,8 +433,8 @@ class _Stitcher:
             raise ValueError('SS_RENDER_EPS_FOLD has no FEATHER form')
         self.use_graph = use_graph
         self.meshes_only = bool(meshes_only)
-        direct = self._fused or (fusion_mode == 'LINEAR' and DIRECT_LINEAR and self._LINEAR_DIRECT)
-        self._direct_render = bool(DIRECT_RENDER and use_graph and direct and not self.meshes_only)
+        direct = self._fused or (fusion_mode == 'LINEAR' and DIRECT_LINEAR and self._LINEAR_DIRECT) or fusion_mode == 'MULTIBAND'
+        self._direct_render = bool((DIRECT_RENDER or fusion_mode == 'MULTIBAND') and use_graph and direct and not self.meshes_only)
         self._lin_ws = {}                # direct LINEAR render: chunk -> ((canvas sizes, views), workspace), re-made when a canvas changes
         # overflow of the fixed canvas(es), and the device-side refit of their boxes; meshes_only: never started
         self.watch = _CanvasWatch(canvases, margin, self.dev, viewport, grow == 'refit', zoom_limit)
@@ -624,9 +636,11 @@ class _Stitcher:
                 return None
             return ops.render_average(imgs, src, T, self.hc, self.wc, self.warp_mode, out=out, footprint=fp, gains=gains,
                                       fusion=self.fusion_mode)
-        if out is _DEFER:                    # LINEAR: the graph ends with the splines and the watcher
+        if out is _DEFER:                    # LINEAR, MULTIBAND: the graph ends with the splines and the watcher
             self._deferred = (src, T, None)
             return None
+        if self.fusion_mode == 'MULTIBAND':  # the window fill, and every push without a graph
+            return ops.render_multiband(list(imgs), src, T, self.hc, self.wc, self.warp_mode, self.bands, out=out, u8=False)
         if gains is not None:                # LINEAR with exposure: the fused render at n = 1 (bit-identical to the chain below)
             shp = (1, 3, self.h, self.w)
             return self._render_linear([f.reshape(shp) for f in imgs], src[None], T[None], [(self.hc, self.wc)], gains=gains,
@@ -650,6 +664,9 @@ class _Stitcher:
         if self.exposure is not None:        # the gains through this frame, from the caller's frames, in front of the render launch
             shp = (1, self.h, self.w, 3) if u8 else (1, 3, self.h, self.w)
             gains = self._exposure_gains([f.reshape(shp) for f in imgs], self._exp_fp)
+        if self.fusion_mode == 'MULTIBAND':  # uint8 frames in -> the uint8 video frame out of the last collapse pass
+            shp = (self.h, self.w, 3) if u8 else (3, self.h, self.w)
+            return [ops.render_multiband([f.reshape(shp) for f in imgs], src, T, self.hc, self.wc, self.warp_mode, self.bands)]
         if self.fusion_mode == 'LINEAR':     # the fused three / four launches at n = 1, uint8 frames in -> the uint8 video frame out
             shp = (1, self.h, self.w, 3) if u8 else (1, 3, self.h, self.w)
             return self._render_linear([f.reshape(shp) for f in imgs], src[None], T[None], [(self.hc, self.wc)], gains=gains)
@@ -678,7 +695,8 @@ class _Stitcher:
         configuration, and the window fill, goes ingest_nv12 -> _push -> canvas_to_u8 (-> bgr_to_nv12)."""
         with ops.deterministic(self.deterministic):
             # (the NV12 render has no SS_RENDER_EPS_FOLD form: with that opt-in set the fp32 route keeps the two formats equal)
-            if self._u8_steady() and not (ops.RENDER_EPS_FOLD and self._fused):
+            # (MULTIBAND has no NV12 source or sink: ingest, push, the sinks)
+            if self._u8_steady() and not (ops.RENDER_EPS_FOLD and self._fused) and self.fusion_mode != 'MULTIBAND':
                 return self._push_static(nv12=(imgs, out))
             v = len(imgs)
             hr = torch.empty((v, 3, self.h, self.w), device=self.dev)
@@ -798,7 +816,13 @@ class _Stitcher:
         views = [f.contiguous() for f in imgs]
         # exposure: the k frames' gains in one update (stream order, bit-identical to k single-frame updates)
         gains = None if self.exposure is None else self._exposure_gains(views, deferred[3])
-        if self._fused:
+        if self.fusion_mode == 'MULTIBAND':  # pipeline.MULTIBAND_FRAMES frames per call: each in the launches of one
+            k, c = src.shape[0], pipeline.MULTIBAND_FRAMES
+            out = torch.empty((k, self.hc, self.wc, 3) if u8 else (k, 3, self.hc, self.wc), device=self.dev, dtype=views[0].dtype)
+            for s in range(0, k, c):
+                ops.render_multiband([f[s:s + c] for f in views], src[s:s + c], T[s:s + c], self.hc, self.wc, self.warp_mode, self.bands,
+                                     out=out[s:s + c])
+        elif self._fused:
             render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
             out = render(views, src, T, self.hc, self.wc, self.warp_mode, footprint=fp, gains=gains, fusion=self.fusion_mode)
         else:
@@ -807,9 +831,15 @@ class _Stitcher:
 
 
 class OnlineStitcher(_Stitcher):
+    _MULTIBAND = True
+
     def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 use_graph=True, grow='never', meshes_only=False, deterministic=False, viewport=None, zoom_limit=2.0, exposure=None):
+                 use_graph=True, grow='never', meshes_only=False, deterministic=False, viewport=None, zoom_limit=2.0, exposure=None,
+                 bands=None):
         """canvas: optional (wmin, wmax, hmin, hmax) in HR pixels (e.g. the offline bbox).
+        fusion_mode: 'AVERAGE', 'FEATHER', 'LINEAR' or 'MULTIBAND' -- the Laplacian-pyramid blend of `bands` levels
+        (0..6, default 5; only with MULTIBAND): the existing warp of B, G, R and a weight plane, then the pyramid launches, always
+        launched by the push on the caller's frames (the graph ends with the splines); not with exposure=.
         exposure: None (default: nothing of it exists), True (ops.ExposureParams() defaults) or an ops.ExposureParams -- exposure
         compensation of the two cameras: every frame handed out (the first window's seven, in order, included) is rendered with
         per-view, per-channel gains estimated on that frame's overlap (the footprint lattice: DESIGN.md, "Exposure compensation")
@@ -838,7 +868,7 @@ class OnlineStitcher(_Stitcher):
         push_many takes one refit per call, behind the batch's watcher: a drift inside one call can crop up to k counted frames."""
         _exposure_params(exposure, meshes_only)
         _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only,
-                           viewport=viewport, zoom_limit=zoom_limit, exposure=exposure)
+                           viewport=viewport, zoom_limit=zoom_limit, exposure=exposure, bands=bands)
         self.deterministic = bool(deterministic)
         self.last_meshes = None
         self.bbox = None if canvas is None else torch.tensor(canvas, dtype=torch.float32, device=self.dev)
@@ -1146,6 +1176,7 @@ class _TwoInFlight:
     order on the ONE stream sb -- the box push t rewrites is the box push t + 1 reads.  grow='recapture' is not offered.
     A subclass provides _pipe_alloc / _pipe_load / _run_a / _run_b (and _pipe_empty for S streams)."""
     _LINEAR_DIRECT = False
+    _MULTIBAND = False       # (MULTIBAND is launched by the push on the caller's frames: not with two pushes in flight)
 
     def _pipe_init(self):
         if not L.QUAD:
@@ -1745,18 +1776,20 @@ class ThreeViewOnlineStitcher(_Stitcher):
     re-fixes the OUTPUT canvas (and captures the graph again) when a mesh comes within half the margin of its edge.  `viewport` and
     grow='refit' as in OnlineStitcher, on the OUTPUT box only: the first canvas is a normalisation frame and stays as it is.
     `push_many` / `push_many_u8` take k consecutive triples per call (see OnlineStitcher.push_many)."""
+    _MULTIBAND = True
 
     def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 use_graph=True, grow='never', deterministic=False, viewport=None, zoom_limit=2.0, exposure=None):
+                 use_graph=True, grow='never', deterministic=False, viewport=None, zoom_limit=2.0, exposure=None, bands=None):
         """deterministic: every push under the conv engine's geometry-only kernel policy (ops.deterministic; as OnlineStitcher's):
-        push_many's frames then equal single pushes' bit for bit."""
+        push_many's frames then equal single pushes' bit for bit.
+        fusion_mode='MULTIBAND' and bands=: as OnlineStitcher's, over the three views at once."""
         _no_exposure(type(self).__name__, exposure)
         # the two pair chains as a batch of two streams over the CHAIN of three views: every launch serves both pairs, view 2's
         # trunk features are computed once
         self.chains = MultiOnlineStitcher(nets, height, width, streams=2, margin=margin, warp_mode=warp_mode, fusion_mode=fusion_mode,
                                           use_graph=False, meshes_only=True, deterministic=deterministic, chain=True)
         _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, viewport=viewport,
-                           zoom_limit=zoom_limit)
+                           zoom_limit=zoom_limit, bands=bands)
         self.deterministic = bool(deterministic)
         box = lambda b: None if b is None else torch.tensor(b, dtype=torch.float32, device=self.dev)
         self.bbox, self.first_canvas = box(canvas), box(first_canvas)

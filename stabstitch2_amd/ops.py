@@ -1255,6 +1255,122 @@ def render_linear_frames(views, source, T, sizes, mode='NORMAL', outs=None, ws=N
     return list(outs)
 
 
+# ------------------------------------------------------------------ MULTIBAND fusion (libstabstitch_blend.so)
+MULTIBAND_BANDS = 5
+_weight_planes = {}
+
+
+def multiband_weight_plane(h, w, device):
+    """The plane that decides MULTIBAND's seam, [h,w] fp32: min(x + 1, w - x) * min(y + 1, h - y) (small integers, exact).  Warped next
+    to B, G, R, the view with the larger value owns a canvas pixel.  Built once per size and device."""
+    device = torch.device(device)
+    key = (int(h), int(w), device.type, device.index)
+
+    def build():
+        x = torch.arange(w, dtype=torch.float32)
+        y = torch.arange(h, dtype=torch.float32)
+        return (torch.minimum(x + 1, w - x)[None, :] * torch.minimum(y + 1, h - y)[:, None]).contiguous().to(device)
+    if device.type != 'cuda':
+        return build()
+    b = _weight_planes.get(key)
+    if b is None:
+        b = _weight_planes[key] = _Built(build, device, 'the MULTIBAND weight plane')
+    return b.get(device)
+
+
+def check_bands(bands, hc=None, wc=None):
+    """ValueError for a band count the blend refuses (on this canvas, when one is given)."""
+    from . import _blend as B
+    if not isinstance(bands, int) or isinstance(bands, bool) or not 0 <= bands <= B.MAX_BANDS:
+        raise ValueError('bands must be an integer 0..%d, got %r' % (B.MAX_BANDS, bands))
+    if hc is not None and B.lib().ssb_multiband_workspace_floats(1, 2, int(hc), int(wc), bands) < 0:
+        raise ValueError('MULTIBAND: %d bands need every reduced level of the %d x %d canvas to be at least 3 pixels a side'
+                         % (bands, hc, wc))
+    return bands
+
+
+def multiband_workspace(frames, views, hc, wc, bands, device):
+    """The workspace of multiband_blend for `frames` frames in one call (ssb_multiband_workspace_floats)."""
+    from . import _blend as B
+    need = int(B.lib().ssb_multiband_workspace_floats(frames, views, hc, wc, bands))
+    if need < 0:
+        raise ValueError('multiband_blend: 2|3 views, 0..%d bands, every reduced level at least 3 pixels a side; got %d frames of %d '
+                         'views on %d x %d with %r bands' % (B.MAX_BANDS, frames, views, hc, wc, bands))
+    return torch.empty(need, device=device, dtype=torch.float32)
+
+
+def multiband_blend(P, bands=MULTIBAND_BANDS, out=None, ws=None, u8=False):
+    """Laplacian-pyramid blend of warped views: P [V,5,hc,wc] (or [n,V,5,hc,wc]: n frames in the launches of one) = per view the warped
+    B, G, R, the warped multiband_weight_plane and the ones-mask, as tps_warp(.., with_mask=True) writes them -> [3,hc,wc] fp32
+    ([n,3,hc,wc]), or with u8 the video frame [hc,wc,3] uint8 ([n,hc,wc,3]) = canvas_to_u8 of the same values.  2 * bands + 2 launches."""
+    from . import _blend as B
+    clip = P.dim() == 5
+    if P.dim() not in (4, 5) or P.shape[-3] != 5:
+        raise ValueError('P must be [V,5,hc,wc] or [n,V,5,hc,wc], got %s' % (tuple(P.shape),))
+    n = P.shape[0] if clip else 1
+    v, hc, wc = P.shape[-4], P.shape[-2], P.shape[-1]
+    if ws is None:
+        ws = multiband_workspace(n, v, hc, wc, bands, P.device)
+    shape = ((n,) if clip else ()) + ((hc, wc, 3) if u8 else (3, hc, wc))
+    dt = torch.uint8 if u8 else torch.float32
+    if out is None:
+        out = torch.empty(shape, device=P.device, dtype=dt)
+    if tuple(out.shape) != shape:
+        raise ValueError('out must be %s, got %s' % (shape, tuple(out.shape)))
+    B.call('ssb_multiband_blend_u8' if u8 else 'ssb_multiband_blend', H.dptr(P), H.dptr(out, dtype=dt), H.dptr(ws), ws.numel(), n, v, hc, wc,
+           bands, H.stream())
+    return out
+
+
+def multiband_stack(imgs):
+    """What MULTIBAND warps: imgs = list of V views, each fp32 planes [3,h,w] / [1,3,h,w] / [n,3,h,w] or decoded uint8 frames [h,w,3] /
+    [n,h,w,3] (through the existing ingest) -> U [n*V,4,h,w], frame-major: B, G, R and the weight plane."""
+    v = len(imgs)
+    u8 = imgs[0].dtype == torch.uint8
+    imgs = [i if i.dim() == 4 else i[None] for i in imgs]
+    if u8:
+        n, h, w, _ = imgs[0].shape
+        want = (n, h, w, 3)
+    else:
+        n, _, h, w = imgs[0].shape
+        want = (n, 3, h, w)
+    if any(tuple(i.shape) != want or i.dtype != imgs[0].dtype for i in imgs):
+        raise ValueError('the views of one MULTIBAND render must have one shape and type, got %s' % [tuple(i.shape) for i in imgs])
+    dev = imgs[0].device
+    U = torch.empty((n * v, 4, h, w), device=dev, dtype=torch.float32)
+    Uv = U.view(n, v, 4, h, w)
+    Uv[:, :, 3] = multiband_weight_plane(h, w, dev)
+    for k, img in enumerate(imgs):
+        if u8 and n == 1:                # straight into the stack: U[k, 0:3] is contiguous
+            H.call('ss_ingest_u8', _u8ptr(img), H.dptr(U[k, 0:3]), None, 1, h, w, 0, 0, H.stream())
+        elif u8:
+            hr = torch.empty((n, 3, h, w), device=dev, dtype=torch.float32)
+            H.call('ss_ingest_u8', _u8ptr(img), H.dptr(hr), None, n, h, w, 0, 0, H.stream())
+            Uv[:, k, 0:3] = hr
+        else:
+            Uv[:, k, 0:3] = img
+    return U
+
+
+def render_multiband(imgs, source, T, hc, wc, mode='NORMAL', bands=MULTIBAND_BANDS, out=None, ws=None, u8=None):
+    """MULTIBAND fusion of one frame or of n: imgs as multiband_stack takes them; source [V,63,2] / [n,V,63,2]; T [V,2,66] / [n,V,2,66]
+    -> [3,hc,wc] / [n,3,hc,wc] fp32, or the uint8 video frame(s) [hc,wc,3] / [n,hc,wc,3] (u8: default, what the input is).  One warp
+    launch of the existing ss_tps_warp_mask_nchw over every (frame, view) and four planes, then multiband_blend: exactly
+    `multiband_blend(tps_warp(multiband_stack(imgs), source, T, hc, wc, mode, with_mask=True))`."""
+    v = len(imgs)
+    clip = source.dim() == 4
+    if u8 is None:
+        u8 = imgs[0].dtype == torch.uint8
+    check_bands(bands, hc, wc)
+    U = multiband_stack(imgs)
+    n = U.shape[0] // v
+    if (clip and source.shape[0] != n) or (not clip and n != 1) or source.shape[-3] != v:
+        raise ValueError('source %s does not match %d frames of %d views' % (tuple(source.shape), n, v))
+    P = tps_warp(U, _f(source).view(n * v, 63, 2), T.view(n * v, 2, 66), hc, wc, mode, with_mask=True)
+    P = P.view(n, v, 5, hc, wc) if clip else P
+    return multiband_blend(P, bands, out=out, ws=ws, u8=u8)
+
+
 def mesh_bbox(meshes, img_h, img_w, bbox=None):
     """meshes: list of LR-scale tensors [...,2] -> device tensor [4] = wmin, wmax, hmin, hmax (HR px).
     bbox: an existing box to fold these meshes into (in place)."""

@@ -498,14 +498,44 @@ def _linear_clip(clips, src, T, hc, wc, warp_mode, out):
     return out
 
 
+# MULTIBAND fusion (ops.render_multiband): frames per call -- the warped planes and the pyramids of one 720p frame are about 160 MB
+MULTIBAND_FRAMES = 8
+
+
+def check_fusion(fusion_mode, bands=None):
+    """ValueError for bands= without MULTIBAND, or for a band count the blend does not have."""
+    if bands is not None:
+        if fusion_mode != 'MULTIBAND':
+            raise ValueError('bands= belongs to fusion_mode=\'MULTIBAND\', got %r' % (fusion_mode,))
+        ops.check_bands(bands)
+
+
+def _multiband_frames(img_lists, src, T, hc, wc, warp_mode, bands, out, dev):
+    """Clips held as tensors go in chunks of MULTIBAND_FRAMES frames (the launches of one frame each), lists frame by frame."""
+    n = src.shape[0]
+    clips = [_as_clip(x, n) for x in img_lists]
+    if all(c is not None for c in clips):
+        for s in range(0, n, MULTIBAND_FRAMES):
+            e = min(s + MULTIBAND_FRAMES, n)
+            ops.render_multiband([c[s:e] for c in clips], src[s:e], T[s:e], hc, wc, warp_mode, bands, out=out[s:e])
+        return out
+    for i in range(n):
+        ops.render_multiband([x[i].to(dev, non_blocking=True) for x in img_lists], src[i], T[i], hc, wc, warp_mode, bands, out=out[i],
+                             u8=False)
+    return out
+
+
 @torch.no_grad()
 def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, prescaled=False, bbox=None,
-                  size=None):
+                  size=None, bands=None):
     """img_lists: V lists (or tensors [N,3,H,W]) of HR frames (0..255); meshes: V tensors [1,N,7,9,2].
     -> (frames [N,3,Hc,Wc] device tensor, Hc, Wc).  AVERAGE and FEATHER fusion of clips held as tensors is ONE launch for the whole
     clip (ops.render_average_clip); lists of separate frames and LINEAR fusion go frame by frame.
     With SKIP_OUTSIDE (default) a view contributes exactly 0 on canvas tiles it cannot reach, where the reference's
-    clamped sampler leaves a rounding residue of <~ 1e-2 grey levels (ops.render_average)."""
+    clamped sampler leaves a rounding residue of <~ 1e-2 grey levels (ops.render_average).
+    MULTIBAND fusion (bands= pyramid levels, default ops.MULTIBAND_BANDS): one warp launch and the pyramid launches per chunk of
+    MULTIBAND_FRAMES frames of a clip, or per frame of a list (ops.render_multiband)."""
+    check_fusion(fusion_mode, bands)
     v = len(img_lists)
     dev = meshes[0].device
     n = meshes[0].shape[1]
@@ -514,6 +544,9 @@ def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', 
     hc, wc, src, T = render_plan(meshes, img_h, img_w, prescaled, bbox, size)
     if out is None or tuple(out.shape) != (n, 3, hc, wc) or not out.is_contiguous():
         out = torch.empty((n, 3, hc, wc), device=dev, dtype=torch.float32)      # (a buffer of another canvas is not reused)
+    if fusion_mode == 'MULTIBAND':
+        _multiband_frames(img_lists, src, T, hc, wc, warp_mode, ops.MULTIBAND_BANDS if bands is None else bands, out, dev)
+        return out, hc, wc
     fused = ops.fused_render(fusion_mode)                # AVERAGE | FEATHER: the one-launch render, the formula its `fusion`
     fp = ops.render_footprints(src, T, img_h, img_w, hc, wc) if (SKIP_OUTSIDE and fused) else None
     clips = [_as_clip(x, n) for x in img_lists]
@@ -547,7 +580,8 @@ def get_stable_sqe(img1_list, img2_list, smooth_mesh1, smooth_mesh2, warp_mode, 
 
 
 @torch.no_grad()
-def run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', to_host=False, out=None, deterministic=False):
+def run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', to_host=False, out=None, deterministic=False,
+                 bands=None):
     """-> (frames, Hc, Wc, smooth_mesh1, smooth_mesh2); frames = device tensor [N,3,Hc,Wc]
     (or list of HWC ndarrays with to_host=True).  out: the frames tensor of a previous call to render into; it is reused
     when the canvas still has that size (same-size clips of one stream), else a new one is allocated.
@@ -555,7 +589,7 @@ def run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode='NORMAL', fusion_mode='AVER
     frames share its launches -- resident clip == chunked passes == stream."""
     with ops.deterministic(deterministic):
         acc = estimate_meshes(nets, lr1, lr2)
-    frames, hc, wc = render_frames([hr1, hr2], [acc['smooth_mesh1'], acc['smooth_mesh2']], warp_mode, fusion_mode, out=out)
+    frames, hc, wc = render_frames([hr1, hr2], [acc['smooth_mesh1'], acc['smooth_mesh2']], warp_mode, fusion_mode, out=out, bands=bands)
     if to_host:
         host = frames.permute(0, 2, 3, 1).cpu().numpy()
         frames = [host[i] for i in range(host.shape[0])]
@@ -583,13 +617,14 @@ def three_view_compose(w12_m1, w12_m2, w23_m1, w23_m2, img_h, img_w, first_canva
 
 
 @torch.no_grad()
-def three_view_render(img1, img2, img3, mesh1, middle, mesh3, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None):
+def three_view_render(img1, img2, img3, mesh1, middle, mesh3, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, bands=None):
     """Meshes are HR-scale canvas pixels here (output of three_view_compose)."""
-    return render_frames([img1, img2, img3], [mesh1, middle, mesh3], warp_mode, fusion_mode, out=out, prescaled=True)
+    return render_frames([img1, img2, img3], [mesh1, middle, mesh3], warp_mode, fusion_mode, out=out, prescaled=True, bands=bands)
 
 
 @torch.no_grad()
-def run_three_view(hr1, hr2, hr3, lr1, lr2, lr3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, deterministic=False):
+def run_three_view(hr1, hr2, hr3, lr1, lr2, lr3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, deterministic=False,
+                   bands=None):
     # the middle view's TemporalNet motions and SpatialNet trunk features are computed once and reused by pair (2,3)
     with ops.deterministic(deterministic):
         a12 = estimate_meshes(nets, lr1, lr2, keep_spatial_cache2=True)
@@ -597,7 +632,7 @@ def run_three_view(hr1, hr2, hr3, lr1, lr2, lr3, nets, warp_mode='NORMAL', fusio
     img_h, img_w = hr1[0].shape[-2:]
     m1, mid, m3 = three_view_compose(a12['smooth_mesh1'], a12['smooth_mesh2'], a23['smooth_mesh1'],
                                      a23['smooth_mesh2'], img_h, img_w)
-    frames, hc, wc = three_view_render(hr1, hr2, hr3, m1, mid, m3, warp_mode, fusion_mode, out=out)
+    frames, hc, wc = three_view_render(hr1, hr2, hr3, m1, mid, m3, warp_mode, fusion_mode, out=out, bands=bands)
     return frames, hc, wc, m1, mid, m3
 
 
