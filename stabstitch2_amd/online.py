@@ -364,6 +364,190 @@ class _CanvasWatch:
         self._event = ev
 
 
+# ------------------------------------------------------------------ how a fusion mode renders
+class _Deferred(collections.namedtuple('_Deferred', 'src T fp efp')):
+    """What a step that does not render itself leaves for the push's render: the control points and splines (src, T) of one frame
+    ([V,63,2], [V,2,66]) or of n ([n,V,63,2], [n,V,2,66]), the footprint row(s) fp the render skips tiles by (None: it skips none) and
+    the footprint rows efp [n, .] the exposure update samples (None: no exposure compensation)."""
+    __slots__ = ()
+
+
+class _Render:
+    """How ONE fusion mode renders in the streaming stitchers: built once by _Stitcher.__init__ (`mode`) from the mode, the switches
+    and the class, and the only code that knows it.  `direct`: does the steady-state push of this stitcher launch the render itself,
+    outside the graph, on the caller's frames?  `skip`: does the render skip tiles by footprint?  `nv12`: does it sample NV12 frames
+    (and hand NV12 out)?  `ragged`: is its direct render of S streams ONE render over canvases of any sizes, into fresh tensors?
+    A kind provides, with left = the step's _Deferred and hc, wc = the canvas size (it changes under grow='recapture'):
+      render_into(imgs, left, hc, wc, gains, out)      one frame inside the step (window fill, use_graph=False, no direct render)
+      frame(imgs, left, hc, wc, u8, gains)             the push's own render of one frame: fp32 planes, or uint8 in -> uint8 out
+      frame_nv12(imgs, left, hc, wc, out)              the same from NV12 frames -> the uint8 frame or NV12 (`out`)
+      batch(views, left, hc, wc, u8, gains, out)       n frames on canvases of one size -> [n, ...]
+      streams(imgs, left, sizes, u8)                   S frames on S canvases: left one record (see `ragged`; or the canvases share
+                                                       a size) or one per stream -> S frames
+    It holds no reference to its stitcher (a cycle would keep the stitcher's buffers until the collector runs)."""
+    skip = False
+    nv12 = True
+    ragged = False
+
+    def __init__(self, st):
+        self.fusion, self.warp, self.h, self.w, self.dev = st.fusion_mode, st.warp_mode, st.h, st.w, st.dev
+        self.exposure = st.exposure is not None
+        self.direct = bool(self._takes_direct(st) and st.use_graph and not st.meshes_only)
+
+    def needs_footprints(self):
+        """Does the captured step end with a footprint launch?  (exposure: the footprint lattice is the estimator's sample set, made
+        whatever the fusion is)"""
+        return self.skip or self.exposure
+
+    def carry(self, src, watch, fit):
+        """The overflow watcher watch = (guard, watch_i, watch_f) has not seen src [n,V,63,2] yet (fit, grow='refit': the ops.CanvasFit
+        the launch that carries it re-fixes the boxes with): -> (watch, fit) for the footprint launch where the step has one; else it
+        runs here, as a launch of its own -> (None, None)."""
+        if watch is None or self.needs_footprints():
+            return watch, fit
+        ops.canvas_watch(src, watch[1], watch[2], watch[0], fit=fit)
+        return None, None
+
+    def footprints(self, src, T, hc, wc, watch=None, fit=None):
+        """End of a step, n frames on canvases of one size: the watcher (`carry`) and the footprint launch where the step needs one
+        -> (fp, efp) of the _Deferred, n rows each."""
+        watch, fit = self.carry(src, watch, fit)
+        if not self.needs_footprints():
+            return None, None
+        rows = ops.render_footprints(src, T, self.h, self.w, hc, wc, watch=watch, fit=None if watch is None else fit)
+        return rows if self.skip else None, rows if self.exposure else None
+
+
+class _FusedRender(_Render):
+    """AVERAGE | FEATHER: the fused single-launch render (ops.render_average*, the formula its `fusion`)."""
+    skip = property(lambda self: pipeline.SKIP_OUTSIDE)      # same footprint skipping as the offline render (pipeline.render_frames)
+    # (the NV12 render has no SS_RENDER_EPS_FOLD form: with that opt-in set the fp32 route keeps the two formats equal)
+    nv12 = property(lambda self: not ops.RENDER_EPS_FOLD)
+
+    def _takes_direct(self, st):
+        return DIRECT_RENDER
+
+    def render_into(self, imgs, left, hc, wc, gains, out):
+        return ops.render_average(imgs, left.src, left.T, hc, wc, self.warp, out=out, footprint=left.fp, gains=gains, fusion=self.fusion)
+
+    def frame(self, imgs, left, hc, wc, u8, gains=None):
+        if u8:                           # uint8 frames in, the uint8 video frame out: no fp32 frame planes, no fp32 canvas
+            return ops.render_average_u8(list(imgs), left.src, left.T, hc, wc, self.warp, footprint=left.fp, gains=gains,
+                                         fusion=self.fusion)
+        return self.render_into([f.reshape(1, 3, self.h, self.w) for f in imgs], left, hc, wc, gains, None)
+
+    def frame_nv12(self, imgs, left, hc, wc, out):
+        """The render writes the requested format itself (NV12_FUSED_SINK off: the uint8 frame, and the sink makes NV12 of it)."""
+        if out == 'nv12' and not NV12_FUSED_SINK:
+            return ops.bgr_to_nv12(ops.render_average_nv12(list(imgs), left.src, left.T, hc, wc, self.warp, footprint=left.fp,
+                                                           fusion=self.fusion))
+        return ops.render_average_nv12(list(imgs), left.src, left.T, hc, wc, self.warp, footprint=left.fp, out_format=out,
+                                       fusion=self.fusion)
+
+    def batch(self, views, left, hc, wc, u8=False, gains=None, out=None):
+        render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
+        return render(views, left.src, left.T, hc, wc, self.warp, out=out, footprint=left.fp, gains=gains, fusion=self.fusion)
+
+    def streams(self, imgs, left, sizes, u8):
+        """One clip-style launch when the canvases share a size, else one launch per stream."""
+        if isinstance(left, _Deferred):
+            return list(self.batch([f.contiguous() for f in imgs], left, sizes[0][0], sizes[0][1], u8))
+        # (uint8 frames [H,W,3], fp32 ones [1,3,H,W])
+        return [self.frame([f[s] if u8 else f[s:s + 1] for f in imgs], left[s], hc, wc, u8) for s, (hc, wc) in enumerate(sizes)]
+
+
+class _LinearRender(_Render):
+    """LINEAR.  Inside the step the per-frame chain (warp, blender launches); the push's own render is the fused three launches (four
+    with three views) of ops.render_linear_frames -- for all S streams of a MultiOnlineStitcher at once, whatever their canvas sizes;
+    bit-identical frames."""
+    ragged = True
+
+    def __init__(self, st):
+        _Render.__init__(self, st)
+        self._ws = {}                    # chunk -> ((canvas sizes, views), workspace), re-made when a canvas changes
+
+    def _takes_direct(self, st):
+        return DIRECT_RENDER and DIRECT_LINEAR and st._LINEAR_DIRECT
+
+    def _frames(self, views, src, T, sizes, nv12=False, gains=None, outs=None):
+        """n frames on their own canvases `sizes` (ops.render_linear_frames, <= 32 frames per call) with the workspaces this stitcher
+        holds; they are re-made when a canvas is set or regrown (the sizes are their key).  nv12: the views are NV12 frames
+        [n,H*3/2,W] (any pitch), sampled where they lie."""
+        res = []
+        for c in range(0, len(sizes), 32):
+            key = (tuple(sizes[c:c + 32]), len(views))
+            if self._ws.get(c, (None, None))[0] != key:
+                self._ws[c] = (key, ops.linear_frames_workspace(key[0], key[1], self.dev))
+            if nv12:
+                res += ops.render_linear_frames_nv12([f[c:c + 32] for f in views], src[c:c + 32], T[c:c + 32], key[0],
+                                                     self.warp, ws=self._ws[c][1])
+                continue
+            res += ops.render_linear_frames([f[c:c + 32].contiguous() for f in views], src[c:c + 32], T[c:c + 32], key[0],
+                                            self.warp, ws=self._ws[c][1], outs=None if outs is None else outs[c:c + 32],
+                                            gains=None if gains is None else gains[c:c + 32])
+        return res
+
+    def render_into(self, imgs, left, hc, wc, gains, out):
+        src, T = left.src, left.T
+        if gains is not None:                # with exposure: the fused render at n = 1 (bit-identical to the chain below)
+            return self._frames([f.reshape(1, 3, self.h, self.w) for f in imgs], src[None], T[None], [(hc, wc)], gains=gains,
+                                outs=None if out is None else [out])[0]
+        w = ops.tps_warp_views(imgs, src, T, hc, wc, self.warp)                   # [V,4,Hc,Wc]
+        res = ops.linear_blend(w[0, 0:3], w[1, 0:3], w[0, 3], w[1, 3])
+        if len(imgs) == 3:
+            res = ops.linear_blend(res, w[2, 0:3], ops.mask_union(w[0, 3], w[1, 3]), w[2, 3])
+        return res if out is None else out.copy_(res)
+
+    def frame(self, imgs, left, hc, wc, u8, gains=None):
+        """The fused three / four launches at n = 1; uint8 frames in -> the uint8 video frame out."""
+        shp = (1, self.h, self.w, 3) if u8 else (1, 3, self.h, self.w)
+        return self._frames([f.reshape(shp) for f in imgs], left.src[None], left.T[None], [(hc, wc)], gains=gains)[0]
+
+    def frame_nv12(self, imgs, left, hc, wc, out):
+        """The render writes the uint8 frame (its blend walks a rolling row window) and the sink makes NV12 of it."""
+        bgr = self._frames([f[None] for f in imgs], left.src[None], left.T[None], [(hc, wc)], nv12=True)[0]
+        return ops.bgr_to_nv12(bgr) if out == 'nv12' else bgr
+
+    def batch(self, views, left, hc, wc, u8=False, gains=None, out=None):
+        """The fused clip render (bit-identical per frame to the chain of render_into)."""
+        return ops.render_linear_clip(views, left.src, left.T, hc, wc, self.warp, out=out, gains=gains)
+
+    def streams(self, imgs, left, sizes, u8):
+        """ONE ragged render over the S streams' own canvases (chunks of 32 streams)."""
+        return self._frames(list(imgs), left.src, left.T, sizes)
+
+
+class _MultibandRender(_Render):
+    """MULTIBAND (ops.render_multiband: the existing warp + the pyramid blend): in the steady state always launched by the push or the
+    batch, on the caller's frames, behind a graph that ends with the splines and the watcher -- as the direct LINEAR render is.  One
+    canvas, one push in flight; no NV12 source or sink (push_nv12: ingest, push, the sinks)."""
+    nv12 = False
+
+    def __init__(self, st):
+        _Render.__init__(self, st)
+        self.bands = st.bands
+
+    def _takes_direct(self, st):
+        return True
+
+    def render_into(self, imgs, left, hc, wc, gains, out):      # the window fill, and every push without a graph
+        return ops.render_multiband(list(imgs), left.src, left.T, hc, wc, self.warp, self.bands, out=out, u8=False)
+
+    def frame(self, imgs, left, hc, wc, u8, gains=None):        # uint8 frames in -> the uint8 video frame out of the last collapse pass
+        shp = (self.h, self.w, 3) if u8 else (3, self.h, self.w)
+        return ops.render_multiband([f.reshape(shp) for f in imgs], left.src, left.T, hc, wc, self.warp, self.bands)
+
+    def batch(self, views, left, hc, wc, u8=False, gains=None, out=None):
+        """pipeline.MULTIBAND_FRAMES frames per call: each in the launches of one."""
+        src, T = left.src, left.T
+        k, c = src.shape[0], pipeline.MULTIBAND_FRAMES
+        if out is None:
+            out = torch.empty((k, hc, wc, 3) if u8 else (k, 3, hc, wc), device=self.dev, dtype=views[0].dtype)
+        for s in range(0, k, c):
+            ops.render_multiband([f[s:s + c] for f in views], src[s:s + c], T[s:s + c], hc, wc, self.warp, self.bands, out=out[s:s + c])
+        return out
+
+
 # ------------------------------------------------------------------ steady state (window full, canvas fixed)
 # State tensors of the steady state (fixed addresses: the step is captured into a HIP graph), with a leading S for S streams:
 #   pair_s [2 views][prev, new][126]   spatial motions of the previous and the current pair
@@ -379,7 +563,8 @@ class _Stitcher:
     steady-state push -- poll the watcher (grow='recapture'), recapture after reloaded weights, load the push's inputs, run the step
     eagerly (use_graph=False) or capture it on first use and replay it, copy the watcher rows behind it, hand the frames out (rendered
     now from the caller's frames with the direct render, else copies of the graph's output).  A subclass provides _load, _step_static
-    and the window-fill push; one with S canvases also _regrown / _render_direct / overflow_report."""
+    and the window-fill push; one with S canvases also _regrown / _render_direct / overflow_report.  How the fusion mode renders, in
+    every one of these places, is `self.mode`'s to say (_Render)."""
     _U8_STEADY = True        # push_u8 in the steady state: the resize writes the graph's LR inputs, the render samples the uint8 frames
     _LINEAR_DIRECT = True    # may LINEAR fusion take the direct render (DIRECT_LINEAR)?  Not with two pushes in flight (_TwoInFlight)
     _MULTIBAND = False       # does the class render MULTIBAND fusion?  (one canvas, one push in flight: the two plain stitchers)
@@ -387,8 +572,6 @@ class _Stitcher:
     def __init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only=False, canvases=1,
                  viewport=None, zoom_limit=2.0, exposure=None, bands=None):
         self.exposure = _exposure_params(exposure, meshes_only)      # None: no launch, buffer or graph node of it exists
-        # MULTIBAND (ops.render_multiband: the existing warp + the pyramid blend): always launched by the push or the batch, on
-        # the caller's frames, behind a graph that ends with the splines and the watcher -- as the direct LINEAR render is
         self.bands = None
         if fusion_mode == 'MULTIBAND':
             if self.exposure is not None:
@@ -426,16 +609,16 @@ class _Stitcher:
         self.h, self.w = height, width
         self.margin = margin
         self.warp_mode, self.fusion_mode = warp_mode, fusion_mode
-        # AVERAGE | FEATHER: the fused single-launch render (ops.render_average*, the formula its `fusion`) -- the direct render, the
-        # uint8 steady state, footprint skipping, NV12 written by the render and the batch renders all ask this, not the mode's name
+        # AVERAGE | FEATHER: the fused single-launch render (ops.render_average*, the formula its `fusion`)
         self._fused = ops.fused_render(fusion_mode)
         if fusion_mode == 'FEATHER' and ops.RENDER_EPS_FOLD:
             raise ValueError('SS_RENDER_EPS_FOLD has no FEATHER form')
         self.use_graph = use_graph
         self.meshes_only = bool(meshes_only)
-        direct = self._fused or (fusion_mode == 'LINEAR' and DIRECT_LINEAR and self._LINEAR_DIRECT) or fusion_mode == 'MULTIBAND'
-        self._direct_render = bool((DIRECT_RENDER or fusion_mode == 'MULTIBAND') and use_graph and direct and not self.meshes_only)
-        self._lin_ws = {}                # direct LINEAR render: chunk -> ((canvas sizes, views), workspace), re-made when a canvas changes
+        # how this mode renders -- the direct render, the uint8 steady state, footprint skipping, NV12 written by the render and the
+        # batch renders all ask `mode`, not the mode's name
+        self.mode = (_FusedRender if self._fused else _MultibandRender if fusion_mode == 'MULTIBAND' else _LinearRender)(self)
+        self._deferred = None            # direct render: the _Deferred the step left for the push's render
         # overflow of the fixed canvas(es), and the device-side refit of their boxes; meshes_only: never started
         self.watch = _CanvasWatch(canvases, margin, self.dev, viewport, grow == 'refit', zoom_limit)
         self.static = None               # steady-state buffers (inputs, rings, output) once the window is full
@@ -450,7 +633,6 @@ class _Stitcher:
         # exposure compensation: the stream's gain state (ops.exposure_state) -- it belongs to the stream, not to a canvas or a
         # graph, and survives a regrow / recapture
         self._exp_state = None if self.exposure is None else ops.exposure_state(self.dev)
-        self._exp_fp = None              # direct render: the footprint row the step left for the push's exposure update
 
     # ------------------------------------------------------------------ canvas overflow
     def overflow_report(self):
@@ -553,7 +735,7 @@ class _Stitcher:
     def _direct(self):
         """Does the steady-state push launch its render itself, outside the graph, on the caller's frames (DIRECT_RENDER; LINEAR
         fusion: DIRECT_LINEAR too, plain stitchers only)?  Decided when the stitcher is built."""
-        return self._direct_render
+        return self.mode.direct
 
     def _u8_steady(self):
         return self.static is not None and self._direct() and self._U8_STEADY
@@ -592,64 +774,30 @@ class _Stitcher:
         if self.grow == 'recapture':
             self.watch.post_copy()
         if nv12 is not None:
-            return self._render_direct_nv12(self._deferred_splines(), *nv12)
-        return self._take(self._deferred_splines(), self.static['out'], u8 or frames[:len(frames) // 2], u8 is not None)
+            return [self.mode.frame_nv12(nv12[0], self._deferred, self.hc, self.wc, nv12[1])]
+        return self._take(self._deferred, self.static['out'], u8 or frames[:len(frames) // 2], u8 is not None)
 
-    def _deferred_splines(self):
-        """Direct render: the splines and footprints (src, T, footprint; LINEAR: None) the step left for the push's render."""
-        return getattr(self, '_deferred', None)
-
-    def _take(self, deferred, out, imgs, u8):
+    def _take(self, left, out, imgs, u8):
         """A push's frames: without the direct render copies of the step's output `out`; with it, rendered now from the caller's
-        frames imgs (HR frames, or uint8 frames when u8) and the step's `deferred` splines into new tensors."""
+        frames imgs (HR frames, or uint8 frames when u8) and the _Deferred `left` by the step into new tensors."""
         if not self._direct():
             return [[o.clone()] for o in out] if isinstance(out, list) else [out.clone()]
-        return self._render_direct(deferred, imgs, u8)
+        return self._render_direct(left, imgs, u8)
 
     def _render_solved(self, imgs, src, T, out=None, watch=None, fit=None):
         """src [V,63,2] normalised control points on this canvas, T [V,2,66] their splines -> the stitched frame of the V = 2 | 3 views
-        imgs [1,3,H,W] (written to `out` if given; out=_DEFER: splines and footprint left in self._deferred for the push's render).
-        watch = (guard, watch_i [1,4], watch_f [1,4]): the overflow watcher has not seen `src` yet; fit (grow='refit'): the
-        ops.CanvasFit of this canvas -- the launch that carries the watcher re-fixes the box behind it."""
-        skip = self._fused and pipeline.SKIP_OUTSIDE
-        if watch is not None and not (skip or self.exposure is not None):
-            ops.canvas_watch(src[None], watch[1], watch[2], watch[0], fit=fit)   # no footprint launch to carry it
-            watch = None
-        efp = gains = None
-        if self.exposure is not None:        # the footprint lattice is the estimator's sample set: made whatever the fusion is
-            efp = ops.render_footprints(src[None], T[None], self.h, self.w, self.hc, self.wc, watch=watch,
-                                        fit=None if watch is None else fit)
-            if out is _DEFER:                # the update reads the frames the render reads: the push runs both on the caller's
-                self._exp_fp = efp
-            else:
-                shp = (1, 3, self.h, self.w)
-                gains = self._exposure_gains([f.reshape(shp) for f in imgs], efp)
-        if self._fused:
-            fp = None
-            if efp is not None:
-                fp = efp[0] if skip else None
-            elif pipeline.SKIP_OUTSIDE:      # same footprint skipping as the offline render (pipeline.render_frames)
-                fp = ops.render_footprints(src[None], T[None], self.h, self.w, self.hc, self.wc, watch=watch,
-                                           fit=None if watch is None else fit)[0]
-            if out is _DEFER:
-                self._deferred = (src, T, fp)
-                return None
-            return ops.render_average(imgs, src, T, self.hc, self.wc, self.warp_mode, out=out, footprint=fp, gains=gains,
-                                      fusion=self.fusion_mode)
-        if out is _DEFER:                    # LINEAR, MULTIBAND: the graph ends with the splines and the watcher
-            self._deferred = (src, T, None)
-            return None
-        if self.fusion_mode == 'MULTIBAND':  # the window fill, and every push without a graph
-            return ops.render_multiband(list(imgs), src, T, self.hc, self.wc, self.warp_mode, self.bands, out=out, u8=False)
-        if gains is not None:                # LINEAR with exposure: the fused render at n = 1 (bit-identical to the chain below)
-            shp = (1, 3, self.h, self.w)
-            return self._render_linear([f.reshape(shp) for f in imgs], src[None], T[None], [(self.hc, self.wc)], gains=gains,
-                                       outs=None if out is None else [out])[0]
-        w = ops.tps_warp_views(imgs, src, T, self.hc, self.wc, self.warp_mode)        # [V,4,Hc,Wc]
-        res = ops.linear_blend(w[0, 0:3], w[1, 0:3], w[0, 3], w[1, 3])
-        if len(imgs) == 3:
-            res = ops.linear_blend(res, w[2, 0:3], ops.mask_union(w[0, 3], w[1, 3]), w[2, 3])
-        return res if out is None else out.copy_(res)
+        imgs [1,3,H,W] (written to `out` if given; out=_DEFER: nothing is rendered -> the _Deferred for the push's render, kept in
+        self._deferred).  watch = (guard, watch_i [1,4], watch_f [1,4]): the overflow watcher has not seen `src` yet; fit
+        (grow='refit'): the ops.CanvasFit of this canvas -- the launch that carries the watcher re-fixes the box behind it."""
+        fp, efp = self.mode.footprints(src[None], T[None], self.hc, self.wc, watch, fit)
+        left = _Deferred(src, T, None if fp is None else fp[0], efp)
+        if out is _DEFER:                    # (exposure: the update reads the frames the render reads -- the push runs both on the caller's)
+            self._deferred = left
+            return left
+        gains = None
+        if efp is not None:
+            gains = self._exposure_gains([f.reshape(1, 3, self.h, self.w) for f in imgs], efp)
+        return self.mode.render_into(imgs, left, self.hc, self.wc, gains, out)
 
     def _grown(self, bb):
         """A box (wmin, wmax, hmin, hmax) grown by the margin on every side, on the device."""
@@ -657,46 +805,20 @@ class _Stitcher:
         gw, gh = self.margin * (bb[1] - bb[0]), self.margin * (bb[3] - bb[2])
         return torch.stack((bb[0] - gw, bb[1] + gw, bb[2] - gh, bb[3] + gh)).to(self.dev)
 
-    def _render_direct(self, deferred, imgs, u8):
+    def _render_direct(self, left, imgs, u8):
         """One canvas, two or three views."""
-        src, T, fp = deferred
         gains = None
-        if self.exposure is not None:        # the gains through this frame, from the caller's frames, in front of the render launch
+        if left.efp is not None:             # the gains through this frame, from the caller's frames, in front of the render launch
             shp = (1, self.h, self.w, 3) if u8 else (1, 3, self.h, self.w)
-            gains = self._exposure_gains([f.reshape(shp) for f in imgs], self._exp_fp)
-        if self.fusion_mode == 'MULTIBAND':  # uint8 frames in -> the uint8 video frame out of the last collapse pass
-            shp = (self.h, self.w, 3) if u8 else (3, self.h, self.w)
-            return [ops.render_multiband([f.reshape(shp) for f in imgs], src, T, self.hc, self.wc, self.warp_mode, self.bands)]
-        if self.fusion_mode == 'LINEAR':     # the fused three / four launches at n = 1, uint8 frames in -> the uint8 video frame out
-            shp = (1, self.h, self.w, 3) if u8 else (1, 3, self.h, self.w)
-            return self._render_linear([f.reshape(shp) for f in imgs], src[None], T[None], [(self.hc, self.wc)], gains=gains)
-        if u8:                           # uint8 frames in, the uint8 video frame out: no fp32 frame planes, no fp32 canvas
-            return [ops.render_average_u8(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp, gains=gains,
-                                          fusion=self.fusion_mode)]
-        shp = (1, 3, self.h, self.w)
-        return [ops.render_average([f.reshape(shp) for f in imgs], src, T, self.hc, self.wc, self.warp_mode, footprint=fp,
-                                   gains=gains, fusion=self.fusion_mode)]
-
-    def _render_direct_nv12(self, deferred, imgs, out):
-        """_render_direct from the caller's NV12 frames: AVERAGE writes the requested format itself; LINEAR writes the uint8 frame
-        (its blend walks a rolling row window) and the sink makes NV12 of it."""
-        src, T, fp = deferred
-        if self.fusion_mode == 'LINEAR':
-            bgr = self._render_linear([f[None] for f in imgs], src[None], T[None], [(self.hc, self.wc)], nv12=True)
-            return [ops.bgr_to_nv12(f) for f in bgr] if out == 'nv12' else bgr
-        if out == 'nv12' and not NV12_FUSED_SINK:
-            return [ops.bgr_to_nv12(ops.render_average_nv12(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp,
-                                                            fusion=self.fusion_mode))]
-        return [ops.render_average_nv12(list(imgs), src, T, self.hc, self.wc, self.warp_mode, footprint=fp, out_format=out,
-                                        fusion=self.fusion_mode)]
+            gains = self._exposure_gains([f.reshape(shp) for f in imgs], left.efp)
+        return [self.mode.frame(imgs, left, self.hc, self.wc, u8, gains)]
 
     def _push_nv12(self, imgs, out):
-        """push_nv12 of V views (checked): the steady state with the direct render samples the caller's NV12 frames; every other
-        configuration, and the window fill, goes ingest_nv12 -> _push -> canvas_to_u8 (-> bgr_to_nv12)."""
+        """push_nv12 of V views (checked): the steady state with the direct render samples the caller's NV12 frames where the mode
+        has an NV12 render; every other configuration, and the window fill, goes ingest_nv12 -> _push -> canvas_to_u8
+        (-> bgr_to_nv12)."""
         with ops.deterministic(self.deterministic):
-            # (the NV12 render has no SS_RENDER_EPS_FOLD form: with that opt-in set the fp32 route keeps the two formats equal)
-            # (MULTIBAND has no NV12 source or sink: ingest, push, the sinks)
-            if self._u8_steady() and not (ops.RENDER_EPS_FOLD and self._fused) and self.fusion_mode != 'MULTIBAND':
+            if self._u8_steady() and self.mode.nv12:
                 return self._push_static(nv12=(imgs, out))
             v = len(imgs)
             hr = torch.empty((v, 3, self.h, self.w), device=self.dev)
@@ -707,27 +829,9 @@ class _Stitcher:
             frames = [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
             return [ops.bgr_to_nv12(f) for f in frames] if out == 'nv12' else frames
 
-    def _render_linear(self, views, src, T, sizes, nv12=False, gains=None, outs=None):
-        """Direct LINEAR render of n frames on their own canvases `sizes` (ops.render_linear_frames, <= 32 frames per call) with
-        the workspaces this stitcher holds; they are re-made when a canvas is set or regrown (the sizes are their key).  nv12: the
-        views are NV12 frames [n,H*3/2,W] (any pitch), sampled where they lie."""
-        res = []
-        for c in range(0, len(sizes), 32):
-            key = (tuple(sizes[c:c + 32]), len(views))
-            if self._lin_ws.get(c, (None, None))[0] != key:
-                self._lin_ws[c] = (key, ops.linear_frames_workspace(key[0], key[1], self.dev))
-            if nv12:
-                res += ops.render_linear_frames_nv12([f[c:c + 32] for f in views], src[c:c + 32], T[c:c + 32], key[0],
-                                                     self.warp_mode, ws=self._lin_ws[c][1])
-                continue
-            res += ops.render_linear_frames([f[c:c + 32].contiguous() for f in views], src[c:c + 32], T[c:c + 32], key[0],
-                                            self.warp_mode, ws=self._lin_ws[c][1], outs=None if outs is None else outs[c:c + 32],
-                                            gains=None if gains is None else gains[c:c + 32])
-        return res
-
     # ------------------------------------------------------------------ k frames of every view per call (one canvas)
     # A subclass provides _push (one plain push), push_u8, _batch_buffers (the per-k work buffers, 'lr' [V,k,3,360,480] among
-    # them) and _step_batch (the capturable batched step, leaving (src, T, footprints) in B['deferred']).
+    # them) and _step_batch (the capturable batched step, ending with _leave_batch: the _Deferred in B['deferred']).
     def _push_many(self, frames):
         """push_many of V views: frames = the V HR batches [k,3,H,W] then the V LR batches [k,3,360,480]."""
         k = self._check_many(frames)
@@ -808,26 +912,19 @@ class _Stitcher:
             self.watch.post_copy()
         return self._render_batch(B['deferred'], u8 if u8 is not None else frames[:views], u8 is not None)
 
-    def _render_batch(self, deferred, imgs, u8):
-        """The batch's frames from the caller's frames imgs (V x [k,3,H,W] fp32, or [k,H,W,3] uint8 when u8) in one render: AVERAGE
-        with the footprints, LINEAR through the fused clip render (bit-identical per frame to the push's tps_warp_views +
-        linear_blend)."""
-        src, T, fp = deferred[:3]
+    def _leave_batch(self, B, src, T):
+        """End of a batched step: the watcher over its k frames src [k,V,63,2], the footprints where the step needs them, and the
+        _Deferred in B['deferred']."""
+        guard, wi, wf = self.watch.args()
+        ops.canvas_watch_frames(src, wi, wf, guard, fit=self.watch.fit_args())
+        B['deferred'] = _Deferred(src, T, *self.mode.footprints(src, T, self.hc, self.wc))
+
+    def _render_batch(self, left, imgs, u8):
+        """The batch's frames from the caller's frames imgs (V x [k,3,H,W] fp32, or [k,H,W,3] uint8 when u8) in one render."""
         views = [f.contiguous() for f in imgs]
         # exposure: the k frames' gains in one update (stream order, bit-identical to k single-frame updates)
-        gains = None if self.exposure is None else self._exposure_gains(views, deferred[3])
-        if self.fusion_mode == 'MULTIBAND':  # pipeline.MULTIBAND_FRAMES frames per call: each in the launches of one
-            k, c = src.shape[0], pipeline.MULTIBAND_FRAMES
-            out = torch.empty((k, self.hc, self.wc, 3) if u8 else (k, 3, self.hc, self.wc), device=self.dev, dtype=views[0].dtype)
-            for s in range(0, k, c):
-                ops.render_multiband([f[s:s + c] for f in views], src[s:s + c], T[s:s + c], self.hc, self.wc, self.warp_mode, self.bands,
-                                     out=out[s:s + c])
-        elif self._fused:
-            render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
-            out = render(views, src, T, self.hc, self.wc, self.warp_mode, footprint=fp, gains=gains, fusion=self.fusion_mode)
-        else:
-            out = ops.render_linear_clip(views, src, T, self.hc, self.wc, self.warp_mode, gains=gains)
-        return list(out.unbind(0))
+        gains = None if left.efp is None else self._exposure_gains(views, left.efp)
+        return list(self.mode.batch(views, left, self.hc, self.wc, u8, gains).unbind(0))
 
 
 class OnlineStitcher(_Stitcher):
@@ -1126,14 +1223,7 @@ class OnlineStitcher(_Stitcher):
         outs, _ = self.smooth.run_windows(wk[0], wk[1], wk[2], wk[3], k, WINDOW, 1, 1)
         m1, m2 = outs['smooth_mesh1'], outs['smooth_mesh2']                      # [k,7,7,9,2]: frame j's mesh is window j's last
         src, T = ops.stream_splines([m1[0, -1], m2[0, -1]], WINDOW * e, self.bbox, self.nrigid, self.h, self.w, frames=k)
-        guard, wi, wf = self.watch.args()
-        ops.canvas_watch_frames(src, wi, wf, guard, fit=self.watch.fit_args())
-        fp = efp = None
-        skip = self._fused and pipeline.SKIP_OUTSIDE
-        if skip or self.exposure is not None:        # (exposure: the lattice is the estimator's sample set whatever the fusion is)
-            efp = ops.render_footprints(src, T, self.h, self.w, self.hc, self.wc)
-            fp = efp if skip else None
-        B['deferred'] = (src, T, fp) if self.exposure is None else (src, T, fp, efp)
+        self._leave_batch(B, src, T)
 
 
 BATCH_MAX = 32                         # push_many: frames of every view per call
@@ -1194,7 +1284,7 @@ class _TwoInFlight:
 
         def half_b(p):
             self._run_b(p)
-            P['deferred'][p] = self._deferred_splines()    # (direct render: the second half left this parity's splines and footprints)
+            P['deferred'][p] = self._deferred              # (direct render: the second half left this parity's splines and footprints)
         steps = [lambda p=p, fn=fn: fn(p) for p in (0, 1) for fn in (self._run_a, half_b)]
         graphs, self.graph_nodes = _capture(self.dev, self._state(), lambda: (self._run_a(0), self._run_b(0)), steps,
                                             per_push=2)    # nodes of one push (both halves)
@@ -1480,7 +1570,7 @@ class MultiOnlineStitcher(_Stitcher):
               'pair_t': torch.zeros((2, 2, S, e), device=d),
               'ring': torch.stack([o['ring'] for o in one], 1).contiguous(),               # [4,S,7,126]
               'ts_out': torch.empty((2, 4 * S, e), device=d),
-              'out': None, 'out_all': None}
+              'out': None, 'out_all': None, 'one_size': False}
         self.static = st
         if not self.meshes_only:
             st['bboxes'] = torch.stack([s.bbox for s in self.single], 0).contiguous()        # [S,4] the streams' fixed canvases
@@ -1503,16 +1593,16 @@ class MultiOnlineStitcher(_Stitcher):
 
     def _alloc_outputs(self):
         st, S, d = self.static, self.S, self.dev
-        st['out_all'] = None
-        linear_direct = self._direct() and self.fusion_mode == 'LINEAR'      # the push renders all streams into fresh tensors
-        if len({(s.hc, s.wc) for s in self.single}) == 1:       # equal canvas sizes: one render launch for all streams
-            # (out_all is also the mark of that case: where nothing is rendered into it, its shape alone, without memory)
-            st['out_all'] = torch.empty((S, 3, self.single[0].hc, self.single[0].wc), device='meta' if linear_direct else d)
-            st['out'] = None if linear_direct else [st['out_all'][s] for s in range(S)]
-        elif linear_direct:
-            st['out'] = None
+        sizes = self.canvas_sizes
+        st['one_size'] = len(set(sizes)) == 1                   # equal canvas sizes: one render launch for all streams
+        st['out_all'] = st['out'] = None
+        if self._direct() and self.mode.ragged:                 # the push renders all streams into fresh tensors
+            return
+        if st['one_size']:
+            st['out_all'] = torch.empty((S, 3) + sizes[0], device=d)
+            st['out'] = [st['out_all'][s] for s in range(S)]
         else:
-            st['out'] = [torch.empty((3, s.hc, s.wc), device=d) for s in self.single]
+            st['out'] = [torch.empty((3, hc, wc), device=d) for hc, wc in sizes]
 
     # ------------------------------------------------------------------ canvas overflow (per stream)
     def overflow_report(self):
@@ -1564,7 +1654,8 @@ class MultiOnlineStitcher(_Stitcher):
 
     def _stage_b(self, f64, feat, off1, hr1, hr2, out_all, out, defer=False):
         """Second half: everything that reads or advances the streams' state, and the render into out_all / out (defer: splines
-        and footprints only -- self._deferred / the single stitchers' _deferred -- the push launches the render itself)."""
+        and footprints only -- self._deferred: one _Deferred over the S streams, or one per stream -- the push launches the render
+        itself)."""
         st, S, e = self.static, self.S, 126
         ps, pt = st['pair_s'], st['pair_t']
         tm_out = (pt[0, 1], pt[1, 1])
@@ -1595,59 +1686,29 @@ class MultiOnlineStitcher(_Stitcher):
         # launch (a solve is latency-bound, ~48 us whether it holds 2 systems or 16), the watcher on the footprint launch(es), then
         # the render stream by stream
         src, T = ops.stream_splines([m1[0, -1], m2[0, -1]], WINDOW * e, st['bboxes'], self.single[0].nrigid, self.h, self.w)
-        watch = None
-        if self._fused and pipeline.SKIP_OUTSIDE:
-            watch = self.watch.args()
-        else:
-            ops.canvas_watch(src, self.watch.wi, self.watch.wf, self.watch.guard, fit=self.watch.fit_args())
-        if defer and self.fusion_mode == 'LINEAR':        # equal or different canvas sizes: one ragged render, launched by the push
-            self._deferred = (src, T, None)
-            return
-        if out_all is not None:
-            # all streams render onto canvases of ONE size (e.g. the caller fixed them): the S current frames are a clip
-            hc, wc = self.single[0].hc, self.single[0].wc
-            if self._fused:
-                fp = (ops.render_footprints(src, T, self.h, self.w, hc, wc, watch=watch, fit=self.watch.fit_args())
-                      if pipeline.SKIP_OUTSIDE else None)
-                if defer:
-                    self._deferred = (src, T, fp)
-                    return
-                ops.render_average_clip([hr1, hr2], src, T, hc, wc, self.warp_mode, out=out_all, footprint=fp, fusion=self.fusion_mode)
+        mode, (hc, wc) = self.mode, self.canvas_sizes[0]
+        watch, fit = mode.carry(src, self.watch.args(), self.watch.fit_args())
+        if st['one_size'] or (defer and mode.ragged):
+            # all streams render onto canvases of ONE size (e.g. the caller fixed them): the S current frames are a clip; or, whatever
+            # the sizes, in one ragged render launched by the push (it has no footprint launch: hc, wc are not looked at)
+            left = _Deferred(src, T, mode.footprints(src, T, hc, wc, watch, fit)[0], None)
+            if defer:
+                self._deferred = left
             else:
-                ops.render_linear_clip([hr1, hr2], src, T, hc, wc, self.warp_mode, out=out_all)
+                mode.batch([hr1, hr2], left, hc, wc, out=out_all)
             return
-        for s, one in enumerate(self.single):
-            one._render_solved(None if defer else [hr1[s:s + 1], hr2[s:s + 1]], src[s], T[s], out=_DEFER if defer else out[s],
-                               watch=None if watch is None else self.watch.args(s),
-                               fit=None if watch is None else self.watch.fit_args(s))
+        # canvases of several sizes: stream by stream, on the streams' own stitchers (defer: their records, kept here)
+        left = [one._render_solved(None if defer else [hr1[s:s + 1], hr2[s:s + 1]], src[s], T[s], out=_DEFER if defer else out[s],
+                                   watch=None if watch is None else self.watch.args(s),
+                                   fit=None if watch is None else self.watch.fit_args(s)) for s, one in enumerate(self.single)]
+        if defer:
+            self._deferred = left
 
-    def _deferred_splines(self):
-        if self.static['out_all'] is not None or self.fusion_mode == 'LINEAR':
-            return getattr(self, '_deferred', None)
-        return [getattr(one, '_deferred', None) for one in self.single]
-
-    def _render_direct(self, deferred, imgs, u8):
-        """S canvases, two views.  AVERAGE: one clip-style launch when the canvases share a size, else one launch per stream."""
-        S = self.S
+    def _render_direct(self, left, imgs, u8):
+        """S canvases, two views."""
         if not u8:
-            imgs = [f.reshape(S, 3, self.h, self.w) for f in imgs]
-        if self.fusion_mode == 'LINEAR':     # ONE ragged render over the S streams' own canvases (chunks of 32 streams)
-            src, T, _ = deferred
-            return [[f] for f in self._render_linear(list(imgs), src, T, self.canvas_sizes)]
-        if self.static['out_all'] is not None:
-            src, T, fp = deferred
-            one = self.single[0]
-            render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
-            frames = render([f.contiguous() for f in imgs], src, T, one.hc, one.wc, self.warp_mode, footprint=fp,
-                            fusion=self.fusion_mode)
-            return [[frames[s]] for s in range(S)]
-        render = ops.render_average_u8 if u8 else ops.render_average          # (uint8 frames [H,W,3], fp32 ones [1,3,H,W])
-        res = []
-        for s, one in enumerate(self.single):
-            src, T, fp = deferred[s]
-            res.append([render([f[s] if u8 else f[s:s + 1] for f in imgs], src, T, one.hc, one.wc, self.warp_mode, footprint=fp,
-                               fusion=self.fusion_mode)])
-        return res
+            imgs = [f.reshape(self.S, 3, self.h, self.w) for f in imgs]
+        return [[f] for f in self.mode.streams(list(imgs), left, self.canvas_sizes, u8)]
 
     @torch.no_grad()
     def push_u8(self, frames1, frames2):
@@ -1721,8 +1782,8 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
         P = {'lr': two(2, S, 3, pipeline.LR_H, pipeline.LR_W),
              'hr': [[None, None], [None, None]] if self._direct() else two(2, S, 3, self.h, self.w),     # (direct render: no copies)
              'f64': two(2 * S, fh, fw, 128), 'feat': two(2 * S, fh, fw, 128), 'off1': two(S, 8)}
-        if self.static['out_all'] is not None:
-            P['out_all'] = two(*self.static['out_all'].shape)
+        if self.static['one_size']:
+            P['out_all'] = two(S, 3, *self.canvas_sizes[0])
             P['out'] = [[oa[s] for s in range(S)] for oa in P['out_all']]
         else:
             P['out_all'] = [None, None]
@@ -1990,12 +2051,7 @@ class ThreeViewOnlineStitcher(_Stitcher):
         meshes, src, T = ops.three_view_splines(m1[0, -1], m2[0, -1], m1[c1, -1], m2[c1, -1], self.first_canvas, self.bbox,
                                                 self.nrigid, self.h, self.w, frames=k, frame_stride=WINDOW * e)
         self.last_composed = meshes
-        guard, wi, wf = self.watch.args()
-        ops.canvas_watch_frames(src, wi, wf, guard, fit=self.watch.fit_args())
-        fp = None
-        if self._fused and pipeline.SKIP_OUTSIDE:
-            fp = ops.render_footprints(src, T, self.h, self.w, self.hc, self.wc)
-        B['deferred'] = (src, T, fp)
+        self._leave_batch(B, src, T)
 
 
 class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):

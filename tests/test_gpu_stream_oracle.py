@@ -346,9 +346,9 @@ def test_multi_stream_vs_oracle(dev, hip_nets, warp, fusion):
         pipe = PipelinedMultiOnlineStitcher(hip_nets, h, w, streams=S, canvases=canvases, warp_mode=warp, fusion_mode=fusion)
         gotp = _run_multi(pipe, n, args, flush=True)
         if name == 'oracle boxes':
-            assert len(set(plain.canvas_sizes)) > 1 and plain.static['out_all'] is None, plain.canvas_sizes
+            assert len(set(plain.canvas_sizes)) > 1 and not plain.static['one_size'], plain.canvas_sizes
         if name == 'one size':
-            assert set(plain.canvas_sizes) == {(sh, sw)} and plain.static['out_all'] is not None, plain.canvas_sizes
+            assert set(plain.canvas_sizes) == {(sh, sw)} and plain.static['one_size'], plain.canvas_sizes
         assert pipe.canvas_sizes == plain.canvas_sizes
         for s in range(S):
             canvas = plain.single[s].bbox.cpu().tolist()
