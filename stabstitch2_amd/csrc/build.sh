@@ -2,6 +2,7 @@
 # Build libstabstitch_hip.so for gfx950 (MI355X) in-tree.
 #   stabstitch2_amd/csrc/build.sh           -> stabstitch2_amd/libstabstitch_hip.so         (the product)
 #                                              stabstitch2_amd/libstabstitch_blend.so       (MULTIBAND fusion, blend.hip)
+#                                              stabstitch2_amd/libstabstitch_seam.so        (MULTIBAND's DP seam, seam.hip)
 #   stabstitch2_amd/csrc/build.sh tuning    -> tools/libstabstitch_hip_tuning.so            (-DSS_TUNING: adds the
 #       ss_debug_set / ss_debug_ptr knobs, the per-workgroup s_memtime stamps of tools/diag_*.py and the comparison kernels
 #       that tests and tools/ab_*.py measure the product against; concluded experiments are not kept in it: LAB_NOTES.md,
@@ -27,4 +28,8 @@ if [ "$1" != "tuning" ]; then
     BLEND="$HERE/../libstabstitch_blend.so"
     "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden "$HERE/blend.hip" -o "$BLEND"
     echo "built $BLEND"
+    # the dynamic-programming seam of MULTIBAND fusion: a third library (include/stabstitch_seam.h), for the same reason
+    SEAM="$HERE/../libstabstitch_seam.so"
+    "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden "$HERE/seam.hip" -o "$SEAM"
+    echo "built $SEAM"
 fi

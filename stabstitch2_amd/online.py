@@ -394,6 +394,9 @@ class _Render:
         self.exposure = st.exposure is not None
         self.direct = bool(self._takes_direct(st) and st.use_graph and not st.meshes_only)
 
+    def canvas_changed(self):
+        """The stitcher's canvas was set or regrown: whatever the kind remembers about the old one goes."""
+
     def needs_footprints(self):
         """Does the captured step end with a footprint launch?  (exposure: the footprint lattice is the estimator's sample set, made
         whatever the fusion is)"""
@@ -526,25 +529,44 @@ class _MultibandRender(_Render):
     def __init__(self, st):
         _Render.__init__(self, st)
         self.bands = st.bands
+        self.seam = dict(st.seam)            # {} (the geometric seam: no launch of it exists) or ops.render_multiband's seam='dp' keywords
+        self._seam_state = None              # ((hc, wc, views), ops.seam_state): the stream's previous seams on this canvas
 
     def _takes_direct(self, st):
         return True
 
+    def canvas_changed(self):
+        self._seam_state = None
+
+    def _seam(self, views, hc, wc):
+        """The seam keywords of one render on the hc x wc canvas: with the DP seam, the stream's state with them -- a fresh one after
+        the canvas was set or regrown (`canvas_changed`) or changed its size."""
+        if not self.seam:
+            return self.seam
+        key = (hc, wc, views)
+        if self._seam_state is None or self._seam_state[0] != key:
+            self._seam_state = (key, ops.seam_state(views, hc, wc, self.seam['seam_cell'], self.dev))
+        return dict(self.seam, seam_state=self._seam_state[1])
+
     def render_into(self, imgs, left, hc, wc, gains, out):      # the window fill, and every push without a graph
-        return ops.render_multiband(list(imgs), left.src, left.T, hc, wc, self.warp, self.bands, out=out, u8=False)
+        return ops.render_multiband(list(imgs), left.src, left.T, hc, wc, self.warp, self.bands, out=out, u8=False,
+                                    **self._seam(len(imgs), hc, wc))
 
     def frame(self, imgs, left, hc, wc, u8, gains=None):        # uint8 frames in -> the uint8 video frame out of the last collapse pass
         shp = (self.h, self.w, 3) if u8 else (3, self.h, self.w)
-        return ops.render_multiband([f.reshape(shp) for f in imgs], left.src, left.T, hc, wc, self.warp, self.bands)
+        return ops.render_multiband([f.reshape(shp) for f in imgs], left.src, left.T, hc, wc, self.warp, self.bands,
+                                    **self._seam(len(imgs), hc, wc))
 
     def batch(self, views, left, hc, wc, u8=False, gains=None, out=None):
-        """pipeline.MULTIBAND_FRAMES frames per call: each in the launches of one."""
+        """pipeline.MULTIBAND_FRAMES frames per call: each in the launches of one (the DP seam takes a call's frames in order)."""
         src, T = left.src, left.T
         k, c = src.shape[0], pipeline.MULTIBAND_FRAMES
         if out is None:
             out = torch.empty((k, hc, wc, 3) if u8 else (k, 3, hc, wc), device=self.dev, dtype=views[0].dtype)
+        seam = self._seam(len(views), hc, wc)
         for s in range(0, k, c):
-            ops.render_multiband([f[s:s + c] for f in views], src[s:s + c], T[s:s + c], hc, wc, self.warp, self.bands, out=out[s:s + c])
+            ops.render_multiband([f[s:s + c] for f in views], src[s:s + c], T[s:s + c], hc, wc, self.warp, self.bands, out=out[s:s + c],
+                                 **seam)
         return out
 
 
@@ -570,9 +592,14 @@ class _Stitcher:
     _MULTIBAND = False       # does the class render MULTIBAND fusion?  (one canvas, one push in flight: the two plain stitchers)
 
     def __init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only=False, canvases=1,
-                 viewport=None, zoom_limit=2.0, exposure=None, bands=None):
+                 viewport=None, zoom_limit=2.0, exposure=None, bands=None, seam=None):
         self.exposure = _exposure_params(exposure, meshes_only)      # None: no launch, buffer or graph node of it exists
         self.bands = None
+        # MULTIBAND's seam (seam = the dict of the constructor's seam= keywords): {} = the geometric one
+        self.seam = pipeline.seam_options(fusion_mode, **(seam or {}))
+        if self.seam and (meshes_only or not self._MULTIBAND):
+            raise ValueError("%s has no seam=: OnlineStitcher and ThreeViewOnlineStitcher render fusion_mode='MULTIBAND'"
+                             % type(self).__name__)
         if fusion_mode == 'MULTIBAND':
             if self.exposure is not None:
                 raise ValueError("exposure= has no fusion_mode='MULTIBAND' form: the warp it uses takes no gains")
@@ -676,6 +703,7 @@ class _Stitcher:
         box is letterboxed to its aspect (on the device, in place: it is the tensor every later launch reads -- and grow='refit'
         rewrites)."""
         self._canvas_set = True
+        self.mode.canvas_changed()
         if self.viewport is not None:
             self.bbox = self.bbox.to(torch.float32).contiguous()
             self.watch.start(self.watch.fit_boxes(self.bbox))
@@ -688,6 +716,7 @@ class _Stitcher:
         """grow='recapture': the watcher re-fixed the canvas -- new box, new size, a new output buffer (the graph is captured again)."""
         self.bbox = self.watch.boxes[0].to(self.dev)
         self.hc, self.wc = _canvas_size(self.watch.boxes[0])
+        self.mode.canvas_changed()
         if self.static['out'] is not None:
             self.static['out'] = torch.empty((3, self.hc, self.wc), device=self.dev)
 
@@ -932,8 +961,13 @@ class OnlineStitcher(_Stitcher):
 
     def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
                  use_graph=True, grow='never', meshes_only=False, deterministic=False, viewport=None, zoom_limit=2.0, exposure=None,
-                 bands=None):
+                 bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None):
         """canvas: optional (wmin, wmax, hmin, hmax) in HR pixels (e.g. the offline bbox).
+        seam: None / 'geometric' (MULTIBAND's seam where the warped weight planes cross) or 'dp' -- the content-aware seam (DESIGN.md 7f;
+        only with MULTIBAND): ops.multiband_seam between the warp and the blend of every frame handed out, on a grid of seam_cell x
+        seam_cell cells, with seam_mu holding the seam to the previous frame's and seam_prior to the geometric one (defaults:
+        ops.seam_params).  The previous seams belong to the stream AND its canvas: they are forgotten when the canvas is set and at every
+        grow='recapture' regrow (grow='refit' moves the box under a fixed grid on the device: the state stays).
         fusion_mode: 'AVERAGE', 'FEATHER', 'LINEAR' or 'MULTIBAND' -- the Laplacian-pyramid blend of `bands` levels
         (0..6, default 5; only with MULTIBAND): the existing warp of B, G, R and a weight plane, then the pyramid launches, always
         launched by the push on the caller's frames (the graph ends with the splines); not with exposure=.
@@ -965,7 +999,8 @@ class OnlineStitcher(_Stitcher):
         push_many takes one refit per call, behind the batch's watcher: a drift inside one call can crop up to k counted frames."""
         _exposure_params(exposure, meshes_only)
         _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only,
-                           viewport=viewport, zoom_limit=zoom_limit, exposure=exposure, bands=bands)
+                           viewport=viewport, zoom_limit=zoom_limit, exposure=exposure, bands=bands,
+                           seam=dict(seam=seam, seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior))
         self.deterministic = bool(deterministic)
         self.last_meshes = None
         self.bbox = None if canvas is None else torch.tensor(canvas, dtype=torch.float32, device=self.dev)
@@ -1840,17 +1875,21 @@ class ThreeViewOnlineStitcher(_Stitcher):
     _MULTIBAND = True
 
     def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 use_graph=True, grow='never', deterministic=False, viewport=None, zoom_limit=2.0, exposure=None, bands=None):
+                 use_graph=True, grow='never', deterministic=False, viewport=None, zoom_limit=2.0, exposure=None, bands=None, seam=None,
+                 seam_cell=None, seam_mu=None, seam_prior=None):
         """deterministic: every push under the conv engine's geometry-only kernel policy (ops.deterministic; as OnlineStitcher's):
         push_many's frames then equal single pushes' bit for bit.
-        fusion_mode='MULTIBAND' and bands=: as OnlineStitcher's, over the three views at once."""
+        fusion_mode='MULTIBAND', bands= and seam= (seam_cell=, seam_mu=, seam_prior=): as OnlineStitcher's, over the three views at once
+        (two seams, between the views that neighbour each other on the canvas)."""
+        pipeline.seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)
         _no_exposure(type(self).__name__, exposure)
         # the two pair chains as a batch of two streams over the CHAIN of three views: every launch serves both pairs, view 2's
         # trunk features are computed once
         self.chains = MultiOnlineStitcher(nets, height, width, streams=2, margin=margin, warp_mode=warp_mode, fusion_mode=fusion_mode,
                                           use_graph=False, meshes_only=True, deterministic=deterministic, chain=True)
         _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, viewport=viewport,
-                           zoom_limit=zoom_limit, bands=bands)
+                           zoom_limit=zoom_limit, bands=bands,
+                           seam=dict(seam=seam, seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior))
         self.deterministic = bool(deterministic)
         box = lambda b: None if b is None else torch.tensor(b, dtype=torch.float32, device=self.dev)
         self.bbox, self.first_canvas = box(canvas), box(first_canvas)

@@ -1352,22 +1352,126 @@ def multiband_stack(imgs):
     return U
 
 
-def render_multiband(imgs, source, T, hc, wc, mode='NORMAL', bands=MULTIBAND_BANDS, out=None, ws=None, u8=None):
+# ------------------------------------------------------------------ MULTIBAND's content-aware seam (libstabstitch_seam.so)
+SEAM_PRIOR = 8.0
+SEAMS = ('geometric', 'dp')
+
+
+def seam_cell(hc, wc, cell=None):
+    """The cell size of the seam's grid on a hc x wc canvas: `cell` checked (one of 1, 2, 4, 8, 16 whose dynamic program fits the LDS
+    of one workgroup), or for None the smallest of 4, 8, 16 that fits.  ValueError names a larger cell where one helps."""
+    from . import _seam as S
+    if cell is None:
+        for c in (4, 8, 16):
+            if S.lds_bytes(hc, wc, c) <= S.LDS_BYTES:
+                return c
+        raise ValueError('the DP seam has no cell size for a %d x %d canvas: its rows and back pointers exceed the LDS at cell 16' % (hc, wc))
+    if isinstance(cell, bool) or not isinstance(cell, int) or cell not in S.CELLS:
+        raise ValueError('seam cell must be one of %s, got %r' % (S.CELLS, cell))
+    if S.lds_bytes(hc, wc, cell) > S.LDS_BYTES:
+        fit = [c for c in S.CELLS if c > cell and S.lds_bytes(hc, wc, c) <= S.LDS_BYTES]
+        raise ValueError('the DP seam at cell=%d on a %d x %d canvas needs %d bytes of LDS, a workgroup has %d: %s'
+                         % (cell, hc, wc, S.lds_bytes(hc, wc, cell), S.LDS_BYTES,
+                            'use a larger cell, cell=%d fits' % fit[0] if fit else 'no larger cell fits either'))
+    return cell
+
+
+def seam_params(hc, wc, cell=None, mu=None, prior=None):
+    """-> (cell, mu, prior) with the defaults filled in (cell: seam_cell; mu = 48 * cell; prior = SEAM_PRIOR) and checked."""
+    from . import _seam as S
+    cell = seam_cell(hc, wc, cell)
+    mu = 48 * cell if mu is None else mu
+    if isinstance(mu, bool) or not isinstance(mu, int) or not 0 <= mu <= S.MU_MAX:
+        raise ValueError('seam mu must be an integer 0..%d, got %r' % (S.MU_MAX, mu))
+    prior = SEAM_PRIOR if prior is None else float(prior)
+    if not 0.0 <= prior <= S.PRIOR_MAX:
+        raise ValueError('seam prior must be in 0..%g, got %r' % (S.PRIOR_MAX, prior))
+    return cell, mu, prior
+
+
+def seam_state(views, hc, wc, cell=None, device='cuda'):
+    """The seam state of one stream on one canvas (int32, all zero = fresh): what multiband_seam's temporal term remembers -- the grid,
+    the view order and the previous seams.  `state.zero_()` forgets it."""
+    from . import _seam as S
+    if views not in (2, 3):
+        raise ValueError('the DP seam takes 2 or 3 views, got %r' % (views,))
+    hq = S.grid(hc, wc, seam_cell(hc, wc, cell))[0]
+    return torch.zeros(S.STATE_HEADER + (views - 1) * hq, device=device, dtype=torch.int32)
+
+
+def seam_workspace(frames, views, hc, wc, cell, device):
+    """The int32 workspace of multiband_seam for `frames` frames in one call (ssm_seam_workspace_bytes; _seam.layout names its parts)."""
+    from . import _seam as S
+    need = int(S.lib().ssm_seam_workspace_bytes(frames, views, hc, wc, cell))
+    if need < 0:
+        raise ValueError('multiband_seam: 1..65535 frames of 2|3 views, a cell of %s whose grid fits the LDS; got %d frames of %d views '
+                         'on %d x %d at cell %r' % (S.CELLS, frames, views, hc, wc, cell))
+    return torch.empty(need // 4, device=device, dtype=torch.int32)
+
+
+def multiband_seam(P, cell=None, mu=None, prior=None, state=None, ws=None):
+    """The content-aware seam of MULTIBAND fusion, in place: P [V,5,hc,wc] or [n,V,5,hc,wc] as tps_warp(.., with_mask=True) writes it;
+    plane 3 of every view becomes the small integer seam weights that multiband_blend then reads -- a top-to-bottom minimal-cost seam per
+    pair of neighbouring views on a grid of cell x cell cells (tests/seam_ref.py is the definition).  mu: the cost of moving the seam
+    one cell sideways against the previous frame's (needs `state`, ops.seam_state; the frames of a clip are taken in order); prior: the
+    pull towards the geometric seam.  Three launches whatever n is.  -> P."""
+    from . import _seam as S
+    clip = P.dim() == 5
+    if P.dim() not in (4, 5) or P.shape[-3] != 5:
+        raise ValueError('P must be [V,5,hc,wc] or [n,V,5,hc,wc], got %s' % (tuple(P.shape),))
+    n = P.shape[0] if clip else 1
+    v, hc, wc = P.shape[-4], P.shape[-2], P.shape[-1]
+    if v not in (2, 3):
+        raise ValueError('the DP seam takes 2 or 3 views, got %d' % v)
+    cell, mu, prior = seam_params(hc, wc, cell, mu, prior)
+    if ws is None:
+        ws = seam_workspace(n, v, hc, wc, cell, P.device)
+    if state is not None and (state.dtype != torch.int32 or state.numel() < S.STATE_HEADER + (v - 1) * S.grid(hc, wc, cell)[0]):
+        raise ValueError('seam state: int32 of at least %d values for %d views on this grid (ops.seam_state), got %s of %d'
+                         % (S.STATE_HEADER + (v - 1) * S.grid(hc, wc, cell)[0], v, state.dtype, state.numel()))
+    S.call('ssm_multiband_seam', H.dptr(P), n, v, hc, wc, cell, mu, prior, H.dptr(state, True, dtype=torch.int32),
+           0 if state is None else state.numel(), H.dptr(ws, dtype=torch.int32), 4 * ws.numel(), H.stream())
+    return P
+
+
+def check_seam(seam, fusion_mode='MULTIBAND'):
+    """ValueError for a seam that does not exist, or for seam= with a fusion mode that has none (None: not given)."""
+    if seam is None:
+        return None
+    if fusion_mode != 'MULTIBAND':
+        raise ValueError("seam= belongs to fusion_mode='MULTIBAND', got %r" % (fusion_mode,))
+    if seam not in SEAMS:
+        raise ValueError('seam must be one of %s, got %r' % (SEAMS, seam))
+    return seam
+
+
+def render_multiband(imgs, source, T, hc, wc, mode='NORMAL', bands=MULTIBAND_BANDS, out=None, ws=None, u8=None, seam='geometric',
+                     seam_state=None, seam_cell=None, seam_mu=None, seam_prior=None):
     """MULTIBAND fusion of one frame or of n: imgs as multiband_stack takes them; source [V,63,2] / [n,V,63,2]; T [V,2,66] / [n,V,2,66]
     -> [3,hc,wc] / [n,3,hc,wc] fp32, or the uint8 video frame(s) [hc,wc,3] / [n,hc,wc,3] (u8: default, what the input is).  One warp
     launch of the existing ss_tps_warp_mask_nchw over every (frame, view) and four planes, then multiband_blend: exactly
-    `multiband_blend(tps_warp(multiband_stack(imgs), source, T, hc, wc, mode, with_mask=True))`."""
+    `multiband_blend(tps_warp(multiband_stack(imgs), source, T, hc, wc, mode, with_mask=True))`.
+    seam='dp': multiband_seam(P, seam_cell, seam_mu, seam_prior, seam_state) between the two (three more launches); 'geometric', the
+    default, is the seam where the warped weight planes cross and launches nothing more."""
     v = len(imgs)
     clip = source.dim() == 4
     if u8 is None:
         u8 = imgs[0].dtype == torch.uint8
     check_bands(bands, hc, wc)
+    if check_seam(seam) is None:
+        raise ValueError('seam must be one of %s, got None' % (SEAMS,))
+    if seam == 'dp':
+        seam_params(hc, wc, seam_cell, seam_mu, seam_prior)
+    elif seam_state is not None or seam_cell is not None or seam_mu is not None or seam_prior is not None:
+        raise ValueError("seam_state=, seam_cell=, seam_mu= and seam_prior= belong to seam='dp'")
     U = multiband_stack(imgs)
     n = U.shape[0] // v
     if (clip and source.shape[0] != n) or (not clip and n != 1) or source.shape[-3] != v:
         raise ValueError('source %s does not match %d frames of %d views' % (tuple(source.shape), n, v))
     P = tps_warp(U, _f(source).view(n * v, 63, 2), T.view(n * v, 2, 66), hc, wc, mode, with_mask=True)
     P = P.view(n, v, 5, hc, wc) if clip else P
+    if seam == 'dp':
+        multiband_seam(P, seam_cell, seam_mu, seam_prior, seam_state)
     return multiband_blend(P, bands, out=out, ws=ws, u8=u8)
 
 

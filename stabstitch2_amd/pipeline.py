@@ -510,32 +510,53 @@ def check_fusion(fusion_mode, bands=None):
         ops.check_bands(bands)
 
 
-def _multiband_frames(img_lists, src, T, hc, wc, warp_mode, bands, out, dev):
-    """Clips held as tensors go in chunks of MULTIBAND_FRAMES frames (the launches of one frame each), lists frame by frame."""
+def seam_options(fusion_mode, seam=None, seam_cell=None, seam_mu=None, seam_prior=None):
+    """What the callers' seam= arguments say, checked: {} for the geometric seam (no seam= given, or 'geometric'), else the keywords
+    of ops.render_multiband for the DP seam, without a state.  ValueError for seam= without MULTIBAND and for parameters without 'dp'."""
+    if ops.check_seam(seam, fusion_mode) != 'dp':
+        if seam_cell is not None or seam_mu is not None or seam_prior is not None:
+            raise ValueError("seam_cell=, seam_mu= and seam_prior= belong to seam='dp'")
+        return {}
+    return dict(seam='dp', seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior)
+
+
+def _multiband_frames(img_lists, src, T, hc, wc, warp_mode, bands, out, dev, seam=None, seam_state=None):
+    """Clips held as tensors go in chunks of MULTIBAND_FRAMES frames (the launches of one frame each), lists frame by frame.
+    seam: seam_options(); with the DP seam one state (seam_state, or a fresh one) is carried from chunk to chunk, so that a clip equals
+    its frames rendered one by one."""
     n = src.shape[0]
+    seam = dict(seam or {})
+    if seam:
+        seam['seam_cell'] = ops.seam_cell(hc, wc, seam['seam_cell'])
+        seam['seam_state'] = ops.seam_state(len(img_lists), hc, wc, seam['seam_cell'], dev) if seam_state is None else seam_state
     clips = [_as_clip(x, n) for x in img_lists]
     if all(c is not None for c in clips):
         for s in range(0, n, MULTIBAND_FRAMES):
             e = min(s + MULTIBAND_FRAMES, n)
-            ops.render_multiband([c[s:e] for c in clips], src[s:e], T[s:e], hc, wc, warp_mode, bands, out=out[s:e])
+            ops.render_multiband([c[s:e] for c in clips], src[s:e], T[s:e], hc, wc, warp_mode, bands, out=out[s:e], **seam)
         return out
     for i in range(n):
         ops.render_multiband([x[i].to(dev, non_blocking=True) for x in img_lists], src[i], T[i], hc, wc, warp_mode, bands, out=out[i],
-                             u8=False)
+                             u8=False, **seam)
     return out
 
 
 @torch.no_grad()
 def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, prescaled=False, bbox=None,
-                  size=None, bands=None):
+                  size=None, bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, seam_state=None):
     """img_lists: V lists (or tensors [N,3,H,W]) of HR frames (0..255); meshes: V tensors [1,N,7,9,2].
     -> (frames [N,3,Hc,Wc] device tensor, Hc, Wc).  AVERAGE and FEATHER fusion of clips held as tensors is ONE launch for the whole
     clip (ops.render_average_clip); lists of separate frames and LINEAR fusion go frame by frame.
     With SKIP_OUTSIDE (default) a view contributes exactly 0 on canvas tiles it cannot reach, where the reference's
     clamped sampler leaves a rounding residue of <~ 1e-2 grey levels (ops.render_average).
     MULTIBAND fusion (bands= pyramid levels, default ops.MULTIBAND_BANDS): one warp launch and the pyramid launches per chunk of
-    MULTIBAND_FRAMES frames of a clip, or per frame of a list (ops.render_multiband)."""
+    MULTIBAND_FRAMES frames of a clip, or per frame of a list (ops.render_multiband).  seam='dp' (MULTIBAND only; seam_cell=, seam_mu=,
+    seam_prior=: ops.multiband_seam) puts the content-aware seam between the warp and the blend; its temporal state runs through the
+    whole clip (seam_state: an ops.seam_state to continue from and leave behind, for a video rendered in several calls)."""
     check_fusion(fusion_mode, bands)
+    seam = seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)
+    if seam_state is not None and not seam:
+        raise ValueError("seam_state= belongs to seam='dp'")
     v = len(img_lists)
     dev = meshes[0].device
     n = meshes[0].shape[1]
@@ -545,7 +566,8 @@ def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', 
     if out is None or tuple(out.shape) != (n, 3, hc, wc) or not out.is_contiguous():
         out = torch.empty((n, 3, hc, wc), device=dev, dtype=torch.float32)      # (a buffer of another canvas is not reused)
     if fusion_mode == 'MULTIBAND':
-        _multiband_frames(img_lists, src, T, hc, wc, warp_mode, ops.MULTIBAND_BANDS if bands is None else bands, out, dev)
+        _multiband_frames(img_lists, src, T, hc, wc, warp_mode, ops.MULTIBAND_BANDS if bands is None else bands, out, dev, seam,
+                          seam_state)
         return out, hc, wc
     fused = ops.fused_render(fusion_mode)                # AVERAGE | FEATHER: the one-launch render, the formula its `fusion`
     fp = ops.render_footprints(src, T, img_h, img_w, hc, wc) if (SKIP_OUTSIDE and fused) else None
@@ -581,15 +603,18 @@ def get_stable_sqe(img1_list, img2_list, smooth_mesh1, smooth_mesh2, warp_mode, 
 
 @torch.no_grad()
 def run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', to_host=False, out=None, deterministic=False,
-                 bands=None):
+                 bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None):
     """-> (frames, Hc, Wc, smooth_mesh1, smooth_mesh2); frames = device tensor [N,3,Hc,Wc]
     (or list of HWC ndarrays with to_host=True).  out: the frames tensor of a previous call to render into; it is reused
     when the canvas still has that size (same-size clips of one stream), else a new one is allocated.
     deterministic: the conv engine's geometry-only kernel policy (ops.deterministic): a frame's bits do not depend on how many
-    frames share its launches -- resident clip == chunked passes == stream."""
+    frames share its launches -- resident clip == chunked passes == stream.
+    seam, seam_cell, seam_mu, seam_prior: MULTIBAND's seam (render_frames)."""
+    seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)      # (refused before the networks run)
     with ops.deterministic(deterministic):
         acc = estimate_meshes(nets, lr1, lr2)
-    frames, hc, wc = render_frames([hr1, hr2], [acc['smooth_mesh1'], acc['smooth_mesh2']], warp_mode, fusion_mode, out=out, bands=bands)
+    frames, hc, wc = render_frames([hr1, hr2], [acc['smooth_mesh1'], acc['smooth_mesh2']], warp_mode, fusion_mode, out=out, bands=bands,
+                                   seam=seam, seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior)
     if to_host:
         host = frames.permute(0, 2, 3, 1).cpu().numpy()
         frames = [host[i] for i in range(host.shape[0])]
@@ -617,14 +642,16 @@ def three_view_compose(w12_m1, w12_m2, w23_m1, w23_m2, img_h, img_w, first_canva
 
 
 @torch.no_grad()
-def three_view_render(img1, img2, img3, mesh1, middle, mesh3, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, bands=None):
-    """Meshes are HR-scale canvas pixels here (output of three_view_compose)."""
-    return render_frames([img1, img2, img3], [mesh1, middle, mesh3], warp_mode, fusion_mode, out=out, prescaled=True, bands=bands)
+def three_view_render(img1, img2, img3, mesh1, middle, mesh3, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, bands=None, **seam):
+    """Meshes are HR-scale canvas pixels here (output of three_view_compose).  seam: render_frames' seam= keywords."""
+    return render_frames([img1, img2, img3], [mesh1, middle, mesh3], warp_mode, fusion_mode, out=out, prescaled=True, bands=bands,
+                         **seam)
 
 
 @torch.no_grad()
 def run_three_view(hr1, hr2, hr3, lr1, lr2, lr3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, deterministic=False,
-                   bands=None):
+                   bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None):
+    seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)
     # the middle view's TemporalNet motions and SpatialNet trunk features are computed once and reused by pair (2,3)
     with ops.deterministic(deterministic):
         a12 = estimate_meshes(nets, lr1, lr2, keep_spatial_cache2=True)
@@ -632,7 +659,8 @@ def run_three_view(hr1, hr2, hr3, lr1, lr2, lr3, nets, warp_mode='NORMAL', fusio
     img_h, img_w = hr1[0].shape[-2:]
     m1, mid, m3 = three_view_compose(a12['smooth_mesh1'], a12['smooth_mesh2'], a23['smooth_mesh1'],
                                      a23['smooth_mesh2'], img_h, img_w)
-    frames, hc, wc = three_view_render(hr1, hr2, hr3, m1, mid, m3, warp_mode, fusion_mode, out=out, bands=bands)
+    frames, hc, wc = three_view_render(hr1, hr2, hr3, m1, mid, m3, warp_mode, fusion_mode, out=out, bands=bands, seam=seam,
+                                       seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior)
     return frames, hc, wc, m1, mid, m3
 
 
@@ -696,8 +724,9 @@ def _as_device_u8(frames, device):
 
 
 @torch.no_grad()
-def run_two_view_u8(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False):
+def run_two_view_u8(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False, **seam):
     """uint8 in, uint8 out: ingest -> estimate -> render -> video frames.  -> (uint8 [N,Hc,Wc,3], Hc, Wc, m1, m2)."""
+    seam_options(fusion_mode, **seam)        # (MULTIBAND's seam= keywords: render_frames)
     if _u8_fused(fusion_mode):
         f1, f2 = _as_device_u8(frames1, device), _as_device_u8(frames2, device)
         _, lr1 = ops.ingest_u8(f1, want_hr=False)
@@ -708,16 +737,17 @@ def run_two_view_u8(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVE
         return (u8.cpu().numpy() if to_host else u8), hc, wc, m1, m2
     hr1, lr1 = load_frames_u8(frames1, device=device)
     hr2, lr2 = load_frames_u8(frames2, device=device)
-    frames, hc, wc, m1, m2 = run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode, fusion_mode)
+    frames, hc, wc, m1, m2 = run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode, fusion_mode, **seam)
     return to_video_frames(frames, to_host), hc, wc, m1, m2
 
 
 @torch.no_grad()
-def run_three_view_u8(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False):
+def run_three_view_u8(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False, **seam):
     """`run_three_view` from decoded uint8 frames [N,H,W,3] to uint8 video frames (device-resident clip).
     -> (uint8 [N,Hc,Wc,3], Hc, Wc, mesh1, middle, mesh3)."""
     f = [_as_device_u8(x, device) for x in (frames1, frames2, frames3)]
     img_h, img_w = f[0].shape[1], f[0].shape[2]
+    seam_options(fusion_mode, **seam)        # (MULTIBAND's seam= keywords: render_frames)
     if _u8_fused(fusion_mode):
         lr = [ops.ingest_u8(x, want_hr=False)[1] for x in f]
         a12 = estimate_meshes(nets, lr[0], lr[1], keep_spatial_cache2=True)
@@ -727,7 +757,7 @@ def run_three_view_u8(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusio
         return (u8.cpu().numpy() if to_host else u8), hc, wc, ms[0], ms[1], ms[2]
     io = [ops.ingest_u8(x) for x in f]
     frames, hc, wc, m1, mid, m3 = run_three_view(io[0][0], io[1][0], io[2][0], io[0][1], io[1][1], io[2][1], nets, warp_mode,
-                                                 fusion_mode)
+                                                 fusion_mode, **seam)
     return to_video_frames(frames, to_host), hc, wc, m1, mid, m3
 
 
@@ -965,9 +995,10 @@ class LongVideoStitcher:
     kernel per launch size (ss_conv_uses_wino43 / ss_conv_uses_winograd / split-K), and another chunk length sums in another order
     (~1e-5 px; set SS_WINO43_MIN_WGS=1 to pin the kernel choice per layer) -- hence so do the canvas and the frames."""
 
-    def __init__(self, nets, device='cuda', warp_mode='NORMAL', fusion_mode='AVERAGE', chunk=None, numa_bind=False):
+    def __init__(self, nets, device='cuda', warp_mode='NORMAL', fusion_mode='AVERAGE', chunk=None, numa_bind=False, **seam):
         self.nets, self.dev = nets, torch.device(device)
         self.warp_mode, self.fusion_mode = warp_mode, fusion_mode
+        self.seam = seam_options(fusion_mode, **seam)        # MULTIBAND's seam= keywords (render_frames); one state per render()
         self.chunk = chunk or SPATIAL_CHUNK
         self.io = HostClipRunner(nets, device, warp_mode, fusion_mode, numa_bind=numa_bind)
         self.acc = self.meshes = self.bbox = self.hc = self.wc = None
@@ -1047,6 +1078,9 @@ class LongVideoStitcher:
         io = self.io
         pending = None
         k = 0
+        seam = dict(self.seam)
+        if seam:                             # the seam's temporal state runs through the chunks
+            seam['seam_state'] = ops.seam_state(len(views), self.hc, self.wc, seam['seam_cell'], self.dev)
         for s, e, d, ev in self._uploads(views):
             io.comp.wait_event(ev)
             with torch.cuda.stream(io.comp):
@@ -1057,7 +1091,7 @@ class LongVideoStitcher:
                 else:
                     hrs = [ops.ingest_u8(t)[0] for t in d]
                     fr, _, _ = render_frames(hrs, ms, self.warp_mode, self.fusion_mode, prescaled=self.prescaled,
-                                             bbox=self.bbox, size=(self.hc, self.wc))
+                                             bbox=self.bbox, size=(self.hc, self.wc), **seam)
                     u8 = ops.canvas_to_u8(fr, out=io.out_buffer((e - s, self.hc, self.wc, 3)))
                 ev2 = torch.cuda.Event()
                 ev2.record(io.comp)
@@ -1073,8 +1107,8 @@ class LongVideoStitcher:
             yield pending[1], pending[2], pending[3]
 
 
-def _run_long(views, nets, warp_mode, fusion_mode, device, chunk, sink):
-    st = LongVideoStitcher(nets, device, warp_mode, fusion_mode, chunk)
+def _run_long(views, nets, warp_mode, fusion_mode, device, chunk, sink, seam={}):
+    st = LongVideoStitcher(nets, device, warp_mode, fusion_mode, chunk, **seam)
     st.estimate(*views)
     video = None
     if sink is None:
@@ -1090,18 +1124,18 @@ def _run_long(views, nets, warp_mode, fusion_mode, device, chunk, sink):
 
 @torch.no_grad()
 def run_two_view_long(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', chunk=None,
-                      sink=None):
+                      sink=None, **seam):
     """`run_two_view_u8` for videos that do not fit the device: frames1, frames2 = uint8 [N,H,W,3] host arrays (anything
     sliceable along frames: ndarray, pinned tensor, np.memmap), rendered onto the reference's single global canvas
     (LongVideoStitcher).  sink(video_chunk [m,Hc,Wc,3] uint8 host tensor, s, e) receives the stitched frames in order
     (e.g. cv2.VideoWriter.write per frame, test_online_tra.py:409-417); without a sink they are collected into one
     ndarray.  -> (video | None, Hc, Wc, smooth_mesh1, smooth_mesh2)."""
-    return _run_long((frames1, frames2), nets, warp_mode, fusion_mode, device, chunk, sink)
+    return _run_long((frames1, frames2), nets, warp_mode, fusion_mode, device, chunk, sink, seam)
 
 
 @torch.no_grad()
 def run_three_view_long(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', chunk=None,
-                        sink=None):
+                        sink=None, **seam):
     """`run_three_view` (test_online_tra_threeview.py:154-505) for host-resident uint8 videos of any length, on the
     reference's single global canvas.  -> (video | None, Hc, Wc, mesh1, middle, mesh3), the meshes in canvas pixels."""
-    return _run_long((frames1, frames2, frames3), nets, warp_mode, fusion_mode, device, chunk, sink)
+    return _run_long((frames1, frames2, frames3), nets, warp_mode, fusion_mode, device, chunk, sink, seam)
