@@ -724,8 +724,10 @@ def _as_device_u8(frames, device):
 
 
 @torch.no_grad()
-def run_two_view_u8(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False, **seam):
-    """uint8 in, uint8 out: ingest -> estimate -> render -> video frames.  -> (uint8 [N,Hc,Wc,3], Hc, Wc, m1, m2)."""
+def run_two_view_u8(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False, bands=None, **seam):
+    """uint8 in, uint8 out: ingest -> estimate -> render -> video frames.  -> (uint8 [N,Hc,Wc,3], Hc, Wc, m1, m2).
+    bands: MULTIBAND's pyramid levels (render_frames; None: ops.MULTIBAND_BANDS)."""
+    check_fusion(fusion_mode, bands)
     seam_options(fusion_mode, **seam)        # (MULTIBAND's seam= keywords: render_frames)
     if _u8_fused(fusion_mode):
         f1, f2 = _as_device_u8(frames1, device), _as_device_u8(frames2, device)
@@ -737,14 +739,16 @@ def run_two_view_u8(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVE
         return (u8.cpu().numpy() if to_host else u8), hc, wc, m1, m2
     hr1, lr1 = load_frames_u8(frames1, device=device)
     hr2, lr2 = load_frames_u8(frames2, device=device)
-    frames, hc, wc, m1, m2 = run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode, fusion_mode, **seam)
+    frames, hc, wc, m1, m2 = run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode, fusion_mode, bands=bands, **seam)
     return to_video_frames(frames, to_host), hc, wc, m1, m2
 
 
 @torch.no_grad()
-def run_three_view_u8(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False, **seam):
-    """`run_three_view` from decoded uint8 frames [N,H,W,3] to uint8 video frames (device-resident clip).
+def run_three_view_u8(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False, bands=None,
+                      **seam):
+    """`run_three_view` from decoded uint8 frames [N,H,W,3] to uint8 video frames (device-resident clip); bands: as run_two_view_u8.
     -> (uint8 [N,Hc,Wc,3], Hc, Wc, mesh1, middle, mesh3)."""
+    check_fusion(fusion_mode, bands)
     f = [_as_device_u8(x, device) for x in (frames1, frames2, frames3)]
     img_h, img_w = f[0].shape[1], f[0].shape[2]
     seam_options(fusion_mode, **seam)        # (MULTIBAND's seam= keywords: render_frames)
@@ -757,7 +761,7 @@ def run_three_view_u8(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusio
         return (u8.cpu().numpy() if to_host else u8), hc, wc, ms[0], ms[1], ms[2]
     io = [ops.ingest_u8(x) for x in f]
     frames, hc, wc, m1, mid, m3 = run_three_view(io[0][0], io[1][0], io[2][0], io[0][1], io[1][1], io[2][1], nets, warp_mode,
-                                                 fusion_mode, **seam)
+                                                 fusion_mode, bands=bands, **seam)
     return to_video_frames(frames, to_host), hc, wc, m1, mid, m3
 
 
@@ -995,9 +999,11 @@ class LongVideoStitcher:
     kernel per launch size (ss_conv_uses_wino43 / ss_conv_uses_winograd / split-K), and another chunk length sums in another order
     (~1e-5 px; set SS_WINO43_MIN_WGS=1 to pin the kernel choice per layer) -- hence so do the canvas and the frames."""
 
-    def __init__(self, nets, device='cuda', warp_mode='NORMAL', fusion_mode='AVERAGE', chunk=None, numa_bind=False, **seam):
+    def __init__(self, nets, device='cuda', warp_mode='NORMAL', fusion_mode='AVERAGE', chunk=None, numa_bind=False, bands=None, **seam):
         self.nets, self.dev = nets, torch.device(device)
         self.warp_mode, self.fusion_mode = warp_mode, fusion_mode
+        check_fusion(fusion_mode, bands)
+        self.bands = bands                                   # MULTIBAND's pyramid levels (render_frames; None: ops.MULTIBAND_BANDS)
         self.seam = seam_options(fusion_mode, **seam)        # MULTIBAND's seam= keywords (render_frames); one state per render()
         self.chunk = chunk or SPATIAL_CHUNK
         self.io = HostClipRunner(nets, device, warp_mode, fusion_mode, numa_bind=numa_bind)
@@ -1091,7 +1097,7 @@ class LongVideoStitcher:
                 else:
                     hrs = [ops.ingest_u8(t)[0] for t in d]
                     fr, _, _ = render_frames(hrs, ms, self.warp_mode, self.fusion_mode, prescaled=self.prescaled,
-                                             bbox=self.bbox, size=(self.hc, self.wc), **seam)
+                                             bbox=self.bbox, size=(self.hc, self.wc), bands=self.bands, **seam)
                     u8 = ops.canvas_to_u8(fr, out=io.out_buffer((e - s, self.hc, self.wc, 3)))
                 ev2 = torch.cuda.Event()
                 ev2.record(io.comp)
@@ -1107,8 +1113,8 @@ class LongVideoStitcher:
             yield pending[1], pending[2], pending[3]
 
 
-def _run_long(views, nets, warp_mode, fusion_mode, device, chunk, sink, seam={}):
-    st = LongVideoStitcher(nets, device, warp_mode, fusion_mode, chunk, **seam)
+def _run_long(views, nets, warp_mode, fusion_mode, device, chunk, sink, seam={}, bands=None):
+    st = LongVideoStitcher(nets, device, warp_mode, fusion_mode, chunk, bands=bands, **seam)
     st.estimate(*views)
     video = None
     if sink is None:
@@ -1124,18 +1130,18 @@ def _run_long(views, nets, warp_mode, fusion_mode, device, chunk, sink, seam={})
 
 @torch.no_grad()
 def run_two_view_long(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', chunk=None,
-                      sink=None, **seam):
+                      sink=None, bands=None, **seam):
     """`run_two_view_u8` for videos that do not fit the device: frames1, frames2 = uint8 [N,H,W,3] host arrays (anything
     sliceable along frames: ndarray, pinned tensor, np.memmap), rendered onto the reference's single global canvas
     (LongVideoStitcher).  sink(video_chunk [m,Hc,Wc,3] uint8 host tensor, s, e) receives the stitched frames in order
     (e.g. cv2.VideoWriter.write per frame, test_online_tra.py:409-417); without a sink they are collected into one
-    ndarray.  -> (video | None, Hc, Wc, smooth_mesh1, smooth_mesh2)."""
-    return _run_long((frames1, frames2), nets, warp_mode, fusion_mode, device, chunk, sink, seam)
+    ndarray.  bands: MULTIBAND's pyramid levels, as run_two_view_u8.  -> (video | None, Hc, Wc, smooth_mesh1, smooth_mesh2)."""
+    return _run_long((frames1, frames2), nets, warp_mode, fusion_mode, device, chunk, sink, seam, bands)
 
 
 @torch.no_grad()
 def run_three_view_long(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', chunk=None,
-                        sink=None, **seam):
+                        sink=None, bands=None, **seam):
     """`run_three_view` (test_online_tra_threeview.py:154-505) for host-resident uint8 videos of any length, on the
     reference's single global canvas.  -> (video | None, Hc, Wc, mesh1, middle, mesh3), the meshes in canvas pixels."""
-    return _run_long((frames1, frames2, frames3), nets, warp_mode, fusion_mode, device, chunk, sink, seam)
+    return _run_long((frames1, frames2, frames3), nets, warp_mode, fusion_mode, device, chunk, sink, seam, bands)

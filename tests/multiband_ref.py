@@ -188,6 +188,40 @@ def made_up(kind, views, hc, wc, seed=0):
     return P
 
 
+# canvases (hc, wc) down to one pixel: one row, one column, the smallest legal reduce (3 -> 2), a 2 x 2 level at the top of a pyramid
+# (4 x 4, 5 x 5 through 3 x 3, 6 x 7 through 3 x 4), one tile wide and three pixels high and the other way round
+SMALL = [(1, 1), (1, 9), (9, 1), (2, 2), (2, 67), (3, 3), (4, 4), (5, 5), (6, 7), (3, 130), (130, 3)]
+
+
+def small_case(views, hc, wc, seed=0):
+    """P [V,5,hc,wc] for the canvases of SMALL: uniform-noise colours; weights a permutation of 1..V hc wc (no two equal, so every
+    owner decision is between different numbers); masks Bernoulli(0.7), a quarter of them moved to made_up's fractional values on
+    their own side of 0.5.  From 2 x 2 upwards one entry is set valid and one invalid, so that both occur whatever the draw."""
+    rs = np.random.RandomState(911 + seed + 7 * hc + 13 * wc + 31 * views)
+    P = np.zeros((views, 5, hc, wc), np.float32)
+    P[:, :3] = rs.uniform(0, 255, (views, 3, hc, wc))
+    P[:, 3] = (rs.permutation(views * hc * wc) + 1).reshape(views, hc, wc)
+    m = (rs.uniform(0, 1, (views, hc, wc)) < 0.7).astype(np.float32)
+    if hc >= 2 and wc >= 2:
+        m[0, 0, 0], m[0, -1, -1] = 1.0, 0.0
+    rim = rs.uniform(0, 1, m.shape) < 0.25
+    hi, lo = rs.choice(np.array([0.5, 0.51, 0.75], np.float32), m.shape), rs.choice(np.array([0.0, 0.49, 0.25], np.float32), m.shape)
+    P[:, 4] = np.where(rim, np.where(m > 0, hi, lo), m)
+    return P
+
+
+def tied(P):
+    """A copy of P whose weight planes are equal in all views on the left half of the canvas (view 0's): where several views are valid
+    there the owner is the first of equal maxima.  -> (P, the pixels [hc,wc] where at least two valid views tie for the maximum)."""
+    P = P.copy()
+    wc = P.shape[-1]
+    P[1:, 3, :, :wc // 2] = P[0, 3, :, :wc // 2]
+    valid = P[:, 4] >= 0.5
+    w = np.where(valid, P[:, 3].astype(np.float64), -np.inf)
+    at_max = valid & (w == w.max(0)[None])
+    return P, at_max.sum(0) >= 2
+
+
 def side_by_side(h=80, w=200, lo=60, hi=140, a=100.0, b=140.0):
     """Two constant views on an h x w canvas overlapping in columns lo..hi-1, each weighted by the weight plane of its own footprint."""
     P = np.zeros((2, 5, h, w), np.float32)

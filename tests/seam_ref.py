@@ -261,6 +261,23 @@ def mismatch(hc, wc, lo, hi, rect, seed=0, colour=(250.0, 5.0, 250.0)):
     return P
 
 
+def cap_scene():
+    """P [2,2,5,4200,8], two frames for one call at cell 1, mu = 65535: colours texture (+7 in view 1), each view weighted by the
+    weight plane of its own footprint.  Frame 0: view 0 on columns 0..1, view 1 on 0..7; frame 1: view 0 on 0..7, view 1 on 6..7 --
+    held to frame 0's seam six columns from its own overlap, M reaches the cap 1 << 30 some 4000 rows down."""
+    hc, wc = 4200, 8
+    P = np.zeros((2, 2, 5, hc, wc), np.float32)
+    colours = texture(hc, wc)
+    spans = [[(0, 2), (0, 8)], [(0, 8), (6, 8)]]                              # [frame][view] -> its valid columns
+    for f in range(2):
+        for v in range(2):
+            a, b = spans[f][v]
+            P[f, v, :3, :, a:b] = (colours + np.float32(7 * v))[:, :, a:b]
+            P[f, v, 3, :, a:b] = weight_plane(hc, b - a)
+            P[f, v, 4, :, a:b] = 1.0
+    return P
+
+
 def geometric_owner(P):
     """The owner map the blend derives from plane 3 (the valid view with the largest weight, the lowest index among equals)."""
     valid = P[:, 4] >= 0.5

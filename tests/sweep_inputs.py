@@ -907,7 +907,8 @@ STITCH_SHAPES = [(1, 2), (1, 7), (2, 2), (2, 7), (30, 2), (30, 7), (300, 2), (30
 # ================================================================================================ the coverage table of the library
 KS, CS, RS_ = 'test_gpu_kernel_sweeps', 'test_gpu_conv_sweeps', 'test_gpu_rest_sweeps'
 SS, NV, EX, VP = 'test_gpu_stream_sweeps', 'test_gpu_nv12', 'test_gpu_exposure', 'test_gpu_viewport'
-SWEEP_MODULES = (KS, CS, RS_, SS, NV, EX, VP)      # the modules whose kernel-level tests compare with numpy or a float64 statement
+MB, SM = 'test_gpu_multiband', 'test_gpu_seam'
+SWEEP_MODULES = (KS, CS, RS_, SS, NV, EX, VP, MB, SM)      # the modules whose kernel-level tests compare with numpy or a float64 statement
 LB_CHAIN = ('lb_init_kernel', 'lb_centroid_kernel', 'lb_range_kernel', 'lb_premask_kernel', 'lb_blur_kernel', 'lb_final_kernel')
 
 # Short names of the overloads' keys: alias -> the key overload_key() gives, base name + the parameter list of the code object.  The
@@ -1030,3 +1031,46 @@ def library_reach():
     add('identity', ['lb_clip_warp_kernel(GainViews)'], gains, ['lb_clip_warp_kernel(RenderViews)', 'tps_warp_views_kernel'])
     add('identity', ['lb_frames_warp_kernel(GainViews)'], gains, ['lb_frames_warp_kernel(RenderViews)', 'tps_warp_views_kernel'])
     return t
+
+
+# ================================================================================================ the blend and the seam libraries
+def instantiation_key(name):
+    """A demangled kernel name of libstabstitch_blend.so / libstabstitch_seam.so -> 'base<a,b,...>' as kernel_key writes it (booleans
+    as 0 / 1), the anonymous namespace dropped.  These two libraries are keyed by instantiation: there are 15 + 6 of them."""
+    return kernel_key(name.replace('(anonymous namespace)::', ''))
+
+
+def blend_reach():
+    """Every kernel instantiation of libstabstitch_blend.so -> (kind, tests), as library_reach: 'fp64' the tests that hold it to the
+    float64 statement of tests/multiband_ref.py inside its bound, 'exact' the tests that hold the uint8 output bit for bit to numpy's
+    cast of the fp32 output (which the same tests hold to float64).  mb_collapse_kernel<V, COARSE, OUT>: COARSE = 0 is the top level
+    of the pyramid; OUT = 0 writes a level (so <V,0,0> needs a band, <V,1,0> two), 1 the fp32 frame, 2 the uint8 frame -- with
+    COARSE = 0 at bands = 0 only.  tests/test_ref64.py holds the table to the code objects, test_gpu_multiband's launch witness to what
+    the smallest calls launch."""
+    t = {}
+    fp64 = [MB + '::test_blend_of_real_warps_against_fp64', MB + '::test_blend_of_made_up_masks_against_fp64',
+            MB + '::test_blend_of_small_canvases_against_fp64', MB + '::test_several_frames_in_one_call_against_fp64',
+            MB + '::test_tied_weights_go_to_the_lowest_view']
+    u8 = [MB + '::test_blend_of_small_canvases_against_fp64', MB + '::test_several_frames_in_one_call_against_fp64']
+    t['mb_reduce_kernel'] = ('fp64', tuple(fp64))
+    for v in (2, 3):
+        t['mb_prepare_kernel<%d>' % v] = ('fp64', tuple(fp64))
+        for coarse in (0, 1):
+            t['mb_collapse_kernel<%d,%d,0>' % (v, coarse)] = ('fp64', tuple(fp64))
+            t['mb_collapse_kernel<%d,%d,1>' % (v, coarse)] = ('fp64', tuple(fp64))
+            t['mb_collapse_kernel<%d,%d,2>' % (v, coarse)] = ('exact', tuple(u8))
+    return t
+
+
+def seam_reach():
+    """Every kernel instantiation of libstabstitch_seam.so -> ('exact', tests): the tests that hold it bit for bit to the integer
+    restatement of tests/seam_ref.py."""
+    tests = tuple(SM + '::' + n for n in (
+        'test_kernels_equal_the_restatement', 'test_kernels_equal_the_restatement_over_several_tile_columns',
+        'test_made_up_scenes_on_the_device', 'test_made_up_scenes_on_either_side_of_a_tile_boundary',
+        'test_grids_of_more_than_256_rows_of_cells', 'test_the_cap_on_M', 'test_an_unaligned_P_takes_the_scalar_loads'))
+    three = tuple(SM + '::' + n for n in (
+        'test_kernels_equal_the_restatement', 'test_kernels_equal_the_restatement_over_several_tile_columns',
+        'test_view_order_follows_the_extents_on_the_device', 'test_an_unaligned_P_takes_the_scalar_loads'))
+    return {'%s<%d>' % (k, v): ('exact', tests if v == 2 else three) for k in ('sm_cost_kernel', 'sm_dp_kernel', 'sm_paint_kernel')
+            for v in (2, 3)}

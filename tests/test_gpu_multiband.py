@@ -1,5 +1,6 @@
 """MULTIBAND fusion on the GPU (libstabstitch_blend.so): the library against the float64 statement of
-tests/multiband_ref.py inside its derived bound E(B) at every pixel, the identities between the entry points and the routes bit for
+tests/multiband_ref.py inside its derived bound E(B) at every pixel (canvases down to one pixel, several frames per call, tied weights,
+NaN under the mask), the launches of the blend and seam libraries, the identities between the entry points and the routes bit for
 bit, and the streaming stitchers under fusion_mode='MULTIBAND' against the ops render of their own splines and against each other.
     python -m pytest tests -m gpu"""
 import functools
@@ -86,6 +87,103 @@ def test_blend_clamps_both_ways(dev, size):
     assert raw.min() < -20 and raw.max() > 275
     got = _check(dev, 'clamp', T(Ph).to(dev), Ph, 3)
     assert got.min() == 0.0 and got.max() == 255.0 and (got == 0).sum() > 50 and (got == 255).sum() > 50
+
+
+@pytest.mark.parametrize('views', [2, 3])
+@pytest.mark.parametrize('size', MR.SMALL, ids=lambda s: '%dx%d' % s)
+def test_blend_of_small_canvases_against_fp64(dev, size, views):
+    """mb_plan accepts hc, wc >= 1: one pixel, one row, one column, 3 -> 2, a 2 x 2 top level, at every band count the canvas allows.
+    fp32 inside the bound and between canaries, uint8 = the cast of the fp32 output (numpy's and ops.canvas_to_u8's), one band more
+    refused.  The fp32 numpy evaluation of the statement stays under 0.02 of the bound on these inputs: a wrong tap is not inside it."""
+    from stabstitch2_amd import ops
+    from test_gpu_rest_sweeps import canaried, canaries_intact
+    hc, wc = size
+    Ph = MR.small_case(views, hc, wc)
+    P = T(Ph).to(dev)
+    valid = Ph[:, 4] >= 0.5
+    assert len(np.unique(Ph[:, 3])) == Ph[:, 3].size                            # no ties
+    if hc >= 2 and wc >= 2:
+        assert valid.any() and not valid.all()                                  # a valid and an invalid pixel
+    top = MR.max_bands(hc, wc)
+    worst = 0.0
+    for b in range(top + 1):
+        ref = MR.blend(Ph, b)
+        buf, mid = canaried(3 * hc * wc, dev)
+        got = ops.multiband_blend(P, b, out=mid.view(3, hc, wc))
+        canaries_intact(buf, 3 * hc * wc, 'multiband_blend %s B%d' % (size, b))
+        err = float(np.abs(got.cpu().numpy().astype(np.float64) - ref).max())
+        worst = max(worst, err / MR.bound(b, views))
+        assert err <= MR.bound(b, views), (size, views, b, err, MR.bound(b, views))
+        buf8, mid8 = canaried(hc * wc * 3, dev, dtype=torch.uint8, value=0xAB)
+        got8 = ops.multiband_blend(P, b, out=mid8.view(hc, wc, 3), u8=True)
+        canaries_intact(buf8, hc * wc * 3, 'multiband_blend u8 %s B%d' % (size, b), value=0xAB)
+        assert np.array_equal(got8.cpu().numpy(), G.astype_u8(got.cpu().numpy()).transpose(1, 2, 0)), (size, views, b)
+        _same(got8, ops.canvas_to_u8(got.clone()[None])[0], ('u8', size, views, b))
+    print('\n[multiband claim] %d x %d V%d, bands 0..%d: worst |diff| = %.4f of the bound; %d of %d mask values valid'
+          % (hc, wc, views, top, worst, int(valid.sum()), valid.size))
+    if top < MR.MAX_BANDS:
+        with pytest.raises(ValueError):
+            ops.multiband_blend(P, top + 1)
+
+
+@pytest.mark.parametrize('views', [2, 3])
+@pytest.mark.parametrize('size', [MR.CASES[5], MR.CASES[1]], ids=lambda s: '%dx%d_to_%dx%d' % s)
+def test_several_frames_in_one_call_against_fp64(dev, size, views):
+    """Three different frames in one call (frames ride in gridDim.z, at their own offsets of P, the workspace and the output): each
+    against the float64 statement of its own P, fp32 and the uint8 cast, at 0 bands and at the most."""
+    from stabstitch2_amd import ops
+    h, w, hc, wc = size
+    n = 3
+    U, src, tgt = G.warp_case(n * views, h, w, hc, wc, seed=12)
+    sd = T(src).to(dev)
+    clips = [T(np.ascontiguousarray(U[v::views, :3])).to(dev) for v in range(views)]
+    P = ops.tps_warp(ops.multiband_stack(clips), sd, ops.tps_solve(sd, T(tgt).to(dev)), hc, wc, 'NORMAL', with_mask=True).view(n, views, 5, hc, wc)
+    Ph = P.cpu().numpy()
+    assert not np.array_equal(Ph[0], Ph[1]) and not np.array_equal(Ph[1], Ph[2]) and not np.array_equal(Ph[0], Ph[2])
+    for b in (0, MR.max_bands(hc, wc)):
+        got = ops.multiband_blend(P, b)
+        got8 = ops.multiband_blend(P, b, u8=True).cpu().numpy()
+        assert got.shape == (n, 3, hc, wc)
+        for f in range(n):
+            err = float(np.abs(got[f].cpu().numpy().astype(np.float64) - MR.blend(Ph[f], b)).max())
+            assert err <= MR.bound(b, views), (f, views, b, err, MR.bound(b, views))
+            assert np.array_equal(got8[f], G.astype_u8(got[f].cpu().numpy()).transpose(1, 2, 0)), (f, views, b)
+
+
+@pytest.mark.parametrize('views', [2, 3])
+@pytest.mark.parametrize('size', [MR.CASES[5], MR.CASES[1]], ids=lambda s: '%dx%d_to_%dx%d' % s)
+def test_tied_weights_go_to_the_lowest_view(dev, size, views):
+    """The 'hole' masks with the weight planes equal in all views on the left half of the canvas: the statement's first of equal maxima
+    and the kernel's strict `>` from view 0 upwards name the same owner; noise colours, so another owner is grey levels away."""
+    hc, wc = size[2:]
+    Ph, ties = MR.tied(MR.made_up('hole', views, hc, wc))
+    assert ties[:, :wc // 2].sum() > 100 and not ties[:, wc // 2:].any()        # tied, doubly valid pixels exist
+    other = Ph.copy()                                                           # (the same pixels given to the highest tied view instead)
+    other[:, 3, :, :wc // 2] += np.arange(views, dtype=np.float32)[:, None, None]
+    assert np.abs(MR.blend(other, 0) - MR.blend(Ph, 0)).max() > 1.0
+    P = T(Ph).to(dev)
+    for b in bands_of(hc, wc):
+        _check(dev, 'tied', P, Ph, b)
+
+
+@pytest.mark.parametrize('views', [2, 3])
+def test_invalid_pixels_carry_nothing(dev, views):
+    """P of a real warp with planes 0..3 of every pixel below the 0.5 mask set to NaN: the output has the bits of the unmodified P's,
+    fp32 and uint8 -- the decisions read the mask first, and no arithmetic touches what an invalid view holds."""
+    from stabstitch2_amd import ops
+    size = MR.CASES[1]
+    hc, wc = size[2:]
+    P, Ph = _warped(dev, size, views)
+    invalid = P[:, 4] < 0.5
+    Q = P.clone()
+    Q[:, :4] = torch.where(invalid[:, None], torch.full_like(Q[:, :4], float('nan')), Q[:, :4])
+    assert int(invalid.sum()) > 100 and int(torch.isnan(Q).sum()) == 4 * int(invalid.sum()) and not bool(torch.isnan(Q[:, 4]).any())
+    assert bool((~invalid).sum(0).eq(0).any())                                  # pixels outside the union too
+    for b in bands_of(hc, wc):
+        want = ops.multiband_blend(P, b)
+        _same(ops.multiband_blend(Q, b), want, ('fp32', views, b))
+        _same(ops.multiband_blend(Q, b, u8=True), ops.multiband_blend(P, b, u8=True), ('u8', views, b))
+        assert not bool(torch.isnan(want).any())
 
 
 # ================================================================================================ identities, bit for bit
@@ -366,3 +464,33 @@ def test_refusals(dev, hip_nets):
                  lambda: online.PipelinedThreeViewOnlineStitcher(hip_nets, SH, SW, fusion_mode='MULTIBAND')):
         with pytest.raises(ValueError, match='MULTIBAND'):
             make()
+
+
+# ================================================================================================ the launches of the two libraries
+def test_every_instantiation_of_the_blend_and_seam_libraries_is_launched(dev):
+    """The smallest calls under torch.profiler -- a 5 x 5 canvas, V = 2 and 3, bands 0, 1 and 2 (a level written from a coarser one
+    needs two), fp32 and uint8, and one seam call each -- launch every instantiation that sweep_inputs.blend_reach and seam_reach
+    list, and nothing else of the two libraries.  Should the profiler report names without template arguments, base names are matched
+    instead and the test says so in its output."""
+    import re
+    from stabstitch2_amd import ops
+    from test_gpu_linear_frames import _kernel_names
+    launched = []
+    for v in (2, 3):
+        P = T(MR.small_case(v, 5, 5)).to(dev)
+        calls = [lambda b=b, u8=u8: ops.multiband_blend(P, b, u8=u8) for b in (0, 1, 2) for u8 in (False, True)]
+        calls.append(lambda: ops.multiband_seam(P.clone(), 1, 0, 8.0))
+        for fn in calls:
+            fn()                                     # (once outside the profiler: module load)
+            launched += _kernel_names(fn)[1]
+    ours = sorted({k for k in launched if re.search(r'\b(mb|sm)_[a-z]+_kernel', k)})
+    wanted = set(G.blend_reach()) | set(G.seam_reach())
+    assert len(wanted) == 21
+    if all('<' in k for k in ours if 'mb_reduce_kernel' not in k):
+        got = {G.instantiation_key(k) for k in ours}
+        print('\n[launch witness] matched by template arguments: %s' % sorted(got))
+        assert got == wanted, (sorted(wanted - got), sorted(got - wanted))
+    else:
+        got = {re.search(r'\b((?:mb|sm)_[a-z]+_kernel)', k).group(1) for k in ours}
+        print('\n[launch witness] the profiler reports no template arguments; matched by base name: %s' % ours)
+        assert got == {k.split('<')[0] for k in wanted}, (got, ours)

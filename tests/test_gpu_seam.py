@@ -1,7 +1,9 @@
 """MULTIBAND's content-aware seam on the GPU (libstabstitch_seam.so): the three kernels against the integer restatement
 of tests/seam_ref.py bit for bit on P of real warps, the call shapes, the blend with a painted seam, the unchanged geometric seam, the
 streaming stitchers and the pipeline under seam='dp' against the ops render of their own splines fed the same state sequence, and the
-scene the feature is for: an object only one camera sees, standing on the geometric seam.  Every comparison is exact.
+scene the feature is for: an object only one camera sees, standing on the geometric seam.  The kernels again where their indexing
+changes -- several tile columns of the cost pass at cells above 1, grids of more than 256 rows of cells, the cap on M, a P that is not
+16-byte aligned -- and the uint8 and long-video routes of the pipeline with bands= and either seam.  Every comparison is exact.
     python -m pytest tests -m gpu"""
 import functools
 import gc
@@ -78,7 +80,10 @@ def _against_the_restatement(dev, P, cell, mu, prior, with_state=True):
         assert parts['meta'][f, :3].tolist() == ref['order'][f] + [-1] * (3 - v), ('order', f)
         assert parts['meta'][f, 3:3 + v - 1].tolist() == ref['seam_cost'][f], ('seam cost', f)
         for p in range(v - 1):
-            assert ref['seam_cost'][f][p] == SR.optimum(ref['energy'][f][p]), ('optimum', f, p)
+            if ref['seam_cost'][f][p] == SR.MCAP:                  # M is capped, the optimum is uncapped int64
+                assert SR.optimum(ref['energy'][f][p]) >= SR.MCAP, ('optimum at the cap', f, p)
+            else:
+                assert ref['seam_cost'][f][p] == SR.optimum(ref['energy'][f][p]), ('optimum', f, p)
     assert np.array_equal(parts['seams'], ref['seams'])
     assert np.array_equal(got.cpu().numpy(), ref['P'])
     if with_state:
@@ -130,6 +135,147 @@ def test_made_up_scenes_on_the_device(dev):
     N[0, 4, :, 40:] = 0.0
     for Ph in (E, N):
         _against_the_restatement(dev, T(Ph[None]).to(dev), 4, 200, 8.0)
+
+
+# ================================================================================================ where the indexing changes
+def _tile_columns(nb, cell):
+    """The tile columns of the cost pass (SSM_TILE_W = 256 canvas columns each) that hold an overlap cell of the plane nb."""
+    return sorted({int(cx) * cell // 256 for cx in np.flatnonzero((nb > 0).any(0))})
+
+
+WIDE_CASES = [  # canvases over 256 columns at every cell size above 1: three tile columns, several tile rows
+    ((36, 400, 37, 530), 2, 2, 1, None), ((36, 400, 37, 530), 3, 4, 5, (2, 0, 1)),
+    ((72, 520, 81, 700), 2, 8, 1, None), ((72, 520, 81, 700), 3, 16, 5, (1, 2, 0)),
+]
+
+
+@pytest.mark.parametrize('size,views,cell,frames,perm', WIDE_CASES,
+                         ids=lambda x: 'x'.join(map(str, x)) if isinstance(x, tuple) else str(x))
+def test_kernels_equal_the_restatement_over_several_tile_columns(dev, size, views, cell, frames, perm):
+    """cx0 = x0 >> shift with x0 > 0, the row flags of three tiles per row of cells and their OR, the extents of gx * gy tiles: frames
+    wider than half the canvas, so that any two views overlap wherever the warp puts them."""
+    hc, wc = size[2:]
+    gx, gy = -(-wc // 256), -(-hc // max(4, cell))
+    assert cell > 1 and gx == 3 and gy > 1
+    P = _warped(dev, size, views, frames, perm=perm)
+    ref = _against_the_restatement(dev, P, cell, 48 * cell, 8.0)
+    assert ref['seams'].shape == (frames, views - 1, SR.grid(hc, wc, cell)[0])
+    assert any((nb > 0).any() for f in ref['cost'] for _, nb, _ in f)          # some overlap somewhere
+    held = sorted({t for f in ref['cost'] for _, nb, _ in f for t in _tile_columns(nb, cell)})
+    print('\n[seam claim] %d x %d, V = %d, cell %d: gx %d, gy %d, overlap cells in the tile columns %s' % (hc, wc, views, cell, gx, gy, held))
+    assert any(t > 0 for t in held)                                            # ... and some of it past the first tile column
+    _against_the_restatement(dev, P, cell, 0, 255.0, with_state=False)
+
+
+@pytest.mark.parametrize('cell', [2, 4, 16])
+def test_made_up_scenes_on_either_side_of_a_tile_boundary(dev, cell):
+    """Without a warp, on 37 x 530: an overlap that lies wholly in tile column 1 (every cell of tile columns 0 and 2 is NONE, the
+    rows are not free), and one that straddles the boundary at column 256 with the object on it; two frames per call, so that with a
+    state the second runs under the temporal term."""
+    first = 256 // cell                                                       # the first cell column of tile column 1
+    inside = SR.side_by_side(37, 530, 300, 420)
+    across = SR.mismatch(37, 530, 200, 330, (12, 25, 240, 280))
+    for with_state in (True, False):
+        for name, scene in (('inside', inside), ('across', across)):
+            P = T(np.stack([scene, scene])).to(dev)
+            ref = _against_the_restatement(dev, P, cell, 48 * cell, 8.0, with_state=with_state)
+            nb = ref['cost'][0][0][1]
+            cols = np.flatnonzero((nb > 0).any(0))
+            print('\n[seam claim] %s at cell %d%s: overlap cells in columns %d..%d, tile columns %s (tile column 1 starts at cell %d)'
+                  % (name, cell, '' if with_state else ', no state', cols.min(), cols.max(), _tile_columns(nb, cell), first))
+            if name == 'inside':
+                assert cols.min() >= first and _tile_columns(nb, cell) == [1]      # no overlap cell has cx < 256 >> shift
+            else:
+                assert cols.min() < first <= cols.max() and _tile_columns(nb, cell) == [0, 1]
+
+
+TALL_CASES = [((300, 61), 1, (320, 48)), ((530, 37), 2, (640, 30))]          # canvas, cell, the frame of the real warp (taller than the
+#                                                                               canvas: every view reaches the rows of the second trip)
+
+
+@pytest.mark.parametrize('canvas,cell,frame', TALL_CASES, ids=lambda x: 'x'.join(map(str, x)) if isinstance(x, tuple) else str(x))
+def test_grids_of_more_than_256_rows_of_cells(dev, canvas, cell, frame):
+    """hq = 300 and 265: every `for (y = tid; y < hq; y += 256)` loop of the dp kernel takes a second trip -- the xprev load, rowany,
+    the seam and the state stores.  Frames A, B, A (B: an object only view 1 sees, on the geometric seam) in one call with a state and
+    again as three calls.  With the object over the middle third of the rows the seams of A and B differ in rows 106..204 (87..177)
+    only -- a seam leaves its column by one cell per row and is back long before row 256 -- so the object also stands over the last
+    third: there the seams differ in rows >= 256, and the third frame, A again, is held to B's seam there by the temporal term."""
+    from stabstitch2_amd import ops
+    hc, wc = canvas
+    hq = SR.grid(hc, wc, cell)[0]
+    assert hq > 256 and SR.lds_bytes(hc, wc, cell) < 9 * 1024
+    lo, hi, mu = wc // 4, 3 * wc // 4, 48 * cell
+    x0, x1 = wc // 2 - wc // 8, wc // 2 + wc // 8
+    A = SR.side_by_side(hc, wc, lo, hi)
+    for where, rows in (('middle', (hc // 3, 2 * hc // 3)), ('last', (2 * hc // 3, hc))):
+        clip = np.stack([A, SR.mismatch(hc, wc, lo, hi, rows + (x0, x1)), A])
+        P = T(clip).to(dev)
+        ref = _against_the_restatement(dev, P, cell, mu, 8.0)                  # one call: seams, painted planes, the state after it
+        seams = ref['seams'][:, 0]
+        differ, held = np.flatnonzero(seams[0] != seams[1]), np.flatnonzero(seams[2] != seams[0])
+        print('\n[seam claim] %d x %d at cell %d, hq = %d, the object over the %s third: the seams of A and B differ in rows %d..%d, '
+              'the held A and the fresh A in rows %d..%d' % (hc, wc, cell, hq, where, differ.min(), differ.max(), held.min(), held.max()))
+        assert differ.size and held.size
+        if where == 'last':
+            assert differ.max() >= 256 and held.max() >= 256
+        state, ref_state = ops.seam_state(2, hc, wc, cell, dev), SR.fresh_state(2, hc, wc, cell)
+        SR.seam(clip, cell, mu, 8.0, ref_state)
+        for f in range(3):                                                     # three calls
+            assert np.array_equal(ops.multiband_seam(P[f].clone(), cell, mu, 8.0, state).cpu().numpy(), ref['P'][f]), (where, f)
+        assert np.array_equal(state.cpu().numpy(), ref_state) and (ref_state[SR.HEADER + 256:] > 0).all()
+    P = _warped(dev, frame + canvas, 2, 3)
+    ref = _against_the_restatement(dev, P, cell, mu, 8.0)
+    assert any((nb[256:] > 0).any() for f in ref['cost'] for _, nb, _ in f)    # overlap in the rows of the second trip
+    _against_the_restatement(dev, P, cell, 0, 255.0, with_state=False)
+
+
+def test_the_cap_on_M(dev):
+    """SM_MCAP on the device: frame 1 is held at mu = 65535 to frame 0's seam at column 0, six columns away from its own overlap; M
+    saturates at 1 << 30 some 4000 rows down, and from there every M of a row ties: straight, then left, then right, and the lowest
+    x of the last row decide the seam."""
+    hc, wc = 4200, 8
+    assert SR.lds_bytes(hc, wc, 1) == 58928
+    ref = _against_the_restatement(dev, T(SR.cap_scene()).to(dev), 1, 65535, 8.0)
+    print('\n[seam claim] 4200 x 8 at cell 1: order %s, seam costs %s, the uncapped optimum of frame 1 %d'
+          % (ref['order'], ref['seam_cost'], SR.optimum(ref['energy'][1][0])))
+    assert ref['order'] == [[0, 1], [0, 1]] and ref['seam_cost'][0] == [88143]
+    assert ref['seam_cost'][1] == [SR.MCAP] and SR.optimum(ref['energy'][1][0]) == 1101092922
+
+
+@pytest.mark.parametrize('size,views,frames', [((72, 96, 37, 64), 2, 1), ((72, 96, 81, 128), 3, 2)],
+                         ids=lambda x: 'x'.join(map(str, x)) if isinstance(x, tuple) else str(x))
+def test_an_unaligned_P_takes_the_scalar_loads(dev, size, views, frames):
+    """P at 4, 8 and 12 bytes past a 16-byte boundary (al4 == false: four scalar loads per quad) on canvases whose rows are whole quads,
+    where the aligned call takes the 16-byte loads: the same painted planes, workspace and state, bit for bit, in place, and nothing
+    written in front of P or behind it."""
+    from stabstitch2_amd import ops
+    from test_gpu_rest_sweeps import canaried, canaries_intact
+    hc, wc = size[2:]
+    cell, mu = 4, 192
+    P = _warped(dev, size, views, frames).contiguous()
+    assert wc % 4 == 0 and P.data_ptr() % 16 == 0
+    ref = _against_the_restatement(dev, P, cell, mu, 8.0)
+    assert any((nb > 0).any() for f in ref['cost'] for _, nb, _ in f)
+    state = ops.seam_state(views, hc, wc, cell, dev)
+    ws = ops.seam_workspace(frames, views, hc, wc, cell, dev).fill_(-7)
+    want = ops.multiband_seam(P.clone(), cell, mu, 8.0, state, ws=ws)
+    n, residues = P.numel(), []
+    for off in (1, 2, 3):
+        buf, mid = canaried(n + 4, dev)
+        view = mid[off:off + n].view(P.shape)
+        view.copy_(P)
+        residues.append(view.data_ptr() % 16)
+        assert view.data_ptr() % 16 != 0 and view.is_contiguous()
+        state_u = ops.seam_state(views, hc, wc, cell, dev)
+        ws_u = ops.seam_workspace(frames, views, hc, wc, cell, dev).fill_(-7)
+        got = ops.multiband_seam(view, cell, mu, 8.0, state_u, ws=ws_u)
+        assert got.data_ptr() == view.data_ptr() and torch.equal(got, want), off
+        assert torch.equal(ws_u, ws) and torch.equal(state_u, state), off
+        assert np.array_equal(got.cpu().numpy(), ref['P']), off
+        canaries_intact(buf, n + 4, 'multiband_seam at float offset %d' % off)
+        assert bool((mid[:off] == 7.0).all()) and bool((mid[off + n:] == 7.0).all()), off
+    print('\n[seam claim] %d x %d, V = %d: data_ptr() %% 16 of the aligned P 0, of the views %s' % (hc, wc, views, residues))
+    assert residues == [4, 8, 12]
 
 
 # ================================================================================================ the call shapes
@@ -357,3 +503,117 @@ def test_run_two_view_with_the_dp_seam_equals_its_frames_one_by_one(dev, hip_net
         three[0], pipeline.run_three_view(hr[0], hr[1], hr[2], lr[0], lr[1], lr[2], hip_nets, fusion_mode='MULTIBAND', bands=3)[0])
     with pytest.raises(ValueError, match='MULTIBAND'):
         pipeline.run_two_view(hr[0], hr[1], lr[0], lr[1], hip_nets, fusion_mode='LINEAR', seam='dp')
+
+
+def test_a_refit_viewport_keeps_one_state_under_the_dp_seam(dev, hip_nets, monkeypatch):
+    """viewport= with grow='refit' and seam='dp' (push_u8, the window's seven frames and two steady-state ones): every frame is the
+    ops render of the stitcher's splines of that frame at the viewport's size, fed ONE state that is never reset -- a refit moves the
+    box under a fixed grid, and the state stays."""
+    from stabstitch2_amd import online, ops
+    from test_gpu_multiband import VIEWPORTS
+    c = _clip(dev)
+    hc, wc = VIEWPORTS[2]
+    st = _make(hip_nets, 2, viewport=(hc, wc), grow='refit', bands=3, **KW)
+    solved = []
+    inner = online._Stitcher._render_solved
+
+    def spy(self, imgs, src, Tk, *a, **kw):
+        solved.append((src.clone(), Tk.clone()))
+        return inner(self, imgs, src, Tk, *a, **kw)
+    monkeypatch.setattr(online.OnlineStitcher, '_render_solved', spy)
+    state, kept, emitted, differs = ops.seam_state(2, hc, wc, 4, dev), None, 0, 0
+    for t in range(9):
+        solved.clear()
+        got = st.push_u8(c['u8'][0, t], c['u8'][1, t])
+        if not got:
+            continue
+        splines, frames_t = (list(solved), range(7)) if len(got) == 7 else ([st._deferred[:2]], [t])
+        assert len(splines) == len(got)
+        for (src, Tk), ft, frame in zip(splines, frames_t, got):
+            imgs = [c['u8'][v, ft] for v in range(2)]
+            want = ops.render_multiband(imgs, src, Tk, hc, wc, 'NORMAL', 3, seam_state=state, **_ops_kw())
+            assert frame.shape == (hc, wc, 3) and frame.dtype == torch.uint8 and torch.equal(frame, want), (t, ft)
+            differs += not torch.equal(frame, ops.render_multiband(imgs, src, Tk, hc, wc, 'NORMAL', 3))
+            emitted += 1
+        if kept is None:
+            kept = st.mode._seam_state[1]
+        assert st.mode._seam_state[1] is kept and st.mode._seam_state[0] == (hc, wc, 2)       # the stream's one state
+    assert emitted == 9 and differs > 0 and st.grow == 'refit' and (st.hc, st.wc) == (hc, wc) and st.mode.seam['seam'] == 'dp'
+    assert torch.equal(kept, state) and int(state[0]) == 1
+
+
+# ================================================================================================ the uint8 and the long routes
+SEAMS = {'geometric': dict(seam='geometric'), 'dp': dict(seam='dp', seam_mu=150)}
+
+
+def _held_to_the_ops_render(dev, video, hc, wc, meshes, seam, prescaled):
+    """video uint8 [12,hc,wc,3] (device tensor or host array) == ops.canvas_to_u8 of ops.render_multiband at bands = 3, frame by frame,
+    on the splines pipeline.render_plan makes of the returned meshes; with the DP seam one ops.seam_state runs through all frames."""
+    from stabstitch2_amd import ops, pipeline
+    c = _clip(dev)
+    views = len(meshes)
+    video = video if torch.is_tensor(video) else T(video).to(dev)
+    assert video.shape == (PUSHES, hc, wc, 3) and video.dtype == torch.uint8
+    phc, pwc, src, Tk = pipeline.render_plan(list(meshes), SH, SW, prescaled=prescaled)
+    assert (phc, pwc) == (hc, wc)
+    kw = dict(SEAMS[seam])
+    if seam == 'dp':
+        kw['seam_state'] = ops.seam_state(views, hc, wc, ops.seam_cell(hc, wc), dev)
+    differs = 0
+    for i in range(PUSHES):
+        imgs = [c['hr'][v, i] for v in range(views)]
+        want = ops.canvas_to_u8(ops.render_multiband(imgs, src[i], Tk[i], hc, wc, 'NORMAL', 3, **kw)[None])[0]
+        assert torch.equal(video[i], want), (seam, 'frame', i)
+        differs += not torch.equal(want, ops.canvas_to_u8(ops.render_multiband(imgs, src[i], Tk[i], hc, wc, 'NORMAL', 3)[None])[0])
+    assert (differs > 0) == (seam == 'dp')                                     # the dp video is not the geometric one
+    assert int(video.max()) > 100
+
+
+@pytest.mark.parametrize('seam', sorted(SEAMS))
+@pytest.mark.parametrize('views', [2, 3])
+def test_the_uint8_routes_render_multiband_with_bands_and_either_seam(dev, hip_nets, views, seam):
+    """pipeline.run_two_view_u8 / run_three_view_u8(fusion_mode='MULTIBAND', bands=3) on the 12-frame clip."""
+    from stabstitch2_amd import pipeline
+    c = _clip(dev)
+    run = pipeline.run_two_view_u8 if views == 2 else pipeline.run_three_view_u8
+    res = run(*[c['u8'][v] for v in range(views)], hip_nets, fusion_mode='MULTIBAND', device=dev, bands=3, **SEAMS[seam])
+    _held_to_the_ops_render(dev, res[0], res[1], res[2], res[3:], seam, prescaled=views == 3)
+
+
+@pytest.mark.parametrize('chunk,chunks', [(5, [(0, 5), (5, 10), (10, 12)]), (9, [(0, 9), (9, 12)])], ids=['chunk5', 'chunk9'])
+@pytest.mark.parametrize('seam', sorted(SEAMS))
+@pytest.mark.parametrize('views', [2, 3])
+def test_the_long_routes_render_multiband_with_bands_and_either_seam(dev, hip_nets, views, seam, chunk, chunks):
+    """pipeline.run_two_view_long / run_three_view_long (LongVideoStitcher) on host copies of the clip: chunks of 5, 5 and 2, and a
+    chunk of 9 that MULTIBAND_FRAMES splits 8 + 1 followed by one of 3; the seam's state runs through the chunks."""
+    from stabstitch2_amd import pipeline
+    c = _clip(dev)
+    assert pipeline.MULTIBAND_FRAMES == 8
+    host = [c['u8'][v].cpu().numpy() for v in range(views)]
+    run = pipeline.run_two_view_long if views == 2 else pipeline.run_three_view_long
+    seen, parts = [], []
+
+    def sink(frames, s, e):
+        seen.append((s, e))
+        parts.append(frames.numpy().copy())
+    res = run(*host, hip_nets, fusion_mode='MULTIBAND', device=dev, chunk=chunk, sink=sink, bands=3, **SEAMS[seam])
+    assert res[0] is None and seen == chunks
+    _held_to_the_ops_render(dev, np.concatenate(parts), res[1], res[2], res[3:], seam, prescaled=views == 3)
+
+
+def test_bands_without_multiband_is_refused_by_every_route(dev, hip_nets):
+    from stabstitch2_amd import pipeline
+    c = _clip(dev)
+    u8 = [c['u8'][v] for v in range(3)]
+    host = [x.cpu().numpy() for x in u8]
+    routes = [lambda **k: pipeline.run_two_view_u8(u8[0], u8[1], hip_nets, device=dev, **k),
+              lambda **k: pipeline.run_three_view_u8(u8[0], u8[1], u8[2], hip_nets, device=dev, **k),
+              lambda **k: pipeline.run_two_view_long(host[0], host[1], hip_nets, device=dev, **k),
+              lambda **k: pipeline.run_three_view_long(host[0], host[1], host[2], hip_nets, device=dev, **k),
+              lambda **k: pipeline.LongVideoStitcher(hip_nets, dev, **k)]
+    for route in routes:
+        with pytest.raises(ValueError, match='bands'):
+            route(fusion_mode='AVERAGE', bands=3)
+        with pytest.raises(ValueError, match='bands'):
+            route(fusion_mode='MULTIBAND', bands=7)
+    assert pipeline.LongVideoStitcher(hip_nets, dev, fusion_mode='MULTIBAND').bands is None      # the default is unchanged

@@ -268,6 +268,23 @@ def test_fp32_program_stays_inside_half_the_bound(size, views):
     assert ((P[:, 4] >= 0.5).sum(0) >= 2).mean() >= 0.1                   # the warped views do overlap
 
 
+@pytest.mark.parametrize('views', [2, 3])
+def test_fp32_program_on_the_small_canvases_stays_under_a_fiftieth_of_the_bound(views):
+    """The inputs of the GPU sweep's small canvases (multiband_ref.SMALL, small_case) at every band count each allows: the bound is not
+    what would let a wrong tap through there.  Observed: at most 0.0175 of the bound.  The inputs are what the sweep says they are:
+    untied weights, and from 2 x 2 upwards a valid and an invalid mask value."""
+    for hc, wc in MR.SMALL:
+        P = MR.small_case(views, hc, wc)
+        valid = P[:, 4] >= 0.5
+        assert len(np.unique(P[:, 3])) == P[:, 3].size and (min(hc, wc) < 2 or (valid.any() and not valid.all())), (hc, wc)
+        for bands in range(MR.max_bands(hc, wc) + 1):
+            err = float(np.abs(MR.blend(P, bands, np.float32).astype(np.float64) - MR.blend(P, bands)).max())
+            assert err <= 0.02 * MR.bound(bands, views), (hc, wc, bands, err)
+        with pytest.raises(ValueError):
+            MR.blend(P, MR.max_bands(hc, wc) + 1)
+    assert [MR.max_bands(*s) for s in MR.SMALL] == [0, 0, 0, 0, 0, 1, 1, 2, 2, 1, 1]
+
+
 # ------------------------------------------------------------------------------------------------ the kernels of the library
 def test_kernels_have_no_scratch_and_no_spills(blend_lib):
     sys.path.insert(0, os.path.join(ROOT, 'tools'))

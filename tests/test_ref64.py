@@ -837,3 +837,46 @@ def test_library_reach_covers_every_kernel_of_the_library():
         return all(k in table and ends_rooted(k, seen + (kernel,)) for k in held_to)
     for kernel in table:
         assert ends_rooted(kernel), kernel
+
+
+def _library_table_against_its_code_objects(lib_path, table):
+    """A per-instantiation reach table (sweep_inputs.blend_reach / seam_reach) against the gfx950 code objects of its library: nothing
+    missing, nothing stale, every cited test defined in a sweep module."""
+    import re
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, os.path.join(os.path.dirname(here), 'tools'))
+    import kernel_resources as KR
+    names = sorted(KR.kernels(lib_path))
+    mangled = [n for n in names if n.startswith('_Z') or '(' not in n]
+    assert not mangled, 'the kernel names came back mangled: template arguments cannot be read, e.g. %s' % mangled[:3]
+    have = {G.instantiation_key(n) for n in names}
+    assert len(have) == len(names), names
+    missing = sorted(have - set(table))
+    assert not missing, 'kernels of %s that its coverage table lacks: %s' % (os.path.basename(lib_path), missing)
+    stale = sorted(set(table) - have)
+    assert not stale, 'the coverage table names kernels that %s does not carry: %s' % (os.path.basename(lib_path), stale)
+    defined = {}
+    for kernel, (kind, tests) in table.items():
+        assert kind in ('fp64', 'exact') and tests, kernel
+        for tid in tests:
+            mod, name = tid.split('::')
+            assert mod in G.SWEEP_MODULES, (kernel, tid)
+            if mod not in defined:
+                defined[mod] = set(re.findall(r'^def (test_\w+)\(', open(os.path.join(here, mod + '.py')).read(), re.M))
+            assert name in defined[mod], 'the coverage table cites %s, which %s.py does not define' % (tid, mod)
+    return have
+
+
+def test_blend_reach_covers_every_kernel_of_the_blend_library():
+    """mb_prepare_kernel<2|3>, mb_reduce_kernel and the twelve mb_collapse_kernel<V, COARSE, OUT> that libstabstitch_blend.so carries."""
+    from stabstitch2_amd import _blend
+    have = _library_table_against_its_code_objects(_blend.LIB_PATH, G.blend_reach())
+    assert len(have) == 15 and sum(k.startswith('mb_collapse_kernel<') for k in have) == 12, sorted(have)
+
+
+def test_seam_reach_covers_every_kernel_of_the_seam_library():
+    """sm_cost_kernel, sm_dp_kernel and sm_paint_kernel of libstabstitch_seam.so, each for two and for three views."""
+    from stabstitch2_amd import _seam
+    have = _library_table_against_its_code_objects(_seam.LIB_PATH, G.seam_reach())
+    assert have == {'%s<%d>' % (k, v) for k in ('sm_cost_kernel', 'sm_dp_kernel', 'sm_paint_kernel') for v in (2, 3)}

@@ -354,3 +354,24 @@ def test_empty_overlap_and_empty_view():
     r = SR.seam(T3, 4, 0, 8.0)
     assert r['order'] == [[0, 2, 1]] and r['seam_cost'] == [[0, 0]]
     assert np.isfinite(MR.blend(r['P'], 2)).all()
+
+
+def test_the_scenes_of_the_gpu_sweep_are_what_they_claim():
+    """The made-up inputs of tests/test_gpu_seam.py's sweep of the indexing, on the restatement alone: the cap scene reaches M's cap
+    (and only in its second frame), and on grids of more than 256 rows of cells an object over the middle third of the rows moves the
+    seam in rows below 256 only, one over the last third in rows past 256 -- where the temporal term then holds the next frame."""
+    P = SR.cap_scene()
+    assert P.shape == (2, 2, 5, 4200, 8) and SR.lds_bytes(4200, 8, 1) == 58928
+    r = SR.seam(P, 1, 65535, 8.0, SR.fresh_state(2, 4200, 8, 1))
+    assert r['order'] == [[0, 1], [0, 1]] and r['seam_cost'] == [[88143], [SR.MCAP]]
+    assert SR.optimum(r['energy'][0][0]) == 88143 and SR.optimum(r['energy'][1][0]) == 1101092922
+    for (hc, wc), cell in (((300, 61), 1), ((530, 37), 2)):
+        lo, hi, rect_x = wc // 4, 3 * wc // 4, (wc // 2 - wc // 8, wc // 2 + wc // 8)
+        A = SR.side_by_side(hc, wc, lo, hi)
+        last = {}
+        for where, rows in (('middle', (hc // 3, 2 * hc // 3)), ('last', (2 * hc // 3, hc))):
+            s = SR.seam(np.stack([A, SR.mismatch(hc, wc, lo, hi, rows + rect_x), A]), cell, 48 * cell, 8.0,
+                        SR.fresh_state(2, hc, wc, cell))['seams'][:, 0]
+            assert s.shape[1] > 256
+            last[where] = (np.flatnonzero(s[0] != s[1]).max(), np.flatnonzero(s[2] != s[0]).max())
+        assert max(last['middle']) < 256 <= min(last['last']), last
