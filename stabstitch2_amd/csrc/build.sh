@@ -3,6 +3,7 @@
 #   stabstitch2_amd/csrc/build.sh           -> stabstitch2_amd/libstabstitch_hip.so         (the product)
 #                                              stabstitch2_amd/libstabstitch_blend.so       (MULTIBAND fusion, blend.hip)
 #                                              stabstitch2_amd/libstabstitch_seam.so        (MULTIBAND's DP seam, seam.hip)
+#                                              stabstitch2_amd/libstabstitch_mbwarp.so      (MULTIBAND's direct warp, mbwarp.hip)
 #   stabstitch2_amd/csrc/build.sh tuning    -> tools/libstabstitch_hip_tuning.so            (-DSS_TUNING: adds the
 #       ss_debug_set / ss_debug_ptr knobs, the per-workgroup s_memtime stamps of tools/diag_*.py and the comparison kernels
 #       that tests and tools/ab_*.py measure the product against; concluded experiments are not kept in it: LAB_NOTES.md,
@@ -32,4 +33,8 @@ if [ "$1" != "tuning" ]; then
     SEAM="$HERE/../libstabstitch_seam.so"
     "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden "$HERE/seam.hip" -o "$SEAM"
     echo "built $SEAM"
+    # the direct warp of MULTIBAND fusion, with exposure gains: a fourth library (include/stabstitch_mbwarp.h), for the same reason
+    MBWARP="$HERE/../libstabstitch_mbwarp.so"
+    "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden "$HERE/mbwarp.hip" -o "$MBWARP"
+    echo "built $MBWARP"
 fi

@@ -1352,6 +1352,37 @@ def multiband_stack(imgs):
     return U
 
 
+def multiband_warp(imgs, source, T, hc, wc, mode='NORMAL', gains=None):
+    """The direct warp of MULTIBAND fusion (libstabstitch_mbwarp.so; DESIGN.md 7g), one launch: imgs as multiband_stack takes them;
+    source [V,63,2] / [n,V,63,2]; T [V,2,66] / [n,V,2,66] -> P [V,5,hc,wc] / [n,V,5,hc,wc], what multiband_seam and multiband_blend
+    read.  Without gains it equals `tps_warp(multiband_stack(imgs), source, T, hc, wc, mode, with_mask=True)` bit for bit, and the
+    stack is never written.  gains [n,V,3] ([V,3] for one frame; exposure_update): planes 0..2 become min(g * s, 255), as in the fused
+    renders; the weight plane and the mask are untouched."""
+    from . import _mbwarp as W
+    v = len(imgs)
+    clip = source.dim() == 4
+    u8 = imgs[0].dtype == torch.uint8
+    imgs = [i if i.dim() == 4 else i[None] for i in imgs]
+    if u8:
+        n, h, w, _ = imgs[0].shape
+        want = (n, h, w, 3)
+    else:
+        n, _, h, w = imgs[0].shape
+        want = (n, 3, h, w)
+    if any(tuple(i.shape) != want or i.dtype != imgs[0].dtype for i in imgs):
+        raise ValueError('the views of one MULTIBAND render must have one shape and type, got %s' % [tuple(i.shape) for i in imgs])
+    if (clip and source.shape[0] != n) or (not clip and n != 1) or source.shape[-3] != v or T.numel() != n * v * 132:
+        raise ValueError('source %s and T %s do not match %d frames of %d views' % (tuple(source.shape), tuple(T.shape), n, v))
+    g = None if gains is None else _gains(gains, n, v)
+    dt = torch.uint8 if u8 else torch.float32
+    if not u8:
+        imgs = [_f(i) for i in imgs]
+    P = torch.empty(((n, v, 5, hc, wc) if clip else (v, 5, hc, wc)), device=imgs[0].device, dtype=torch.float32)
+    W.call('ssw_multiband_warp_u8' if u8 else 'ssw_multiband_warp', H.ptr_array(imgs, dtype=dt), H.dptr(_f(source)), H.dptr(T), g,
+           H.dptr(P), n, v, h, w, hc, wc, MODES[mode], H.stream())
+    return P
+
+
 # ------------------------------------------------------------------ MULTIBAND's content-aware seam (libstabstitch_seam.so; DESIGN.md 7f)
 SEAM_PRIOR = 8.0
 SEAMS = ('geometric', 'dp')
@@ -1446,15 +1477,21 @@ def check_seam(seam, fusion_mode='MULTIBAND'):
 
 
 def render_multiband(imgs, source, T, hc, wc, mode='NORMAL', bands=MULTIBAND_BANDS, out=None, ws=None, u8=None, seam='geometric',
-                     seam_state=None, seam_cell=None, seam_mu=None, seam_prior=None):
+                     seam_state=None, seam_cell=None, seam_mu=None, seam_prior=None, gains=None):
     """MULTIBAND fusion of one frame or of n: imgs as multiband_stack takes them; source [V,63,2] / [n,V,63,2]; T [V,2,66] / [n,V,2,66]
     -> [3,hc,wc] / [n,3,hc,wc] fp32, or the uint8 video frame(s) [hc,wc,3] / [n,hc,wc,3] (u8: default, what the input is).  One warp
     launch of the existing ss_tps_warp_mask_nchw over every (frame, view) and four planes, then multiband_blend: exactly
     `multiband_blend(tps_warp(multiband_stack(imgs), source, T, hc, wc, mode, with_mask=True))`.
     seam='dp': multiband_seam(P, seam_cell, seam_mu, seam_prior, seam_state) between the two (three more launches); 'geometric', the
-    default, is the seam where the warped weight planes cross and launches nothing more."""
+    default, is the seam where the warped weight planes cross and launches nothing more.
+    gains [n,V,3] ([V,3] for one frame; exposure_update): the warp is multiband_warp(gains=) instead -- one launch from the frames, no
+    stack -- so the seam and the blend both see the compensated colours.  Without gains the launches are the ones above."""
     v = len(imgs)
     clip = source.dim() == 4
+    if gains is not None:
+        n = imgs[0].shape[0] if imgs[0].dim() == 4 else 1
+        if tuple(gains.shape) not in ((n, v, 3),) + (((v, 3),) if n == 1 else ()):
+            raise ValueError('gains must be [%d,%d,3], got %s' % (n, v, tuple(gains.shape)))
     if u8 is None:
         u8 = imgs[0].dtype == torch.uint8
     check_bands(bands, hc, wc)
@@ -1464,6 +1501,11 @@ def render_multiband(imgs, source, T, hc, wc, mode='NORMAL', bands=MULTIBAND_BAN
         seam_params(hc, wc, seam_cell, seam_mu, seam_prior)
     elif seam_state is not None or seam_cell is not None or seam_mu is not None or seam_prior is not None:
         raise ValueError("seam_state=, seam_cell=, seam_mu= and seam_prior= belong to seam='dp'")
+    if gains is not None:
+        P = multiband_warp(imgs, source, T, hc, wc, mode, gains=gains)
+        if seam == 'dp':
+            multiband_seam(P, seam_cell, seam_mu, seam_prior, seam_state)
+        return multiband_blend(P, bands, out=out, ws=ws, u8=u8)
     U = multiband_stack(imgs)
     n = U.shape[0] // v
     if (clip and source.shape[0] != n) or (not clip and n != 1) or source.shape[-3] != v:

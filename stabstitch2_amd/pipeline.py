@@ -490,11 +490,12 @@ LINEAR_CLIP = os.environ.get('SS_LINEAR_CLIP', '1') == '1'
 LINEAR_CLIP_FRAMES = int(os.environ.get('SS_LINEAR_CLIP_FRAMES', '64'))     # frames per launch group (workspace: 44 MB per 720p frame and view)
 
 
-def _linear_clip(clips, src, T, hc, wc, warp_mode, out):
+def _linear_clip(clips, src, T, hc, wc, warp_mode, out, gains=None):
     n = src.shape[0]
     for s in range(0, n, LINEAR_CLIP_FRAMES):
         e = min(s + LINEAR_CLIP_FRAMES, n)
-        ops.render_linear_clip([c[s:e] for c in clips], src[s:e], T[s:e], hc, wc, warp_mode, out=out[s:e])
+        ops.render_linear_clip([c[s:e] for c in clips], src[s:e], T[s:e], hc, wc, warp_mode, out=out[s:e],
+                               gains=None if gains is None else gains[s:e])
     return out
 
 
@@ -520,10 +521,24 @@ def seam_options(fusion_mode, seam=None, seam_cell=None, seam_mu=None, seam_prio
     return dict(seam='dp', seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior)
 
 
-def _multiband_frames(img_lists, src, T, hc, wc, warp_mode, bands, out, dev, seam=None, seam_state=None):
+def exposure_params(exposure, exposure_state=None):
+    """exposure= of the offline routes -> None | ops.ExposureParams (True: the defaults), as the streaming stitcher reads it.
+    ValueError for anything else, and for an exposure_state= without exposure=."""
+    if exposure is None or exposure is False:
+        if exposure_state is not None:
+            raise ValueError('exposure_state= belongs to exposure=')
+        return None
+    if exposure is True:
+        return ops.ExposureParams()
+    if not isinstance(exposure, ops.ExposureParams):
+        raise ValueError('exposure must be None, True or an ops.ExposureParams, got %r' % (exposure,))
+    return exposure
+
+
+def _multiband_frames(img_lists, src, T, hc, wc, warp_mode, bands, out, dev, seam=None, seam_state=None, gains=None):
     """Clips held as tensors go in chunks of MULTIBAND_FRAMES frames (the launches of one frame each), lists frame by frame.
     seam: seam_options(); with the DP seam one state (seam_state, or a fresh one) is carried from chunk to chunk, so that a clip equals
-    its frames rendered one by one."""
+    its frames rendered one by one.  gains [n,V,3] (clips only: _exposed_frames takes lists itself): ops.render_multiband's."""
     n = src.shape[0]
     seam = dict(seam or {})
     if seam:
@@ -533,17 +548,62 @@ def _multiband_frames(img_lists, src, T, hc, wc, warp_mode, bands, out, dev, sea
     if all(c is not None for c in clips):
         for s in range(0, n, MULTIBAND_FRAMES):
             e = min(s + MULTIBAND_FRAMES, n)
-            ops.render_multiband([c[s:e] for c in clips], src[s:e], T[s:e], hc, wc, warp_mode, bands, out=out[s:e], **seam)
+            more = {} if gains is None else {'gains': gains[s:e]}
+            ops.render_multiband([c[s:e] for c in clips], src[s:e], T[s:e], hc, wc, warp_mode, bands, out=out[s:e], **seam, **more)
         return out
+    assert gains is None
     for i in range(n):
         ops.render_multiband([x[i].to(dev, non_blocking=True) for x in img_lists], src[i], T[i], hc, wc, warp_mode, bands, out=out[i],
                              u8=False, **seam)
     return out
 
 
+def _exposed_frames(img_lists, src, T, img_h, img_w, hc, wc, warp_mode, fusion_mode, bands, out, dev, seam, seam_state, params, state):
+    """render_frames with exposure compensation: the clip's footprints (the estimator's sample lattice, whatever the fusion mode and
+    SKIP_OUTSIDE -- tile skipping stays SKIP_OUTSIDE's), the gains of ops.exposure_update on the frames the render reads with ONE
+    state run through the clip in order (`state`, or a fresh one), then the render each case has with gains=.  Clips held as tensors:
+    one update for all n frames; lists: one per frame with that frame's footprint row (bit-identical either way)."""
+    n, v = src.shape[0], len(img_lists)
+    fp = ops.render_footprints(src, T, img_h, img_w, hc, wc)
+    st = ops.exposure_state(dev) if state is None else state
+    fused = ops.fused_render(fusion_mode)
+    skip = fp if (SKIP_OUTSIDE and fused) else None
+    clips = [_as_clip(x, n) for x in img_lists]
+    if all(c is not None for c in clips):
+        gains = ops.exposure_update(clips, fp, hc, wc, st, params, warp_mode)
+        if fused:
+            ops.render_average_clip(clips, src, T, hc, wc, warp_mode, out=out, footprint=skip, gains=gains, fusion=fusion_mode)
+        elif fusion_mode == 'MULTIBAND':
+            _multiband_frames(clips, src, T, hc, wc, warp_mode, bands, out, dev, seam, seam_state, gains=gains)
+        elif LINEAR_CLIP:
+            _linear_clip(clips, src, T, hc, wc, warp_mode, out, gains=gains)
+        else:                                # the per-frame chain has no gains: the ragged-canvas render at n = 1, as the stitcher does
+            for i in range(n):
+                ops.render_linear_frames([c[i:i + 1] for c in clips], src[i:i + 1], T[i:i + 1], [(hc, wc)], warp_mode, outs=[out[i]],
+                                         gains=gains[i:i + 1])
+        return out
+    seam = dict(seam or {})
+    if seam:
+        seam['seam_cell'] = ops.seam_cell(hc, wc, seam['seam_cell'])
+        seam['seam_state'] = ops.seam_state(v, hc, wc, seam['seam_cell'], dev) if seam_state is None else seam_state
+    for i in range(n):
+        imgs = [ops._f(img_lists[k][i].to(dev, non_blocking=True)) for k in range(v)]
+        imgs = [t if t.dim() == 4 else t[None] for t in imgs]
+        gains = ops.exposure_update(imgs, fp[i], hc, wc, st, params, warp_mode)
+        if fused:
+            ops.render_average(imgs, src[i], T[i], hc, wc, warp_mode, out=out[i], footprint=None if skip is None else skip[i],
+                               gains=gains, fusion=fusion_mode)
+        elif fusion_mode == 'MULTIBAND':
+            ops.render_multiband(imgs, src[i], T[i], hc, wc, warp_mode, bands, out=out[i], u8=False, gains=gains, **seam)
+        else:
+            ops.render_linear_frames(imgs, src[i:i + 1], T[i:i + 1], [(hc, wc)], warp_mode, outs=[out[i]], gains=gains)
+    return out
+
+
 @torch.no_grad()
 def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, prescaled=False, bbox=None,
-                  size=None, bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, seam_state=None):
+                  size=None, bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, seam_state=None, exposure=None,
+                  exposure_state=None):
     """img_lists: V lists (or tensors [N,3,H,W]) of HR frames (0..255); meshes: V tensors [1,N,7,9,2].
     -> (frames [N,3,Hc,Wc] device tensor, Hc, Wc).  AVERAGE and FEATHER fusion of clips held as tensors is ONE launch for the whole
     clip (ops.render_average_clip); lists of separate frames and LINEAR fusion go frame by frame.
@@ -552,11 +612,16 @@ def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', 
     MULTIBAND fusion (bands= pyramid levels, default ops.MULTIBAND_BANDS): one warp launch and the pyramid launches per chunk of
     MULTIBAND_FRAMES frames of a clip, or per frame of a list (ops.render_multiband).  seam='dp' (MULTIBAND only; seam_cell=, seam_mu=,
     seam_prior=: ops.multiband_seam) puts the content-aware seam between the warp and the blend; its temporal state runs through the
-    whole clip (seam_state: an ops.seam_state to continue from and leave behind, for a video rendered in several calls)."""
+    whole clip (seam_state: an ops.seam_state to continue from and leave behind, for a video rendered in several calls).
+    exposure (None | True | ops.ExposureParams): exposure compensation in every fusion mode -- per frame, view and channel the gains of
+    ops.exposure_update on the clip's footprints, smoothed through the clip in order, scale the sampled colours (min(g * s, 255)); for
+    MULTIBAND in the warp, in front of the seam and the blend.  exposure_state: an ops.exposure_state to continue from and leave
+    advanced (a video rendered in several calls); without it every call starts fresh."""
     check_fusion(fusion_mode, bands)
     seam = seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)
     if seam_state is not None and not seam:
         raise ValueError("seam_state= belongs to seam='dp'")
+    exposure = exposure_params(exposure, exposure_state)
     v = len(img_lists)
     dev = meshes[0].device
     n = meshes[0].shape[1]
@@ -565,6 +630,10 @@ def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', 
     hc, wc, src, T = render_plan(meshes, img_h, img_w, prescaled, bbox, size)
     if out is None or tuple(out.shape) != (n, 3, hc, wc) or not out.is_contiguous():
         out = torch.empty((n, 3, hc, wc), device=dev, dtype=torch.float32)      # (a buffer of another canvas is not reused)
+    if exposure is not None:
+        _exposed_frames(img_lists, src, T, img_h, img_w, hc, wc, warp_mode, fusion_mode, ops.MULTIBAND_BANDS if bands is None else bands,
+                        out, dev, seam, seam_state, exposure, exposure_state)
+        return out, hc, wc
     if fusion_mode == 'MULTIBAND':
         _multiband_frames(img_lists, src, T, hc, wc, warp_mode, ops.MULTIBAND_BANDS if bands is None else bands, out, dev, seam,
                           seam_state)
@@ -603,18 +672,19 @@ def get_stable_sqe(img1_list, img2_list, smooth_mesh1, smooth_mesh2, warp_mode, 
 
 @torch.no_grad()
 def run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', to_host=False, out=None, deterministic=False,
-                 bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None):
+                 bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, exposure=None):
     """-> (frames, Hc, Wc, smooth_mesh1, smooth_mesh2); frames = device tensor [N,3,Hc,Wc]
     (or list of HWC ndarrays with to_host=True).  out: the frames tensor of a previous call to render into; it is reused
     when the canvas still has that size (same-size clips of one stream), else a new one is allocated.
     deterministic: the conv engine's geometry-only kernel policy (ops.deterministic): a frame's bits do not depend on how many
     frames share its launches -- resident clip == chunked passes == stream.
-    seam, seam_cell, seam_mu, seam_prior: MULTIBAND's seam (render_frames)."""
+    seam, seam_cell, seam_mu, seam_prior: MULTIBAND's seam (render_frames); exposure: exposure compensation (render_frames)."""
     seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)      # (refused before the networks run)
+    exposure = exposure_params(exposure)
     with ops.deterministic(deterministic):
         acc = estimate_meshes(nets, lr1, lr2)
     frames, hc, wc = render_frames([hr1, hr2], [acc['smooth_mesh1'], acc['smooth_mesh2']], warp_mode, fusion_mode, out=out, bands=bands,
-                                   seam=seam, seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior)
+                                   seam=seam, seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior, exposure=exposure)
     if to_host:
         host = frames.permute(0, 2, 3, 1).cpu().numpy()
         frames = [host[i] for i in range(host.shape[0])]
@@ -642,16 +712,19 @@ def three_view_compose(w12_m1, w12_m2, w23_m1, w23_m2, img_h, img_w, first_canva
 
 
 @torch.no_grad()
-def three_view_render(img1, img2, img3, mesh1, middle, mesh3, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, bands=None, **seam):
-    """Meshes are HR-scale canvas pixels here (output of three_view_compose).  seam: render_frames' seam= keywords."""
+def three_view_render(img1, img2, img3, mesh1, middle, mesh3, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, bands=None,
+                      exposure=None, exposure_state=None, **seam):
+    """Meshes are HR-scale canvas pixels here (output of three_view_compose).  seam: render_frames' seam= keywords; exposure,
+    exposure_state: render_frames'."""
     return render_frames([img1, img2, img3], [mesh1, middle, mesh3], warp_mode, fusion_mode, out=out, prescaled=True, bands=bands,
-                         **seam)
+                         exposure=exposure, exposure_state=exposure_state, **seam)
 
 
 @torch.no_grad()
 def run_three_view(hr1, hr2, hr3, lr1, lr2, lr3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, deterministic=False,
-                   bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None):
+                   bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, exposure=None):
     seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)
+    exposure = exposure_params(exposure)     # (refused before the networks run)
     # the middle view's TemporalNet motions and SpatialNet trunk features are computed once and reused by pair (2,3)
     with ops.deterministic(deterministic):
         a12 = estimate_meshes(nets, lr1, lr2, keep_spatial_cache2=True)
@@ -660,7 +733,7 @@ def run_three_view(hr1, hr2, hr3, lr1, lr2, lr3, nets, warp_mode='NORMAL', fusio
     m1, mid, m3 = three_view_compose(a12['smooth_mesh1'], a12['smooth_mesh2'], a23['smooth_mesh1'],
                                      a23['smooth_mesh2'], img_h, img_w)
     frames, hc, wc = three_view_render(hr1, hr2, hr3, m1, mid, m3, warp_mode, fusion_mode, out=out, bands=bands, seam=seam,
-                                       seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior)
+                                       seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior, exposure=exposure)
     return frames, hc, wc, m1, mid, m3
 
 
@@ -697,10 +770,12 @@ def _u8_fused(fusion_mode):
 
 @torch.no_grad()
 def render_frames_u8(frame_lists, meshes, warp_mode='NORMAL', out=None, bbox=None, size=None, prescaled=False,
-                     fusion_mode='AVERAGE'):
+                     fusion_mode='AVERAGE', exposure=None, exposure_state=None):
     """frame_lists: V device tensors [N,H,W,3] uint8; meshes: V tensors [1,N,7,9,2] -> (uint8 [N,Hc,Wc,3], Hc, Wc):
     `render_frames(..., fusion_mode)` followed by `to_video_frames`, fused: one launch for the clip (AVERAGE, FEATHER), three / four
-    (LINEAR: the warped planes are fp32 either way, the blend writes the video frame)."""
+    (LINEAR: the warped planes are fp32 either way, the blend writes the video frame).  exposure, exposure_state: as render_frames
+    takes them -- the gains of ops.exposure_update on the uint8 frames, into the renders' _gains entries."""
+    exposure = exposure_params(exposure, exposure_state)
     n = meshes[0].shape[1]
     img_h, img_w = frame_lists[0].shape[1], frame_lists[0].shape[2]
     hc, wc, src, T = render_plan(meshes, img_h, img_w, prescaled, bbox=bbox, size=size)
@@ -708,6 +783,17 @@ def render_frames_u8(frame_lists, meshes, warp_mode='NORMAL', out=None, bbox=Non
         out = out((n, hc, wc, 3))
     if out is None or tuple(out.shape) != (n, hc, wc, 3) or not out.is_contiguous():
         out = torch.empty((n, hc, wc, 3), device=meshes[0].device, dtype=torch.uint8)
+    if exposure is not None:
+        clips = [f if f.is_contiguous() else f.contiguous() for f in frame_lists]
+        fp = ops.render_footprints(src, T, img_h, img_w, hc, wc)
+        st = ops.exposure_state(meshes[0].device) if exposure_state is None else exposure_state
+        gains = ops.exposure_update(clips, fp, hc, wc, st, exposure, warp_mode)
+        if fusion_mode == 'LINEAR':
+            _linear_clip(clips, src, T, hc, wc, warp_mode, out, gains=gains)
+        else:
+            ops.render_average_clip_u8(clips, src, T, hc, wc, warp_mode, out=out, footprint=fp if SKIP_OUTSIDE else None, gains=gains,
+                                       fusion=fusion_mode)
+        return out, hc, wc
     if fusion_mode == 'LINEAR':
         _linear_clip([f if f.is_contiguous() else f.contiguous() for f in frame_lists], src, T, hc, wc, warp_mode, out)
         return out, hc, wc
@@ -724,31 +810,34 @@ def _as_device_u8(frames, device):
 
 
 @torch.no_grad()
-def run_two_view_u8(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False, bands=None, **seam):
+def run_two_view_u8(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False, bands=None,
+                    exposure=None, **seam):
     """uint8 in, uint8 out: ingest -> estimate -> render -> video frames.  -> (uint8 [N,Hc,Wc,3], Hc, Wc, m1, m2).
-    bands: MULTIBAND's pyramid levels (render_frames; None: ops.MULTIBAND_BANDS)."""
+    bands: MULTIBAND's pyramid levels (render_frames; None: ops.MULTIBAND_BANDS); exposure: exposure compensation (render_frames)."""
     check_fusion(fusion_mode, bands)
     seam_options(fusion_mode, **seam)        # (MULTIBAND's seam= keywords: render_frames)
+    exposure = exposure_params(exposure)     # (refused before the networks run)
     if _u8_fused(fusion_mode):
         f1, f2 = _as_device_u8(frames1, device), _as_device_u8(frames2, device)
         _, lr1 = ops.ingest_u8(f1, want_hr=False)
         _, lr2 = ops.ingest_u8(f2, want_hr=False)
         acc = estimate_meshes(nets, lr1, lr2)
         m1, m2 = acc['smooth_mesh1'], acc['smooth_mesh2']
-        u8, hc, wc = render_frames_u8([f1, f2], [m1, m2], warp_mode, fusion_mode=fusion_mode)
+        u8, hc, wc = render_frames_u8([f1, f2], [m1, m2], warp_mode, fusion_mode=fusion_mode, exposure=exposure)
         return (u8.cpu().numpy() if to_host else u8), hc, wc, m1, m2
     hr1, lr1 = load_frames_u8(frames1, device=device)
     hr2, lr2 = load_frames_u8(frames2, device=device)
-    frames, hc, wc, m1, m2 = run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode, fusion_mode, bands=bands, **seam)
+    frames, hc, wc, m1, m2 = run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode, fusion_mode, bands=bands, exposure=exposure, **seam)
     return to_video_frames(frames, to_host), hc, wc, m1, m2
 
 
 @torch.no_grad()
 def run_three_view_u8(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False, bands=None,
-                      **seam):
+                      exposure=None, **seam):
     """`run_three_view` from decoded uint8 frames [N,H,W,3] to uint8 video frames (device-resident clip); bands: as run_two_view_u8.
     -> (uint8 [N,Hc,Wc,3], Hc, Wc, mesh1, middle, mesh3)."""
     check_fusion(fusion_mode, bands)
+    exposure = exposure_params(exposure)     # (refused before the networks run)
     f = [_as_device_u8(x, device) for x in (frames1, frames2, frames3)]
     img_h, img_w = f[0].shape[1], f[0].shape[2]
     seam_options(fusion_mode, **seam)        # (MULTIBAND's seam= keywords: render_frames)
@@ -757,11 +846,11 @@ def run_three_view_u8(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusio
         a12 = estimate_meshes(nets, lr[0], lr[1], keep_spatial_cache2=True)
         a23 = estimate_meshes(nets, lr[1], lr[2], tmotion1=a12['tmotion2'], spatial_cache1=a12.get('spatial_cache2'))
         ms = three_view_compose(a12['smooth_mesh1'], a12['smooth_mesh2'], a23['smooth_mesh1'], a23['smooth_mesh2'], img_h, img_w)
-        u8, hc, wc = render_frames_u8(f, list(ms), warp_mode, prescaled=True, fusion_mode=fusion_mode)
+        u8, hc, wc = render_frames_u8(f, list(ms), warp_mode, prescaled=True, fusion_mode=fusion_mode, exposure=exposure)
         return (u8.cpu().numpy() if to_host else u8), hc, wc, ms[0], ms[1], ms[2]
     io = [ops.ingest_u8(x) for x in f]
     frames, hc, wc, m1, mid, m3 = run_three_view(io[0][0], io[1][0], io[2][0], io[0][1], io[1][1], io[2][1], nets, warp_mode,
-                                                 fusion_mode, bands=bands, **seam)
+                                                 fusion_mode, bands=bands, exposure=exposure, **seam)
     return to_video_frames(frames, to_host), hc, wc, m1, mid, m3
 
 
