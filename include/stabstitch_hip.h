@@ -55,7 +55,7 @@ SS_API int ss_version(void);
 SS_API const char* ss_error_string(int code);
 
 /* ---- layout plumbing (replaces the implicit NCHW tensors of the reference modules) ---------- */
-/* [n][c][h][w] -> [n][h][w][c_pad], channels c..c_pad-1 written as 0 */
+/* [n][c][h][w] -> [n][h][w][c_pad], channels c..c_pad-1 written as 0; ONE image holds at most 2^31 - 1 pixels (SS_ERR_ARG beyond) */
 SS_API int ss_nchw_to_nhwc(const float* in, float* out, int n, int c, int h, int w, int c_pad, void* stream);
 /* [n][h][w][c_stride] (first c channels) -> [n][c][h][w] */
 SS_API int ss_nhwc_to_nchw(const float* in, float* out, int n, int c, int h, int w, int c_stride, void* stream);
@@ -278,7 +278,8 @@ SS_API int ss_tsmotion_lag(const float* smotion, const float* tmotion, float* sm
 
 /* ---- K12/K13: dense TPS warp and fusion (utils/torch_tps_transform.py:108-165,
  *      test_online_tra.py:34-58, 138-150) ----------------------------------------------------- */
-/* generic: U [b][c][h][w] NCHW, source [b][63][2], T [b][2][66] -> out [b][c][hc][wc] */
+/* generic: U [b][c][h][w] NCHW, source [b][63][2], T [b][2][66] -> out [b][c][hc][wc]; b <= 65535 and hc <= 524280 (items and row
+ * tiles ride in the grid: SS_ERR_ARG beyond, here and in the _mask form); the buffers are addressed with 64 bits */
 SS_API int ss_tps_warp_nchw(const float* U, const float* source, const float* T, float* out, int b, int c, int h,
                      int w, int hc, int wc, int mode, void* stream);
 /* same, plus one extra output channel = warp of an all-ones plane (the validity mask of
@@ -624,7 +625,10 @@ SS_API int ss_mask_union(const float* a, const float* b, float* out, long long n
  * equal sizes copied.  Parity of this entry point is UNPINNED against cv2 itself (absent from the image); see
  * oracle/frame_io.py.
  * ss_canvas_to_u8 replaces `stable_list[k].astype(np.uint8)` (:413): [n][3][h][w] fp32 -> uint8 [n][h][w][3]
- * (truncation toward zero, low 8 bits of the int32 value outside 0..255). */
+ * (truncation toward zero, low 8 bits of the int32 value outside 0..255).
+ * Both address n * h * w with 64 bits, so a call's buffers may pass 2^31 elements.  SS_ERR_ARG, before any launch: ONE frame of more
+ * than 2^31 - 1 pixels (h * w); with lr, n > 65535 or lr_h > 262140 (frames and rows ride in the grid); n * h * w / 256 >= 2^31 - 1
+ * (/ 1024 for hr where w % 4 == 0 and the pointers are aligned). */
 SS_API int ss_ingest_u8(const unsigned char* frames, float* hr, float* lr, int n, int h, int w, int lr_h, int lr_w,
                  void* stream);
 SS_API int ss_canvas_to_u8(const float* canvas, unsigned char* out, int n, int h, int w, void* stream);
@@ -651,7 +655,7 @@ SS_API int ss_bgr_to_nv12(const unsigned char* bgr, unsigned char* y, unsigned c
  * w1, w2: [frames][4][h][w] = 3 colour planes (0..255) + validity-mask plane, as ss_tps_warp_mask_nchw
  * writes them.  out (device, fp64) [frames][2] = alignment PSNR (dB), SSIM of (w1*ov, w2*ov), ov = m1*m2,
  * computed in fp64 with scikit-image 0.15 compare_psnr / compare_ssim semantics (data_range 255, 7x7
- * uniform window, multichannel).  ws: 2*frames doubles. */
+ * uniform window, multichannel).  ws: 2*frames doubles.  frames <= 65535, h <= 262140 (SS_ERR_ARG beyond); 64-bit addressing. */
 SS_API int ss_alignment_psnr_ssim(const float* w1, const float* w2, double* out, double* ws, int frames, int h,
                            int w, void* stream);
 /* path [t][63][2] (stitched smooth path of view 2) -> out[0] = stability score (test_metric_ssd.py:459-468) */

@@ -1045,6 +1045,7 @@ __global__ void nhwc_to_nchw_kernel(const float* __restrict__ in, float* __restr
 
 extern "C" int ss_nchw_to_nhwc(const float* in, float* out, int n, int c, int h, int w, int c_pad, void* stream) {
     if (!in || !out || n <= 0 || c <= 0 || h <= 0 || w <= 0 || c_pad < c) return SS_ERR_ARG;
+    if ((long long)h * w > 0x7fffffffLL) return SS_ERR_ARG;       // the pixels of ONE image are an int in the kernels
     long long total = (long long)n * h * w * c_pad;
     if (c_pad == 4 && (((uintptr_t)out) & 15) == 0) {
         long long pixels = (long long)n * h * w;

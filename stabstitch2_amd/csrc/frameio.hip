@@ -107,6 +107,8 @@ extern "C" int ss_ingest_u8(const unsigned char* frames, float* hr, float* lr, i
                             void* stream) {
     if (!frames || (!hr && !lr) || n < 0 || h < 1 || w < 1) return SS_ERR_ARG;
     if (lr && (lr_h < 1 || lr_w < 1)) return SS_ERR_ARG;
+    if ((long long)h * w > 0x7fffffffLL) return SS_ERR_ARG;       // the pixels of ONE frame are an int in the plane kernels
+    if (lr && (n > 65535 || ss_cdiv(lr_h, 4) > 65535)) return SS_ERR_ARG;      // the resize rides frames in grid.z, rows in grid.y: refused before hr is launched
     if (n == 0) return SS_OK;
     hipStream_t st = (hipStream_t)stream;
     long long pixels = (long long)n * h * w;
@@ -123,7 +125,6 @@ extern "C" int ss_ingest_u8(const unsigned char* frames, float* hr, float* lr, i
         }
     }
     if (lr) {
-        if (n > 65535) return SS_ERR_ARG;
         dim3 grid(ss_cdiv(lr_w, 64), ss_cdiv(lr_h, 4), n);
         double scale_x = 1.0 / ((double)lr_w / (double)w), scale_y = 1.0 / ((double)lr_h / (double)h);
         if (lr_w == w && lr_h == h)
@@ -266,6 +267,7 @@ __global__ __launch_bounds__(256) void canvas_u8x1_kernel(const float* __restric
 
 extern "C" int ss_canvas_to_u8(const float* canvas, unsigned char* out, int n, int h, int w, void* stream) {
     if (!canvas || !out || n < 0 || h < 1 || w < 1) return SS_ERR_ARG;
+    if ((long long)h * w > 0x7fffffffLL) return SS_ERR_ARG;       // the pixels of ONE frame are an int in the kernels
     if (n == 0) return SS_OK;
     hipStream_t st = (hipStream_t)stream;
     long long pixels = (long long)n * h * w;

@@ -78,7 +78,7 @@ __global__ void psnr_ssim_finish_kernel(const double* __restrict__ acc, double* 
 
 extern "C" int ss_alignment_psnr_ssim(const float* w1, const float* w2, double* out, double* ws, int frames, int h,
                                       int w, void* stream) {
-    if (!w1 || !w2 || !out || !ws || frames <= 0 || h < 7 || w < 7) return SS_ERR_ARG;
+    if (!w1 || !w2 || !out || !ws || frames <= 0 || frames > 65535 || h < 7 || w < 7 || ss_cdiv(h, 4) > 65535) return SS_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(ws, 0, sizeof(double) * 2 * frames, st) != hipSuccess) return SS_ERR_LAUNCH;
     hipLaunchKernelGGL(psnr_ssim_kernel, dim3(ss_cdiv(w, 64), ss_cdiv(h, 4), frames), dim3(256), 0, st, w1, w2, ws, h, w);

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void tps_warp_kernel(const float* __restrict__
 static int launch_warp(const float* U, const float* source, const float* T, float* out, int b, int c, int h, int w,
                        int hc, int wc, int mode, int append_mask, void* stream) {
     if (!U || !source || !T || !out || b <= 0 || c <= 0 || h <= 1 || w <= 1 || hc <= 1 || wc <= 1 ||
-        (mode != SS_WARP_NORMAL && mode != SS_WARP_FAST))
+        (mode != SS_WARP_NORMAL && mode != SS_WARP_FAST) || b > 65535 || ss_cdiv(hc, 8) > 65535)      // (items and row tiles: grid.z, grid.y)
         return SS_ERR_ARG;
     dim3 g(ss_cdiv(wc, 64), ss_cdiv(hc, 8), b);
     hipLaunchKernelGGL(tps_warp_kernel, g, dim3(256), 0, (hipStream_t)stream, U, source, T, out, c, h, w, hc, wc, mode,
