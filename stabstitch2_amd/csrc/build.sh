@@ -4,6 +4,7 @@
 #                                              stabstitch2_amd/libstabstitch_blend.so       (MULTIBAND fusion, blend.hip)
 #                                              stabstitch2_amd/libstabstitch_seam.so        (MULTIBAND's DP seam, seam.hip)
 #                                              stabstitch2_amd/libstabstitch_mbwarp.so      (MULTIBAND's direct warp, mbwarp.hip)
+#                                              stabstitch2_amd/libstabstitch_surfaces.so    (NV12 surfaces -> BGR frames, surfaces.hip)
 #   stabstitch2_amd/csrc/build.sh tuning    -> tools/libstabstitch_hip_tuning.so            (-DSS_TUNING: adds the
 #       ss_debug_set / ss_debug_ptr knobs, the per-workgroup s_memtime stamps of tools/diag_*.py and the comparison kernels
 #       that tests and tools/ab_*.py measure the product against; concluded experiments are not kept in it: LAB_NOTES.md,
@@ -37,4 +38,8 @@ if [ "$1" != "tuning" ]; then
     MBWARP="$HERE/../libstabstitch_mbwarp.so"
     "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden "$HERE/mbwarp.hip" -o "$MBWARP"
     echo "built $MBWARP"
+    # NV12 surfaces to packed BGR frames, a list of surfaces per launch: a fifth library (include/stabstitch_surfaces.h), for the same reason
+    SURFACES="$HERE/../libstabstitch_surfaces.so"
+    "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden "$HERE/surfaces.hip" -o "$SURFACES"
+    echo "built $SURFACES"
 fi

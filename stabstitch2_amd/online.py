@@ -154,6 +154,60 @@ def _check_nv12(st, frames, out):
                          'fixed size (this stitcher: viewport=%r)' % (st.viewport,))
 
 
+def _even_viewport(st, what):
+    if st.viewport is None or st.viewport[0] % 2 or st.viewport[1] % 2:
+        raise ValueError("%s needs a stitcher built with an even viewport=(Hout, Wout): an NV12 frame has an even, fixed size "
+                         '(this stitcher: viewport=%r)' % (what, st.viewport))
+
+
+def _check_many_nv12(st, views, out, what, count=None):
+    """The arguments of push_many_nv12 (count=None: 1..BATCH_MAX surfaces per view) and of MultiOnlineStitcher.push_nv12 (count = S):
+    every view a tensor [k,H*3/2,W] or a list of k NV12 surfaces of the stitcher's H x W, and the output format; shapes only, run
+    before any state changes -> the views' surface lists."""
+    if out not in ('bgr', 'nv12'):
+        raise ValueError("%s: out must be 'bgr' or 'nv12', got %r" % (what, out))
+    if st.meshes_only or getattr(st, 'chain', False):
+        raise ValueError('%s renders frames: not for meshes_only stitchers' % what)
+    if st.h % 2 or st.w % 2:
+        raise ValueError('NV12 frames have an even height and width: not for a %d x %d stitcher' % (st.h, st.w))
+    surfs = []
+    for v in views:
+        if torch.is_tensor(v) and v.dim() != 3:
+            raise ValueError('%s takes every view as an NV12 tensor [k,%d,%d] or a list of k NV12 surfaces, got a tensor %s'
+                             % (what, st.h // 2 * 3, st.w, tuple(v.shape)))
+        s, h, w, _ = ops.nv12_surfaces(v)
+        if (h, w) != (st.h, st.w):
+            raise ValueError('%s takes NV12 surfaces [%d,%d] = [H*3/2, W] of this stitcher, got [%d,%d]'
+                             % (what, st.h // 2 * 3, st.w, h // 2 * 3, w))
+        surfs.append(s)
+    k = len(surfs[0])
+    if any(len(s) != k for s in surfs):
+        raise ValueError('%s: the NV12 views differ in length: %s' % (what, [len(s) for s in surfs]))
+    if count is not None and k != count:
+        raise ValueError('%s takes %d NV12 surfaces per view (one per stream), got %d' % (what, count, k))
+    if count is None and not 1 <= k <= BATCH_MAX:
+        raise ValueError('%s takes 1 to %d frames of every view per call, got %d' % (what, BATCH_MAX, k))
+    if out == 'nv12':
+        _even_viewport(st, "%s(out='nv12')" % what)
+    return surfs
+
+
+def _stacked(frames):
+    """uint8 frames of one size as ONE tensor [n,...]: the frames themselves where they already lie back to back in one allocation (the
+    frames of a batched render), else a copy."""
+    f0, step = frames[0], frames[0].numel()
+    base = f0.untyped_storage().data_ptr()
+    if all(f.shape == f0.shape and f.is_contiguous() and f.untyped_storage().data_ptr() == base
+           and f.data_ptr() == f0.data_ptr() + i * step for i, f in enumerate(frames)):
+        return f0.as_strided((len(frames),) + tuple(f0.shape), (step,) + tuple(f0.stride()))
+    return torch.stack(list(frames))
+
+
+def _frames_to_nv12(frames):
+    """uint8 video frames of one size -> their NV12 frames, views of one tensor [n,Hc*3/2,Wc]: one ops.bgr_to_nv12 launch."""
+    return list(ops.bgr_to_nv12(_stacked(frames)).unbind(0)) if frames else []
+
+
 def _exposure_params(exposure, meshes_only=False):
     """OnlineStitcher's exposure= -> None | ops.ExposureParams (True: the defaults)."""
     if exposure is None or exposure is False:
@@ -893,6 +947,17 @@ class _Stitcher:
                 out += self._push_batch(k - i, None, tuple(f[i:] for f in frames))
             return out
 
+    def _push_many_nv12(self, views, out):
+        """push_many_nv12 of V views: every view's k decoded NV12 surfaces -> packed BGR in ONE converter launch for all V k of them
+        (ops.nv12_to_bgr), then _push_many_u8; out='nv12': one ops.bgr_to_nv12 over the call's frames behind it."""
+        surfs = _check_many_nv12(self, views, out, 'push_many_nv12')
+        if not L.QUAD:
+            raise ValueError('push_many needs the shared regressor launches (SS_QUAD_REGRESSOR=1)')
+        k = len(surfs[0])
+        bgr = ops.nv12_to_bgr([s for view in surfs for s in view])
+        frames = self._push_many_u8(tuple(bgr[v * k:(v + 1) * k] for v in range(len(surfs))))
+        return _frames_to_nv12(frames) if out == 'nv12' else frames
+
     def _check_many(self, frames):
         """push_many's refusals that do not depend on the frame type -> k."""
         if self.meshes_only:
@@ -1214,6 +1279,16 @@ class OnlineStitcher(_Stitcher):
         what k calls of `push_u8` return, joined (see push_many)."""
         return self._push_many_u8((frames1, frames2))
 
+    @torch.no_grad()
+    def push_many_nv12(self, frames1, frames2, out='bgr'):
+        """k DECODED frame pairs as a hardware decoder delivers them, 1 <= k <= BATCH_MAX: every view an NV12 device tensor
+        [k,H*3/2,W] (any row and frame stride) or a list of k surfaces [H*3/2,W], each with its own pitch -- a decoder's surface pool
+        -> the stitched video frames with push_many_u8's cadence: out='bgr' uint8 [Hc,Wc,3], byte for byte push_many_u8 of the frames
+        converted to packed BGR; out='nv12' uint8 [Hc*3/2,Wc], byte for byte ops.bgr_to_nv12 of those, views of one
+        tensor (an even viewport=, as push_nv12).  All 2 k surfaces are converted in ONE launch, the rest is push_many_u8: every
+        fusion mode, seam=, viewport=, every grow and exposure= work as they do there.  Interleaves freely with the other entries."""
+        return self._push_many_nv12((frames1, frames2), out)
+
     def _batch_buffers(self, k):
         d, e = self.dev, 126
         fh, fw = pipeline.LR_H // 8, pipeline.LR_W // 8
@@ -1492,6 +1567,9 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
     def push_nv12(self, *frames, **kw):
         raise ValueError('PipelinedOnlineStitcher has no push_nv12: use OnlineStitcher.push_nv12')
 
+    def push_many_nv12(self, *frames, **kw):
+        raise ValueError('PipelinedOnlineStitcher has no push_many_nv12: use OnlineStitcher.push_many_nv12')
+
     def _pipe_alloc(self):
         d = self.dev
         two = lambda *shape: [torch.empty(shape, device=d) for _ in range(2)]
@@ -1762,6 +1840,18 @@ class MultiOnlineStitcher(_Stitcher):
             return [[ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in per] for per in outs]
 
     @torch.no_grad()
+    def push_nv12(self, frames1, frames2, out='bgr'):
+        """One DECODED frame pair of every stream as NV12 surfaces: each view a device tensor [S,H*3/2,W] or a list of S surfaces
+        [H*3/2,W], each with its own pitch -> S lists of stitched video frames, uint8 [Hc,Wc,3] (out='bgr'), byte for byte push_u8 of
+        the converted frames, or NV12 [Hc*3/2,Wc] (out='nv12', even viewport), byte for byte ops.bgr_to_nv12 of those.  The 2 S
+        surfaces are converted in one launch (ops.nv12_to_bgr), then push_u8 runs."""
+        S = self.S
+        surfs = _check_many_nv12(self, (frames1, frames2), out, 'push_nv12', count=S)
+        bgr = ops.nv12_to_bgr(surfs[0] + surfs[1])
+        outs = self.push_u8(bgr[:S], bgr[S:])
+        return [_frames_to_nv12(per) for per in outs] if out == 'nv12' else outs
+
+    @torch.no_grad()
     def push(self, hr1, hr2, lr1, lr2):
         """One frame pair of every stream: hr* [S,3,H,W] (0..255), lr* [S,3,360,480] ([-1,1]), device tensors.
         -> S lists of newly stitched frames (empty for the first 6 pushes, 7 frames each on the 7th, then one per push)."""
@@ -1809,6 +1899,9 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
                                      grow=grow, meshes_only=False, deterministic=deterministic, viewport=viewport,
                                      zoom_limit=zoom_limit)
         self._pipe_init()
+
+    def push_nv12(self, *frames, **kw):
+        raise ValueError('PipelinedMultiOnlineStitcher has no push_nv12: use MultiOnlineStitcher.push_nv12')
 
     def _pipe_alloc(self):
         d, S = self.dev, self.S
@@ -2033,6 +2126,13 @@ class ThreeViewOnlineStitcher(_Stitcher):
         byte what k calls of `push_u8` return, joined (see push_many)."""
         return self._push_many_u8((frames1, frames2, frames3))
 
+    @torch.no_grad()
+    def push_many_nv12(self, frames1, frames2, frames3, out='bgr'):
+        """k DECODED frame triples as NV12 surfaces ([k,H*3/2,W] tensors or lists of k surfaces) -> stitched video frames, uint8
+        [Hc,Wc,3] (out='bgr') or NV12 [Hc*3/2,Wc] (out='nv12', even viewport): the 3 k surfaces converted in one launch, then
+        push_many_u8 (see OnlineStitcher.push_many_nv12)."""
+        return self._push_many_nv12((frames1, frames2, frames3), out)
+
     def _batch_buffers(self, k):
         d, e, S = self.dev, 126, 2
         fh, fw = pipeline.LR_H // 8, pipeline.LR_W // 8
@@ -2119,6 +2219,9 @@ class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
     def push_nv12(self, *frames, **kw):
         raise ValueError('PipelinedThreeViewOnlineStitcher has no push_nv12: use ThreeViewOnlineStitcher.push_nv12')
 
+    def push_many_nv12(self, *frames, **kw):
+        raise ValueError('PipelinedThreeViewOnlineStitcher has no push_many_nv12: use ThreeViewOnlineStitcher.push_many_nv12')
+
     def _pipe_alloc(self):
         d = self.dev
         two = lambda *shape: [torch.empty(shape, device=d) for _ in range(2)]
@@ -2170,37 +2273,93 @@ class HostFrameStream:
     `tools/diag_host_stream2.py`) -- the host waits for push t - 1's end event while push t is already queued, and a staging slot is reused
     only when its last reader is known to have ended.  Frames come out in order, `depth` frames late at most; a yielded tensor stays
     valid until `depth` more frames have been yielded.  Pinned (page-locked) input frames upload asynchronously; pageable ones (numpy
-    arrays) work and stall the loop for their copy."""
+    arrays) work and stall the loop for their copy.
 
-    def __init__(self, stitcher, depth=4, prefetch=2, streams=None):
+    frame_format='nv12': the source yields decoded NV12 frames uint8 [H*3/2,W] ([S,H*3/2,W] for S streams), half the bytes of packed
+    BGR over the link.  They are uploaded as they are and converted on the device -- all views of a push in one launch
+    (ops.nv12_to_bgr) on the compute stream -- in front of `push_u8` / `push_many_u8`: one route for every stitcher class, the
+    pipelined ones included, and byte for byte the frames of a `push_nv12` loop.  out='nv12': ops.bgr_to_nv12 on the compute stream in
+    front of the download, the pinned results are [Hc*3/2,Wc]; the stitcher needs an even viewport= (checked here).
+    batch=k, 1 < k <= BATCH_MAX: consecutive items of the source are grouped k at a time (the last group may be shorter), each
+    group uploaded into one staging slot [k,...] per view and pushed with `push_many_u8`; frames are still yielded one
+    by one, in order.  Not for stitchers without push_many_u8 (Pipelined*, Multi*).  A group that completes the first window hands out
+    up to k + 6 frames at once; the pinned ring holds 2 depth + batch + 8 frames (2 depth + 9 at batch 1), which keeps the promise
+    above for such a burst: when a download overwrites the slot of frame i, at most `depth` frames wait undelivered, so frame
+    i + depth + 1 has been yielded."""
+
+    def __init__(self, stitcher, depth=4, prefetch=2, streams=None, batch=1, frame_format='bgr', out='bgr'):
+        if frame_format not in ('bgr', 'nv12'):
+            raise ValueError("HostFrameStream: frame_format must be 'bgr' or 'nv12', got %r" % (frame_format,))
+        if out not in ('bgr', 'nv12'):
+            raise ValueError("HostFrameStream: out must be 'bgr' or 'nv12', got %r" % (out,))
+        if isinstance(batch, bool) or not isinstance(batch, int) or not 1 <= batch <= BATCH_MAX:
+            raise ValueError('HostFrameStream: batch must be an int in 1..%d, got %r' % (BATCH_MAX, batch))
+        if batch > 1 and (isinstance(stitcher, _TwoInFlight) or not hasattr(stitcher, 'push_many_u8')):
+            raise ValueError('HostFrameStream(batch=%d) pushes with push_many_u8, which %s does not have: use batch=1'
+                             % (batch, type(stitcher).__name__))
+        if frame_format == 'nv12' and (stitcher.h % 2 or stitcher.w % 2):
+            raise ValueError('NV12 frames have an even height and width: not for a %d x %d stitcher' % (stitcher.h, stitcher.w))
+        if out == 'nv12':
+            _even_viewport(stitcher, "HostFrameStream(out='nv12')")
         self.st, self.dev = stitcher, stitcher.dev
         self.depth, self.prefetch = int(depth), max(1, int(prefetch))
+        self.batch, self.frame_format, self.out = batch, frame_format, out
         self.up, self.comp, self.down = streams if streams is not None else pipeline.io_streams(self.dev)
-        self._in, self._free, self._k = None, None, 0          # ring of prefetch + 3 uploaded pairs and the end events of their readers
-        self._host, self._hk = None, 0                          # ring of 2 depth + 9 pinned result frames (7 arrive at once)
+        self._in, self._free, self._k = None, None, 0          # ring of prefetch + 3 uploaded groups and the end events of their readers
+        self._host, self._hk = None, 0                          # ring of 2 depth + batch + 8 pinned result frames (batch + 6 arrive at once)
 
-    def _stage(self, frames):
-        src = [torch.from_numpy(f) if not torch.is_tensor(f) else f for f in frames]
+    def _stage(self, group):
+        """Upload one group of the source's items (batch=1: one item, into slots of the item's own shape; else up to `batch` items
+        into slots [batch,...] per view) -> (slot, items in it, the upload's end event)."""
         st = self.st
-        _check_shapes('uint8 frames', src, (((st.S,) if hasattr(st, 'S') else ()) + (st.h, st.w, 3),))   # before the upload
+        lead = (st.S,) if hasattr(st, 'S') else ()
+        shape = lead + ((st.h // 2 * 3, st.w) if self.frame_format == 'nv12' else (st.h, st.w, 3))
+        items = []
+        for frames in group:
+            src = [torch.from_numpy(f) if not torch.is_tensor(f) else f for f in frames]
+            _check_shapes('uint8 NV12 frames' if self.frame_format == 'nv12' else 'uint8 frames', src, (shape,))   # before the upload
+            if self.frame_format == 'nv12' and any(t.dtype != torch.uint8 for t in src):
+                raise ValueError('NV12 frames are uint8, got %s' % [str(t.dtype) for t in src])
+            items.append(src)
+        views = len(items[0])
+        if any(len(src) != views for src in items):
+            raise ValueError('the items of the source differ in their number of views: %s' % [len(src) for src in items])
+        slot = shape if self.batch == 1 else (self.batch,) + shape
         n = self.prefetch + 3
-        if self._in is None or tuple(self._in[0][0].shape) != tuple(src[0].shape) or len(self._in[0]) != len(src):
+        if self._in is None or tuple(self._in[0][0].shape) != slot or len(self._in[0]) != views:
             torch.cuda.synchronize(self.dev)
-            self._in = [[torch.empty(tuple(t.shape), dtype=torch.uint8, device=self.dev) for t in src] for _ in range(n)]
+            self._in = [[torch.empty(slot, dtype=torch.uint8, device=self.dev) for _ in range(views)] for _ in range(n)]
             self._free = [None] * n
         j = self._k % n
         self._k += 1
         if self._free[j] is not None:
             self._free[j].synchronize()          # host-side: the push that read this slot ended long ago (returns at once)
         with torch.cuda.stream(self.up):
-            for dst, t in zip(self._in[j], src):
-                dst.copy_(t, non_blocking=True)
+            for i, src in enumerate(items):
+                for dst, t in zip(self._in[j], src):
+                    (dst if self.batch == 1 else dst[i]).copy_(t, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self.up)
-        return j, ev
+        return j, len(items), ev
+
+    def _push(self, j, m):
+        """The push of staging slot j (m items) on the current stream -> its frames in the output format, a flat list."""
+        frames = self._in[j] if self.batch == 1 else [f[:m] for f in self._in[j]]
+        if self.frame_format == 'nv12':
+            # all views' surfaces in one converter launch: [V * n, H, W, 3], view-major
+            surfs = [s for f in frames for s in (f.unbind(0) if f.dim() == 3 else (f,))]
+            bgr = ops.nv12_to_bgr(surfs)
+            n = len(surfs) // len(frames)
+            frames = [bgr[v * n:(v + 1) * n] if self._in[j][0].dim() == 3 else bgr[v] for v in range(len(frames))]
+        outs = self.st.push_u8(*frames) if self.batch == 1 else self.st.push_many_u8(*frames)
+        return self._format(outs)
+
+    def _format(self, outs):
+        outs = list(_tensors_of(outs))
+        return _frames_to_nv12(outs) if self.out == 'nv12' else outs
 
     def _host_slot(self, shape):
-        n = 2 * self.depth + 9
+        n = 2 * self.depth + self.batch + 8
         if self._host is None or tuple(self._host[0].shape) != tuple(shape):
             torch.cuda.synchronize(self.dev)
             self._host = [torch.empty(tuple(shape), dtype=torch.uint8).pin_memory() for _ in range(n)]
@@ -2226,7 +2385,9 @@ class HostFrameStream:
     @torch.no_grad()
     def run(self, source):
         from collections import deque
-        it = iter(source)
+        import itertools
+        items = iter(source)
+        it = iter(lambda: tuple(itertools.islice(items, self.batch)), ())      # the source's items, `batch` at a time
         staged, results = deque(), deque()
         prev = None                                          # the previous push: (end event, frames still on the device)
         for _ in range(self.prefetch):
@@ -2234,13 +2395,13 @@ class HostFrameStream:
             if nxt is not None:
                 staged.append(self._stage(nxt))
         while staged:
-            j, ev = staged.popleft()
+            j, m, ev = staged.popleft()
             nxt = next(it, None)
             if nxt is not None:
-                staged.append(self._stage(nxt))              # a later pair's upload is enqueued before this pair's launches
+                staged.append(self._stage(nxt))              # a later group's upload is enqueued before this group's launches
             with torch.cuda.stream(self.comp):
                 self.comp.wait_event(ev)
-                outs = self.st.push_u8(*self._in[j])
+                outs = self._push(j, m)
                 done = torch.cuda.Event()
                 done.record(self.comp)
             self._free[j] = done
@@ -2255,7 +2416,7 @@ class HostFrameStream:
             self._download(prev, results)
         if hasattr(self.st, 'flush_u8'):                     # a pipelined stitcher still holds its last push's frame
             with torch.cuda.stream(self.comp):
-                outs = self.st.flush_u8()
+                outs = self._format(self.st.flush_u8())
                 done = torch.cuda.Event()
                 done.record(self.comp)
             self._download((done, outs), results)

@@ -1122,6 +1122,58 @@ def bgr_to_nv12(bgr, out=None):
     return out[0] if single else out
 
 
+def nv12_surfaces(frames):
+    """The surfaces of an NV12 argument: a tensor [n,H*3/2,W] (any row stride >= W, any frame stride), one frame [H*3/2,W], or a list of
+    such 2-D tensors, each with its own pitch -> (list of 2-D surfaces, H, W, is it the single frame?).  Shapes, dtypes and strides
+    only: no device is looked at.  What is no NV12 surface -- and an odd pitch, which the converter refuses -- is a ValueError."""
+    single = torch.is_tensor(frames) and frames.dim() == 2
+    if torch.is_tensor(frames):
+        surf = [frames] if single else (list(frames.unbind(0)) if frames.dim() == 3 else [])
+    else:
+        surf = list(frames)
+    s0 = surf[0] if surf and torch.is_tensor(surf[0]) else None
+    if s0 is None or any(not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 2 or f.shape != s0.shape or f.shape[0] % 3
+                         or f.shape[0] == 0 or f.shape[1] == 0 or f.shape[1] % 2 or f.stride(1) != 1 or f.stride(0) < f.shape[1]
+                         or f.stride(0) % 2 or f.device != s0.device for f in surf):
+        raise ValueError('NV12 frames are uint8 tensors [n,H*3/2,W], one frame [H*3/2,W] or a list of such frames on one GPU: even H and '
+                         'W, dense columns, an even row stride >= W; got %s'
+                         % ([(str(f.dtype), tuple(f.shape), tuple(f.stride())) if torch.is_tensor(f) else type(f).__name__ for f in surf]
+                            if surf else (tuple(frames.shape) if torch.is_tensor(frames) else 'an empty list'),))
+    return surf, s0.shape[0] // 3 * 2, s0.shape[1], single
+
+
+def nv12_to_bgr(frames, out=None):
+    """Decoded NV12 surfaces -> the uint8 video frames [n,H,W,3] in B,G,R order ([H,W,3] for the single frame), byte for byte
+    tests/nv12_ref.py's nv12_to_bgr.  frames: a device tensor [n,H*3/2,W] (any row stride >= W, any frame stride), one frame
+    [H*3/2,W], or a list of such 2-D tensors each with its own pitch -- a decoder's surface pool; the UV plane of a surface is its rows
+    H.. .  ONE launch for up to 96 surfaces (libstabstitch_surfaces.so), more go in chunks.  out: [n,H,W,3] uint8 to write, its frames
+    dense, its frame stride free."""
+    from . import _surfaces as F
+    surf, h, w, single = nv12_surfaces(frames)
+    n, dev = len(surf), surf[0].device
+    if not surf[0].is_cuda:
+        raise H.HipError('stabstitch2_amd kernels need device tensors (got %s); there is no CPU path' % dev)
+    if out is None:
+        out = torch.empty((n, h, w, 3), device=dev, dtype=torch.uint8)
+    else:
+        if single and out.dim() == 3:
+            out = out[None]
+        if out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3) or out.device != dev or not out[0].is_contiguous() \
+                or (n > 1 and out.stride(0) < 3 * h * w):
+            raise ValueError('nv12_to_bgr: out must be uint8 [%d,%d,%d,3] with dense frames on %s, got %s %s strides %s'
+                             % (n, h, w, dev, out.dtype, tuple(out.shape), tuple(out.stride())))
+    stride = out.stride(0) if n > 1 else 3 * h * w
+    for c in range(0, n, F.MAX_SURFACES):
+        part = surf[c:c + F.MAX_SURFACES]
+        m = len(part)
+        ys = (ctypes.c_void_p * m)(*[f.data_ptr() for f in part])
+        uvs = (ctypes.c_void_p * m)(*[f.data_ptr() + h * f.stride(0) for f in part])
+        ys.dev = dev.index
+        F.call('ssf_nv12_to_bgr', ys, uvs, (ctypes.c_int * m)(*[f.stride(0) for f in part]), m, h, w, _nv12_ptr(out[c]), stride,
+               H.stream())
+    return out[0] if single else out
+
+
 def render_average_nv12(frames, source, T, hc, wc, mode='NORMAL', out=None, footprint=None, out_format='bgr', fusion='AVERAGE'):
     """render_average_u8 from decoded NV12 frames: frames = list of 2|3 NV12 device tensors [H*3/2,W]; out_format 'bgr' -> the uint8
     video frame [hc,wc,3] (byte for byte render_average_u8 of the converted frames), 'nv12' -> that frame as NV12 [hc*3/2,wc]

@@ -34,19 +34,19 @@ runner = HostFrameStream(st, depth=args.depth, prefetch=args.prefetch)
 if args.no_up:          # experiment: the frames are uploaded once, later stages reuse the slots
     real_stage = runner._stage
     cache = {}
-    def stage(frames):
+    def stage(group):
         if len(cache) < args.prefetch + 2:
-            j, ev = real_stage(frames)
+            j, m, ev = real_stage(group)
             cache[j] = ev
-            return j, ev
+            return j, m, ev
         j = runner._k % (args.prefetch + 2)
         runner._k += 1
-        return j, cache[j]
+        return j, len(group), cache[j]
     runner._stage = stage
 if args.no_down:        # experiment: results stay on the device
     import types
     def run(self, source):
-        it = iter(source)
+        it = ((item,) for item in source)                # groups of one: batch = 1
         from collections import deque
         staged = deque()
         for _ in range(self.prefetch):
@@ -54,13 +54,13 @@ if args.no_down:        # experiment: results stay on the device
             if nxt is not None:
                 staged.append(self._stage(nxt))
         while staged:
-            j, ev = staged.popleft()
+            j, m, ev = staged.popleft()
             nxt = next(it, None)
             if nxt is not None:
                 staged.append(self._stage(nxt))
             with torch.cuda.stream(self.comp):
                 self.comp.wait_event(ev)
-                outs = self.st.push_u8(*self._in[j])
+                outs = self._push(j, m)
                 done = torch.cuda.Event()
                 done.record(self.comp)
             self._free[j] = done

@@ -23,11 +23,11 @@ K = 300
 t_all = pc()
 k = 0
 for _ in range(r.prefetch):
-    a = pc(); staged.append(r._stage(tuple(hp[v][k % n] for v in range(2)))); T['stage'] += pc() - a; k += 1
+    a = pc(); staged.append(r._stage((tuple(hp[v][k % n] for v in range(2)),))); T['stage'] += pc() - a; k += 1
 while staged:
-    j, ev = staged.popleft()
+    j, _, ev = staged.popleft()
     if k < K:
-        a = pc(); staged.append(r._stage(tuple(hp[v][k % n] for v in range(2)))); T['stage'] += pc() - a; k += 1
+        a = pc(); staged.append(r._stage((tuple(hp[v][k % n] for v in range(2)),))); T['stage'] += pc() - a; k += 1
     a = pc()
     with torch.cuda.stream(r.comp):
         r.comp.wait_event(ev)
