@@ -9,7 +9,16 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+
+# The native libraries, in the order they were added: the names of their binding modules in this package.  Each module describes its
+# library with LIB_PATH, HEADER (under include/), API (the macro in front of a declaration), PREFIX (of every exported symbol) and
+# SIGNATURES, and has lib() and call().  The build, its surface check and the tests go over this list ("Adding a native
+# library").
+LIBRARIES = ('_hip', '_blend', '_seam', '_mbwarp', '_surfaces')
+
 LIB_PATH = os.path.join(_HERE, 'libstabstitch_hip.so')
+HEADER, API, PREFIX = 'stabstitch_hip.h', 'SS_API', 'ss_'
+ERR_ARG = -1                  # SS?_ERR_ARG of every side library's header: `check_side` makes it a ValueError
 
 c_fp = ctypes.c_void_p        # device pointer
 c_i = ctypes.c_int
@@ -147,21 +156,25 @@ SIGNATURES = {
 _lib = None
 
 
+def load(path, signatures):
+    """ctypes handle of the library at `path` with the restype / argtypes of `signatures` set; raises if it has not been built."""
+    if not os.path.exists(path):
+        raise ImportError(
+            'stabstitch2_amd: %s not found. Build it with `python -c "import __graft_entry__ as g; g.build()"` '
+            'or stabstitch2_amd/csrc/build.sh (hipcc --offload-arch=gfx950). There is no CPU fallback.' % path)
+    handle = ctypes.CDLL(path)
+    for name, (res, args) in signatures.items():
+        fn = getattr(handle, name)
+        fn.restype = res
+        fn.argtypes = args
+    return handle
+
+
 def lib():
     """The loaded library (loads on first use; raises if it has not been built)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(
-                'stabstitch2_amd: %s not found. Build it with `python -c "import __graft_entry__ as g; g.build()"` '
-                'or stabstitch2_amd/csrc/build.sh (hipcc --offload-arch=gfx950). There is no CPU fallback.'
-                % LIB_PATH)
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = handle
+        _lib = load(LIB_PATH, SIGNATURES)
     return _lib
 
 
@@ -170,8 +183,19 @@ class HipError(RuntimeError):
 
 
 def check(code, what):
+    """The main library's return codes: anything but 0 is a HipError with the library's own text."""
     if code != 0:
         err = HipError('%s failed: %s (%d)' % (what, lib().ss_error_string(code).decode(), code))
+        err.code = code
+        raise err
+
+
+def check_side(code, what):
+    """The side libraries' return codes: an argument the library refuses is a ValueError, a failed launch a HipError."""
+    if code == ERR_ARG:
+        raise ValueError('%s refused its arguments' % what)
+    if code != 0:
+        err = HipError('%s failed: launch error (%d)' % (what, code))
         err.code = code
         raise err
 
@@ -218,10 +242,11 @@ def ptr_array(tensors, dtype=torch.float32):
     return arr
 
 
-def call(name, *args):
-    """Launch on the GPU that owns the pointer arguments, on THAT device's current stream (not the current device's):
-    nets moved to cuda:1 keep working while cuda:0 is current, and launches stay ordered with the torch ops that
-    produced their inputs."""
+def launch(lib, name, args, host_ok=False):
+    """The one launch path of the five libraries -> the entry point's return code.  `lib`: the binding module's `lib`.  Launches on
+    the GPU that owns the pointer arguments, on THAT device's current stream (not the current device's): nets moved to cuda:1 keep
+    working while cuda:0 is current, and launches stay ordered with the torch ops that produced their inputs.  A call without device
+    pointers (workspace queries, version) is an error unless `host_ok`."""
     dev = None
     for a in args:
         d = getattr(a, 'dev', None)
@@ -230,12 +255,21 @@ def call(name, *args):
                 dev = d
             elif d != dev:
                 raise HipError('%s: tensors of one launch live on different GPUs (cuda:%d and cuda:%d)' % (name, dev, d))
+    if dev is None:
+        if host_ok:
+            return getattr(lib(), name)(*args)
+        raise HipError('%s needs device tensors; there is no CPU path' % name)
     fn = getattr(lib(), name)
-    if dev is None:                          # no device pointers (workspace queries, version)
-        return check(fn(*args), name)
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     args = tuple(st if a is _STREAM else a for a in args)
     if dev == torch.cuda.current_device():
-        return check(fn(*args), name)
+        return fn(*args)
     with torch.cuda.device(dev):
-        return check(fn(*args), name)
+        return fn(*args)
+
+
+def call(name, *args):
+    """`launch` on the main library; a call without device pointers is allowed."""
+    code = launch(lib, name, args, True)
+    if code != 0:                            # `check`, without a second Python call per launch: a push is ~80 of these, host-bound
+        check(code, name)

@@ -20,26 +20,18 @@ if [ "$1" = "tuning" ]; then
     DEFS="-DSS_TUNING"
 fi
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-"$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden $DEFS \
+FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden"
+"$HIPCC" $FLAGS $DEFS \
     "$HERE/conv.hip" "$HERE/wino.hip" "$HERE/corr.hip" "$HERE/geom.hip" "$HERE/render.hip" "$HERE/smooth.hip" "$HERE/metrics.hip" \
     "$HERE/frameio.hip" "$HERE/stem.hip" "$HERE/wino43.hip" \
     -o "$OUT"
 echo "built $OUT"
 if [ "$1" != "tuning" ]; then
-    # MULTIBAND fusion: a library of its own (include/stabstitch_blend.h), so that the surface of libstabstitch_hip.so stays as it is
-    BLEND="$HERE/../libstabstitch_blend.so"
-    "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden "$HERE/blend.hip" -o "$BLEND"
-    echo "built $BLEND"
-    # the dynamic-programming seam of MULTIBAND fusion: a third library (include/stabstitch_seam.h), for the same reason
-    SEAM="$HERE/../libstabstitch_seam.so"
-    "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden "$HERE/seam.hip" -o "$SEAM"
-    echo "built $SEAM"
-    # the direct warp of MULTIBAND fusion, with exposure gains: a fourth library (include/stabstitch_mbwarp.h), for the same reason
-    MBWARP="$HERE/../libstabstitch_mbwarp.so"
-    "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden "$HERE/mbwarp.hip" -o "$MBWARP"
-    echo "built $MBWARP"
-    # NV12 surfaces to packed BGR frames, a list of surfaces per launch: a fifth library (include/stabstitch_surfaces.h), for the same reason
-    SURFACES="$HERE/../libstabstitch_surfaces.so"
-    "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden "$HERE/surfaces.hip" -o "$SURFACES"
-    echo "built $SURFACES"
+    # every later feature is a library of its own (NAME.hip, include/stabstitch_NAME.h), so that the surface and the machine code of
+    # libstabstitch_hip.so stay as they are
+    for NAME in blend seam mbwarp surfaces; do
+        SIDE="$HERE/../libstabstitch_$NAME.so"
+        "$HIPCC" $FLAGS "$HERE/$NAME.hip" -o "$SIDE"
+        echo "built $SIDE"
+    done
 fi

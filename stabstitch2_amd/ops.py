@@ -10,6 +10,7 @@ import ctypes
 import torch
 
 from . import _hip as H
+from . import _blend as B, _mbwarp as W, _seam as S, _surfaces as F
 
 
 def _f(t):
@@ -1148,7 +1149,6 @@ def nv12_to_bgr(frames, out=None):
     [H*3/2,W], or a list of such 2-D tensors each with its own pitch -- a decoder's surface pool; the UV plane of a surface is its rows
     H.. .  ONE launch for up to 96 surfaces (libstabstitch_surfaces.so), more go in chunks.  out: [n,H,W,3] uint8 to write, its frames
     dense, its frame stride free."""
-    from . import _surfaces as F
     surf, h, w, single = nv12_surfaces(frames)
     n, dev = len(surf), surf[0].device
     if not surf[0].is_cuda:
@@ -1332,7 +1332,6 @@ def multiband_weight_plane(h, w, device):
 
 def check_bands(bands, hc=None, wc=None):
     """ValueError for a band count the blend refuses (on this canvas, when one is given)."""
-    from . import _blend as B
     if not isinstance(bands, int) or isinstance(bands, bool) or not 0 <= bands <= B.MAX_BANDS:
         raise ValueError('bands must be an integer 0..%d, got %r' % (B.MAX_BANDS, bands))
     if hc is not None and B.lib().ssb_multiband_workspace_floats(1, 2, int(hc), int(wc), bands) < 0:
@@ -1343,7 +1342,6 @@ def check_bands(bands, hc=None, wc=None):
 
 def multiband_workspace(frames, views, hc, wc, bands, device):
     """The workspace of multiband_blend for `frames` frames in one call (ssb_multiband_workspace_floats)."""
-    from . import _blend as B
     need = int(B.lib().ssb_multiband_workspace_floats(frames, views, hc, wc, bands))
     if need < 0:
         raise ValueError('multiband_blend: 2|3 views, 0..%d bands, every reduced level at least 3 pixels a side; got %d frames of %d '
@@ -1355,7 +1353,6 @@ def multiband_blend(P, bands=MULTIBAND_BANDS, out=None, ws=None, u8=False):
     """Laplacian-pyramid blend of warped views: P [V,5,hc,wc] (or [n,V,5,hc,wc]: n frames in the launches of one) = per view the warped
     B, G, R, the warped multiband_weight_plane and the ones-mask, as tps_warp(.., with_mask=True) writes them -> [3,hc,wc] fp32
     ([n,3,hc,wc]), or with u8 the video frame [hc,wc,3] uint8 ([n,hc,wc,3]) = canvas_to_u8 of the same values.  2 * bands + 2 launches."""
-    from . import _blend as B
     clip = P.dim() == 5
     if P.dim() not in (4, 5) or P.shape[-3] != 5:
         raise ValueError('P must be [V,5,hc,wc] or [n,V,5,hc,wc], got %s' % (tuple(P.shape),))
@@ -1410,7 +1407,6 @@ def multiband_warp(imgs, source, T, hc, wc, mode='NORMAL', gains=None):
     read.  Without gains it equals `tps_warp(multiband_stack(imgs), source, T, hc, wc, mode, with_mask=True)` bit for bit, and the
     stack is never written.  gains [n,V,3] ([V,3] for one frame; exposure_update): planes 0..2 become min(g * s, 255), as in the fused
     renders; the weight plane and the mask are untouched."""
-    from . import _mbwarp as W
     v = len(imgs)
     clip = source.dim() == 4
     u8 = imgs[0].dtype == torch.uint8
@@ -1443,7 +1439,6 @@ SEAMS = ('geometric', 'dp')
 def seam_cell(hc, wc, cell=None):
     """The cell size of the seam's grid on a hc x wc canvas: `cell` checked (one of 1, 2, 4, 8, 16 whose dynamic program fits the LDS
     of one workgroup), or for None the smallest of 4, 8, 16 that fits.  ValueError names a larger cell where one helps."""
-    from . import _seam as S
     if cell is None:
         for c in (4, 8, 16):
             if S.lds_bytes(hc, wc, c) <= S.LDS_BYTES:
@@ -1461,7 +1456,6 @@ def seam_cell(hc, wc, cell=None):
 
 def seam_params(hc, wc, cell=None, mu=None, prior=None):
     """-> (cell, mu, prior) with the defaults filled in (cell: seam_cell; mu = 48 * cell; prior = SEAM_PRIOR) and checked."""
-    from . import _seam as S
     cell = seam_cell(hc, wc, cell)
     mu = 48 * cell if mu is None else mu
     if isinstance(mu, bool) or not isinstance(mu, int) or not 0 <= mu <= S.MU_MAX:
@@ -1475,7 +1469,6 @@ def seam_params(hc, wc, cell=None, mu=None, prior=None):
 def seam_state(views, hc, wc, cell=None, device='cuda'):
     """The seam state of one stream on one canvas (int32, all zero = fresh): what multiband_seam's temporal term remembers -- the grid,
     the view order and the previous seams.  `state.zero_()` forgets it."""
-    from . import _seam as S
     if views not in (2, 3):
         raise ValueError('the DP seam takes 2 or 3 views, got %r' % (views,))
     hq = S.grid(hc, wc, seam_cell(hc, wc, cell))[0]
@@ -1484,7 +1477,6 @@ def seam_state(views, hc, wc, cell=None, device='cuda'):
 
 def seam_workspace(frames, views, hc, wc, cell, device):
     """The int32 workspace of multiband_seam for `frames` frames in one call (ssm_seam_workspace_bytes; _seam.layout names its parts)."""
-    from . import _seam as S
     need = int(S.lib().ssm_seam_workspace_bytes(frames, views, hc, wc, cell))
     if need < 0:
         raise ValueError('multiband_seam: 1..65535 frames of 2|3 views, a cell of %s whose grid fits the LDS; got %d frames of %d views '
@@ -1498,7 +1490,6 @@ def multiband_seam(P, cell=None, mu=None, prior=None, state=None, ws=None):
     pair of neighbouring views on a grid of cell x cell cells (tests/seam_ref.py is the definition).  mu: the cost of moving the seam
     one cell sideways against the previous frame's (needs `state`, ops.seam_state; the frames of a clip are taken in order); prior: the
     pull towards the geometric seam.  Three launches whatever n is.  -> P."""
-    from . import _seam as S
     clip = P.dim() == 5
     if P.dim() not in (4, 5) or P.shape[-3] != 5:
         raise ValueError('P must be [V,5,hc,wc] or [n,V,5,hc,wc], got %s' % (tuple(P.shape),))

@@ -107,6 +107,35 @@ def test_converter_variants(dev, size):
         _intact(buf, out, ('out_stride gap', gap))
 
 
+def test_a_refused_call_is_a_value_error_and_launches_nothing(dev):
+    """The binding's one path the CPU tests cannot reach (tests/test_native_binding.py has the others): real device pointers and a
+    real stream through _surfaces.call, SSF_ERR_ARG mapped to ValueError with `out` untouched -- then the same call with the right
+    count.  4 x 8 with pitch 16: the smallest geometry ssf_nv12_to_bgr takes on its aligned path."""
+    import ctypes
+    from stabstitch2_amd import _hip, _surfaces, ops
+    h, w = 4, 8
+    nv, ref = _case(dev, 77, 2, h, w, 8)
+    surf = list(nv.unbind(0))
+    assert [s.stride(0) for s in surf] == [16, 16]
+    buf, out = _fenced(dev, 2, h, w)
+    ys = (ctypes.c_void_p * 2)(*[s.data_ptr() for s in surf])
+    uvs = (ctypes.c_void_p * 2)(*[s.data_ptr() + h * s.stride(0) for s in surf])
+    pitches = (ctypes.c_int * 2)(16, 16)
+    ys.dev = nv.device.index
+
+    def convert(n):
+        _surfaces.call('ssf_nv12_to_bgr', ys, uvs, pitches, n, h, w, _hip.dptr(out, dtype=torch.uint8), 3 * h * w, _hip.stream())
+
+    with pytest.raises(ValueError, match='^ssf_nv12_to_bgr refused its arguments$'):
+        convert(0)
+    torch.cuda.synchronize(dev)
+    assert bool((buf == FILL).all())
+    convert(2)
+    _equal(out, ref, 'the same call with n = 2')
+    assert torch.equal(out, ops.nv12_to_bgr(surf))
+    _intact(buf, out, 'n = 2')
+
+
 def _ours(names):
     return [k for k in names if re.search(r'\bsf_[a-z]+_kernel', k)]
 

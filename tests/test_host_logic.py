@@ -14,11 +14,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope='module')
 def built_lib():
+    import abi_surface
     from stabstitch2_amd import _hip
-    if not os.path.exists(_hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _hip.lib()
+    return abi_surface.built(_hip)
 
 
 def test_cabi_exports_exactly_the_declared_symbols(built_lib):

@@ -5,12 +5,12 @@ The kernels themselves: tests/test_gpu_mbwarp.py.
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import pytest
 import torch
 
+import abi_surface as A
 import mbwarp_ref as WR
 import sweep_inputs as G
 
@@ -21,33 +21,21 @@ ERR_ARG = -1
 @pytest.fixture(scope='module')
 def warp_lib():
     from stabstitch2_amd import _mbwarp
-    if not os.path.exists(_mbwarp.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _mbwarp.lib()
+    return A.built(_mbwarp)
 
 
 def test_header_exports_and_ctypes_table_agree(warp_lib):
     from stabstitch2_amd import _mbwarp
-    hdr = open(os.path.join(ROOT, 'include', 'stabstitch_mbwarp.h')).read()
-    declared = sorted(set(re.findall(r'\bSSW_API[^;]*?\b(ssw_[a-z0-9_]+)\s*\(', hdr)))
-    assert declared == sorted(_mbwarp.SIGNATURES) == ['ssw_multiband_warp', 'ssw_multiband_warp_u8', 'ssw_version']
-    nm = subprocess.run(['nm', '-D', '--defined-only', _mbwarp.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    exported = sorted(line.split()[-1] for line in nm.splitlines() if ' T ' in line and not line.split()[-1].startswith('_'))
-    assert exported == declared, exported                              # nothing else leaves the library
-    # every declaration's parameter count is the ctypes table's
-    for name, params in re.findall(r'\bSSW_API[^;]*?\b(ssw_[a-z0-9_]+)\s*\(([^)]*)\)', hdr):
-        count = 0 if params.strip() == 'void' else len(params.split(','))
-        assert count == len(_mbwarp.SIGNATURES[name][1]), name
-    defines = {k: int(v) for k, v in re.findall(r'^#define (SSW_[A-Z_]+) (-?\d+)\b', hdr, re.M)}
+    declared, defines = A.check(_mbwarp)
+    assert declared == ['ssw_multiband_warp', 'ssw_multiband_warp_u8', 'ssw_version']
     assert defines['SSW_ERR_ARG'] == _mbwarp.ERR_ARG == ERR_ARG and defines['SSW_MAX_VIEWS'] == _mbwarp.MAX_VIEWS == 3
     assert defines['SSW_MAX_ITEMS'] == _mbwarp.MAX_ITEMS == 65535
     from stabstitch2_amd import ops
     assert (defines['SSW_WARP_NORMAL'], defines['SSW_WARP_FAST']) == (ops.MODES['NORMAL'], ops.MODES['FAST'])
     assert warp_lib.ssw_version() == 1
-    # the three other libraries do not know of it
-    for other in ('stabstitch_hip.h', 'stabstitch_blend.h', 'stabstitch_seam.h'):
-        assert not re.search(r'ssw_|mbwarp', open(os.path.join(ROOT, 'include', other)).read())
+    # the libraries before it do not know of it: not even the word (its prefix and header: test_native_binding.py, for every library)
+    for other, text in A.headers_before(_mbwarp).items():
+        assert not re.search(r'mbwarp', text), other
 
 
 def test_code_objects_hold_the_reach_table_without_scratch_or_spills(warp_lib):

@@ -6,13 +6,13 @@ import ctypes
 import itertools
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+import abi_surface as A
 import multiband_ref as MR
 import sweep_inputs as G
 from oracle import samplers as S
@@ -26,10 +26,7 @@ EPS64 = 2.0 ** -53
 @pytest.fixture(scope='module')
 def blend_lib():
     from stabstitch2_amd import _blend
-    if not os.path.exists(_blend.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _blend.lib()
+    return A.built(_blend)
 
 
 def warped(size, views, seed=11):
@@ -46,13 +43,8 @@ def bands_of(hc, wc):
 # ------------------------------------------------------------------------------------------------ the surface
 def test_header_exports_and_ctypes_table_agree(blend_lib):
     from stabstitch2_amd import _blend, _hip
-    hdr = open(os.path.join(ROOT, 'include', 'stabstitch_blend.h')).read()
-    declared = sorted(set(re.findall(r'\bSSB_API[^;]*?\b(ssb_[a-z0-9_]+)\s*\(', hdr)))
-    assert declared == sorted(_blend.SIGNATURES) and len(declared) == 4
-    nm = subprocess.run(['nm', '-D', '--defined-only', _blend.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    exported = sorted(line.split()[-1] for line in nm.splitlines() if ' T ' in line and not line.split()[-1].startswith('_'))
-    assert exported == declared, exported                              # nothing else leaves the library
-    defines = {k: int(v) for k, v in re.findall(r'^#define (SSB_[A-Z_]+) (-?\d+)\b', hdr, re.M)}
+    declared, defines = A.check(_blend)
+    assert len(declared) == 4
     assert defines['SSB_ERR_ARG'] == _blend.ERR_ARG == ERR_ARG and defines['SSB_MAX_VIEWS'] == _blend.MAX_VIEWS == 3
     assert defines['SSB_MAX_BANDS'] == _blend.MAX_BANDS == MR.MAX_BANDS == 6
     assert blend_lib.ssb_version() == 1

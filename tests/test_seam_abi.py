@@ -6,12 +6,12 @@ import ctypes
 import itertools
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import abi_surface as A
 import multiband_ref as MR
 import seam_ref as SR
 
@@ -22,29 +22,19 @@ ERR_ARG = -1
 @pytest.fixture(scope='module')
 def seam_lib():
     from stabstitch2_amd import _seam
-    if not os.path.exists(_seam.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _seam.lib()
+    return A.built(_seam)
 
 
 # ------------------------------------------------------------------------------------------------ the surface
 def test_header_exports_and_ctypes_table_agree(seam_lib):
     from stabstitch2_amd import _seam
-    hdr = open(os.path.join(ROOT, 'include', 'stabstitch_seam.h')).read()
-    declared = sorted(set(re.findall(r'\bSSM_API[^;]*?\b(ssm_[a-z0-9_]+)\s*\(', hdr)))
-    assert declared == sorted(_seam.SIGNATURES) == ['ssm_multiband_seam', 'ssm_seam_workspace_bytes', 'ssm_version']
-    nm = subprocess.run(['nm', '-D', '--defined-only', _seam.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    exported = sorted(line.split()[-1] for line in nm.splitlines() if ' T ' in line and not line.split()[-1].startswith('_'))
-    assert exported == declared, exported                              # nothing else leaves the library
-    defines = {k: int(v) for k, v in re.findall(r'^#define (SSM_[A-Z_]+) (-?\d+)\b', hdr, re.M)}
+    declared, defines = A.check(_seam)
+    assert declared == ['ssm_multiband_seam', 'ssm_seam_workspace_bytes', 'ssm_version']
     assert defines['SSM_ERR_ARG'] == _seam.ERR_ARG == ERR_ARG and defines['SSM_MAX_VIEWS'] == _seam.MAX_VIEWS == 3
     assert defines['SSM_MU_MAX'] == _seam.MU_MAX == 65535 and defines['SSM_STATE_HEADER'] == _seam.STATE_HEADER == SR.HEADER
     assert defines['SSM_LDS_BYTES'] == _seam.LDS_BYTES == SR.LDS_BYTES == 160 * 1024 and defines['SSM_TILE_W'] == _seam.TILE_W
     assert seam_lib.ssm_version() == 1
-    # the two other libraries do not know of it
-    for other in ('stabstitch_hip.h', 'stabstitch_blend.h'):
-        assert not re.search(r'ssm_|seam\.h', open(os.path.join(ROOT, 'include', other)).read())
+    # (that the libraries before it do not know of it: test_native_binding.py, for every library)
 
 
 def test_every_refusal_comes_before_a_launch(seam_lib):

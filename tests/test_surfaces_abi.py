@@ -5,12 +5,12 @@ kernels and the routes themselves: tests/test_gpu_surfaces.py.
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import pytest
 import torch
 
+import abi_surface as A
 import sweep_inputs as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,29 +21,16 @@ KERNELS = ['sf_convert_kernel<0>', 'sf_convert_kernel<1>']
 @pytest.fixture(scope='module')
 def surf_lib():
     from stabstitch2_amd import _surfaces
-    if not os.path.exists(_surfaces.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _surfaces.lib()
+    return A.built(_surfaces)
 
 
 def test_header_exports_and_ctypes_table_agree(surf_lib):
     from stabstitch2_amd import _surfaces
-    hdr = open(os.path.join(ROOT, 'include', 'stabstitch_surfaces.h')).read()
-    declared = sorted(set(re.findall(r'\bSSF_API[^;]*?\b(ssf_[a-z0-9_]+)\s*\(', hdr)))
-    assert declared == sorted(_surfaces.SIGNATURES) == ['ssf_nv12_to_bgr', 'ssf_version']
-    nm = subprocess.run(['nm', '-D', '--defined-only', _surfaces.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    exported = sorted(line.split()[-1] for line in nm.splitlines() if ' T ' in line and not line.split()[-1].startswith('_'))
-    assert exported == declared, exported                              # nothing else leaves the library
-    for name, params in re.findall(r'\bSSF_API[^;]*?\b(ssf_[a-z0-9_]+)\s*\(([^)]*)\)', hdr):
-        count = 0 if params.strip() == 'void' else len(params.split(','))
-        assert count == len(_surfaces.SIGNATURES[name][1]), name
-    defines = {k: int(v) for k, v in re.findall(r'^#define (SSF_[A-Z_]+) (-?\d+)\b', hdr, re.M)}
+    declared, defines = A.check(_surfaces)
+    assert declared == ['ssf_nv12_to_bgr', 'ssf_version']
     assert defines['SSF_ERR_ARG'] == _surfaces.ERR_ARG == ERR_ARG and defines['SSF_MAX_SURFACES'] == _surfaces.MAX_SURFACES == 96
     assert surf_lib.ssf_version() == 1
-    # the four other libraries do not know of it
-    for other in ('stabstitch_hip.h', 'stabstitch_blend.h', 'stabstitch_seam.h', 'stabstitch_mbwarp.h'):
-        assert not re.search(r'ssf_', open(os.path.join(ROOT, 'include', other)).read()), other
+    # (that the libraries before it do not know of it: test_native_binding.py, for every library)
     # the kernels use nv12.h's statement and do not restate its constants
     src = open(os.path.join(ROOT, 'stabstitch2_amd', 'csrc', 'surfaces.hip')).read()
     assert '#include "nv12.h"' in src and 'nv12_to_bgr(' in src

@@ -19,11 +19,7 @@ def ensure_built():
 
 def lib():
     from stabstitch2_amd import _hip
-    h = ctypes.CDLL(ensure_built())
-    for name, (res, args) in _hip.SIGNATURES.items():
-        fn = getattr(h, name)
-        fn.restype = res
-        fn.argtypes = args
+    h = _hip.load(ensure_built(), _hip.SIGNATURES)
     h.ss_debug_set.argtypes = [ctypes.c_int, ctypes.c_int]
     h.ss_debug_set.restype = None
     h.ss_debug_ptr.argtypes = [ctypes.c_void_p]

@@ -1,13 +1,12 @@
 """A/B of the cost volume's 16-byte tail reads: tools/lib_old_cv.so (before) vs the product library, alternating.  python tools/ab_cv_tail.py"""
-import sys, os, ctypes, torch
+import sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from stabstitch2_amd import ops, _hip
 dev = torch.device('cuda:0')
 new = _hip.lib()
-old = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib_old_cv.so'))
-for name, (res, args) in _hip.SIGNATURES.items():
-    if hasattr(old, name):
-        fn = getattr(old, name); fn.restype = res; fn.argtypes = args
+# (the entry points this script reaches: an older build need not export the later ones)
+old = _hip.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib_old_cv.so'),
+                {n: _hip.SIGNATURES[n] for n in ('ss_error_string', 'ss_cost_volume', 'ss_cost_volume_bidir')})
 def t(n, r, bidir):
     a = torch.randn(n, 45, 60, 128, device=dev); b = torch.randn(n, 45, 60, 128, device=dev)
     f = (lambda: ops.cost_volume_bidir(a, b, r)) if bidir else (lambda: ops.cost_volume(a, b, r))
