@@ -25,6 +25,10 @@ Once the window is full every push runs the same ~150 small kernels on buffers o
 captured ONCE into a HIP graph (state lives in static tensors: the rings are shifted, not rotated) and each push is
 two input copies + one graph launch: the Python / ctypes launch overhead (~1 ms per pair, more than the kernels'
 own time at batch 1) disappears.  `use_graph=False` runs the same code eagerly.
+
+That step -- from the LR frames to the newest smoothed meshes -- is written once (_PairStep) for S two-view streams: OnlineStitcher
+runs it with S = 1, MultiOnlineStitcher with its S, ThreeViewOnlineStitcher through a chain of two pairs; a class adds only what
+follows the meshes (its render), and the forms with two pushes in flight (_TwoInFlight) cut the same step in two.
 """
 import collections
 import contextlib
@@ -136,22 +140,26 @@ def _check_u8(what, frames, shape):
     _check_shapes('uint8 frames', frames, (shape,))
 
 
+def _check_nv12_stitcher(st, out, what):
+    """What every NV12 entry refuses before it looks at a frame: the output format, a stitcher that renders nothing, odd frame sizes."""
+    if out not in ('bgr', 'nv12'):
+        raise ValueError("%s: out must be 'bgr' or 'nv12', got %r" % (what, out))
+    if st.meshes_only:                   # (chain=True stitchers are meshes_only)
+        raise ValueError('%s renders frames: not for meshes_only stitchers' % what)
+    if st.h % 2 or st.w % 2:
+        raise ValueError('NV12 frames have an even height and width: not for a %d x %d stitcher' % (st.h, st.w))
+
+
 def _check_nv12(st, frames, out):
     """push_nv12's arguments: decoded NV12 frames uint8 [H*3/2, W] of the stitcher's H x W (dense columns, any row stride >= W) and
     the output format; run before any state changes."""
-    if out not in ('bgr', 'nv12'):
-        raise ValueError("push_nv12: out must be 'bgr' or 'nv12', got %r" % (out,))
-    if st.meshes_only:
-        raise ValueError('push_nv12 renders frames: not for meshes_only stitchers')
-    if st.h % 2 or st.w % 2:
-        raise ValueError('NV12 frames have an even height and width: not for a %d x %d stitcher' % (st.h, st.w))
+    _check_nv12_stitcher(st, out, 'push_nv12')
     shape = (st.h // 2 * 3, st.w)
     if any(f.dtype != torch.uint8 or tuple(f.shape) != shape or f.stride(-1) != 1 or f.stride(0) < st.w for f in frames):
         raise ValueError('push_nv12 takes %d uint8 NV12 frames [%d,%d] = [H*3/2, W] with dense columns (a row stride > W is fine), got %s'
                          % (len(frames), shape[0], shape[1], [(str(f.dtype), tuple(f.shape), tuple(f.stride())) for f in frames]))
-    if out == 'nv12' and (st.viewport is None or st.viewport[0] % 2 or st.viewport[1] % 2):
-        raise ValueError("push_nv12(out='nv12') needs a stitcher built with an even viewport=(Hout, Wout): an NV12 frame has an even, "
-                         'fixed size (this stitcher: viewport=%r)' % (st.viewport,))
+    if out == 'nv12':
+        _even_viewport(st, "push_nv12(out='nv12')")
 
 
 def _even_viewport(st, what):
@@ -164,12 +172,7 @@ def _check_many_nv12(st, views, out, what, count=None):
     """The arguments of push_many_nv12 (count=None: 1..BATCH_MAX surfaces per view) and of MultiOnlineStitcher.push_nv12 (count = S):
     every view a tensor [k,H*3/2,W] or a list of k NV12 surfaces of the stitcher's H x W, and the output format; shapes only, run
     before any state changes -> the views' surface lists."""
-    if out not in ('bgr', 'nv12'):
-        raise ValueError("%s: out must be 'bgr' or 'nv12', got %r" % (what, out))
-    if st.meshes_only or getattr(st, 'chain', False):
-        raise ValueError('%s renders frames: not for meshes_only stitchers' % what)
-    if st.h % 2 or st.w % 2:
-        raise ValueError('NV12 frames have an even height and width: not for a %d x %d stitcher' % (st.h, st.w))
+    _check_nv12_stitcher(st, out, what)
     surfs = []
     for v in views:
         if torch.is_tensor(v) and v.dim() != 3:
@@ -201,6 +204,14 @@ def _stacked(frames):
            and f.data_ptr() == f0.data_ptr() + i * step for i, f in enumerate(frames)):
         return f0.as_strided((len(frames),) + tuple(f0.shape), (step,) + tuple(f0.stride()))
     return torch.stack(list(frames))
+
+
+def _to_u8(x):
+    """A push's frames (a list, or a list per stream) as uint8 video frames [Hc,Wc,3]: ops.canvas_to_u8 of each fp32 canvas; frames
+    the render wrote as uint8 stay as they are."""
+    if torch.is_tensor(x):
+        return x if x.dtype == torch.uint8 else ops.canvas_to_u8(x.reshape((1,) + tuple(x.shape[-3:])))[0]
+    return [_to_u8(y) for y in x]
 
 
 def _frames_to_nv12(frames):
@@ -625,12 +636,8 @@ class _MultibandRender(_Render):
 
 
 # ------------------------------------------------------------------ steady state (window full, canvas fixed)
-# State tensors of the steady state (fixed addresses: the step is captured into a HIP graph), with a leading S for S streams:
-#   pair_s [2 views][prev, new][126]   spatial motions of the previous and the current pair
-#   pair_t [2 views][zero, new][126]   temporal motions (slot 0 stays zero: tsmotion of a 2-frame batch reads slot 1 only)
-#   ring   [smesh v0, smesh v1, tsm v0, tsm v1][7][126]     the sliding SmoothNet window
-#   prev_feat [2,45,60,128]            TemporalNet stage-1 features of the previous frame, both views
-# pair_t is rewritten in full by every push; the canvas watcher's rows (ops.canvas_watch) count every run of the step and are state too.
+# The static tensors a steady-state step advances (_PairStep has their layout); the canvas watcher's rows (ops.canvas_watch) count
+# every run of the step and are state too.
 _STATE = ('prev_feat', 'pair_s', 'ring')
 
 
@@ -638,8 +645,9 @@ class _Stitcher:
     """What the three plain stitchers share: their common fields, the canvas watcher, the twin trunk and its weights check, and the
     steady-state push -- poll the watcher (grow='recapture'), recapture after reloaded weights, load the push's inputs, run the step
     eagerly (use_graph=False) or capture it on first use and replay it, copy the watcher rows behind it, hand the frames out (rendered
-    now from the caller's frames with the direct render, else copies of the graph's output).  A subclass provides _load, _step_static
-    and the window-fill push; one with S canvases also _regrown / _render_direct / overflow_report.  How the fusion mode renders, in
+    now from the caller's frames with the direct render, else copies of the graph's output).  _load and _step_static are _PairStep's
+    for the two-view stitchers (ThreeViewOnlineStitcher: its own, around its chains'); a subclass provides the window-fill push and the
+    tail behind the meshes; one with S canvases also _regrown / _render_direct / overflow_report.  How the fusion mode renders, in
     every one of these places, is `self.mode`'s to say (_Render)."""
     _U8_STEADY = True        # push_u8 in the steady state: the resize writes the graph's LR inputs, the render samples the uint8 frames
     _LINEAR_DIRECT = True    # may LINEAR fusion take the direct render (DIRECT_LINEAR)?  Not with two pushes in flight (_TwoInFlight)
@@ -896,6 +904,18 @@ class _Stitcher:
             gains = self._exposure_gains([f.reshape(shp) for f in imgs], left.efp)
         return [self.mode.frame(imgs, left, self.hc, self.wc, u8, gains)]
 
+    def _push_u8(self, imgs):
+        """push_u8 of V views (checked): in the steady state with the direct render the resize writes the graph's LR inputs and the
+        render samples the uint8 frames; every other configuration, and the window fill, goes ingest_u8 -> _push -> canvas_to_u8."""
+        with ops.deterministic(self.deterministic):
+            if self._u8_steady():
+                return self._push_static(u8=tuple(i.contiguous() for i in imgs))
+            if imgs[0].dim() == 4:           # S streams: every view's [S,H,W,3] where it lies, a launch per view
+                hr, lr = zip(*[ops.ingest_u8(i, pipeline.LR_H, pipeline.LR_W) for i in imgs])
+            else:                            # one stream: its V frames [H,W,3] in one launch
+                hr, lr = (t.split(1) for t in ops.ingest_u8(torch.stack(imgs, 0), pipeline.LR_H, pipeline.LR_W))
+            return _to_u8(self._push(*hr, *lr))
+
     def _push_nv12(self, imgs, out):
         """push_nv12 of V views (checked): the steady state with the direct render samples the caller's NV12 frames where the mode
         has an NV12 render; every other configuration, and the window fill, goes ingest_nv12 -> _push -> canvas_to_u8
@@ -909,7 +929,7 @@ class _Stitcher:
             for k, img in enumerate(imgs):
                 ops.ingest_nv12(img, pipeline.LR_H, pipeline.LR_W, hr_out=hr[k:k + 1], lr_out=lr[k:k + 1])
             frames = self._push(*([hr[k:k + 1] for k in range(v)] + [lr[k:k + 1] for k in range(v)]))
-            frames = [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
+            frames = _to_u8(frames)
             return [ops.bgr_to_nv12(f) for f in frames] if out == 'nv12' else frames
 
     # ------------------------------------------------------------------ k frames of every view per call (one canvas)
@@ -1021,7 +1041,97 @@ class _Stitcher:
         return list(self.mode.batch(views, left, self.hc, self.wc, u8, gains).unbind(0))
 
 
-class OnlineStitcher(_Stitcher):
+class _PairStep:
+    """Mixin: the steady-state step of S two-view streams advancing together, from their LR frames to their newest smoothed meshes --
+    THE place where a streaming push advances its state.  OnlineStitcher runs it with S = 1, MultiOnlineStitcher with its S (chain:
+    the S pairs are the neighbours of a chain of S + 1 views, each passing the trunks once), ThreeViewOnlineStitcher through its
+    `chains`.  State layout (_pair_static; fixed addresses, the step is captured):
+      lr1, lr2 [S,3,360,480] back to back (chain: lrc [S+1,3,360,480]), hr1, hr2 [S,3,H,W] only where the graph renders
+      pair_s [2 views][prev, new][S][126]   spatial motions of the previous and the current pair
+      pair_t [2 views][zero, new][S][126]   temporal motions (slot 0 stays zero; rewritten in full by every push)
+      ring   [smesh v0, smesh v1, tsm v0, tsm v1][S][7][126]     the sliding SmoothNet windows
+      prev_feat [2 S,45,60,128] view-major (chain: [S+1,45,60,128])   TemporalNet stage-1 features of the previous frame
+    A class provides _init_static (the state its window fill left -> _pair_static) and _tail (what follows the meshes)."""
+    S, chain = 1, False
+
+    def _pair_static(self, prev_feat, pair_s, ring):
+        d, S, e = self.dev, self.S, 126
+        lr = torch.empty((2, S, 3, pipeline.LR_H, pipeline.LR_W), device=d)       # both views back to back: one layout launch per push
+        # frame copies only where the graph renders (meshes_only: no render; direct: the push renders from the caller's frames)
+        inside = not self.meshes_only and not self._direct()
+        hr = torch.empty((2, S, 3, self.h, self.w), device=d) if inside else (None, None)
+        self.static = {'hr1': hr[0], 'hr2': hr[1], 'lr1': lr[0], 'lr2': lr[1],
+                       # (chain: the S + 1 views once -- pair s holds views s and s + 1; ops.cost_volume(chain=S) pairs them up)
+                       'lrc': torch.empty((S + 1, 3, pipeline.LR_H, pipeline.LR_W), device=d) if self.chain else None,
+                       'prev_feat': prev_feat, 'pair_s': pair_s, 'pair_t': torch.zeros((2, 2, S, e), device=d), 'ring': ring,
+                       'ts_out': torch.empty((2, 4 * S, e), device=d),
+                       # the render's targets inside the graph: per class ('out_all': all streams' canvases as one tensor)
+                       'out': None, 'out_all': None}
+
+    def _load(self, frames, u8):
+        st, S = self.static, self.S
+        if u8 is not None:               # decoded uint8 frames (push_u8): the cv2-exact resize writes the graph's LR inputs itself
+            for img, lr in zip(u8, (st['lr1'], st['lr2'])):
+                ops.ingest_u8(img.reshape(S, self.h, self.w, 3), pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=lr)
+            return
+        hr1, hr2, lr1, lr2 = frames
+        if self.chain:                   # (pair s = views s, s + 1: lr1 holds views 0 .. S-1, lr2's last row is view S)
+            st['lrc'][:S].copy_(lr1); st['lrc'][S:].copy_(lr2[S - 1:])
+        else:
+            st['lr1'].copy_(lr1.reshape(st['lr1'].shape)); st['lr2'].copy_(lr2.reshape(st['lr2'].shape))
+        if st['hr1'] is not None:        # (meshes_only: the frames are not looked at, None will do; direct: rendered where they lie)
+            st['hr1'].copy_(hr1.reshape(st['hr1'].shape)); st['hr2'].copy_(hr2.reshape(st['hr2'].shape))
+
+    def _step_static(self):
+        """One steady-state push on the static buffers (capturable: no host sync, no data-dependent shapes; every result
+        lands in place -- no torch op in the step besides the copy of the cached features)."""
+        st = self.static
+        f2, off1 = self._stage_a(st['lrc'] if self.chain else (st['lr1'], st['lr2']))
+        out = st['out'] if st['out_all'] is None else st['out_all']
+        self._stage_b(f2[0], f2[1], off1, st['hr1'], st['hr2'], _DEFER if self._direct() else out)
+
+    def _stage_a(self, lr):
+        """First half of a steady-state push -- it touches NO stream state: both nets' stage-1 trunks on the LR frames (one grouped
+        launch per layer: SpatialNet and TemporalNet read the same frames through trunks of identical architecture), then
+        SpatialNet's stage-2 trunk, contextual correlation and regressNet1.
+        lr: the two views' frames (lr1, lr2), [S,3,360,480] each, or -- chain -- the S + 1 views' frames [S+1,3,360,480], each once
+        -> (f2 [2(net), 2 S view-major (chain: S + 1), 45,60,128]: f2[0] SpatialNet's, f2[1] TemporalNet's features; offset_1 [S,8] |
+        None)."""
+        f2 = L.run_stage1_pair([lr] if self.chain else list(lr), self._trunk())
+        return f2, (_heads_a(self.spatial, f2[0], self.S, self.chain) if L.QUAD else None)
+
+    def _stage_b(self, f64, feat, off1, hr1, hr2, out):
+        """Second half: everything that reads or advances the streams' state (cached features, previous motions, the sliding
+        windows) -> the smoothed meshes of the S newest windows, then the class's `_tail`: the render of the new frames into `out`
+        (out=_DEFER: splines and footprints only, the push launches the render itself), or the meshes themselves (meshes_only)."""
+        st, S, e = self.static, self.S, 126
+        ps, pt = st['pair_s'], st['pair_t']
+        tm_out = (pt[0, 1], pt[1, 1])
+        if off1 is None:
+            off1, off_ref, off_tgt = _spatial_temporal_heads(self.spatial, self.temporal, f64, st['prev_feat'], feat, S, tm_out,
+                                                             chain=self.chain)
+        else:
+            off_ref, off_tgt = _heads_b(self.spatial, self.temporal, f64, off1, st['prev_feat'], feat, S, tm_out, self.chain)
+        ops.spatial_meshes(off1, off_ref, off_tgt, pipeline.LR_H, pipeline.LR_W,
+                           out=(ps[0, 1].view(S, 7, 9, 2), ps[1, 1].view(S, 7, 9, 2)))
+        st['prev_feat'].copy_(feat)
+        # tsmotion of all streams and both views as ONE batch of 4 S frames laid out [view][prev, new][stream]: frame k pairs
+        # with frame k - S (its own stream's previous frame); the rows of the `prev` halves are computed and ignored
+        ops.tsmotion(ps.view(4 * S, 7, 9, 2), pt.view(4 * S, 7, 9, 2), pipeline.LR_H, pipeline.LR_W,
+                     out=(st['ts_out'][0], st['ts_out'][1]), lag=S)
+        # shift the 4 S rings, append this push's rows (smesh v0, smesh v1, tsm v0, tsm v1 of every stream), and make the
+        # current spatial motions the previous ones
+        ops.window_push(st['ring'] if S > 1 else st['ring'].view(4, WINDOW, e), st['ts_out'],
+                        [1 * S * e, 3 * S * e, (4 * S + 1 * S) * e, (4 * S + 3 * S) * e], state=ps,
+                        blocks=2, block=S * e, stride=2 * S * e, delta=S * e, per=S)
+        r = st['ring'].view(4, S * WINDOW, 7, 9, 2)
+        outs, _ = self.smooth.run_windows(r[0], r[1], r[2], r[3], S, WINDOW, WINDOW, 1)       # S windows, one per stream
+        self._tail(outs['smooth_mesh1'], outs['smooth_mesh2'], hr1, hr2, out)                # [S,7,7,9,2]
+
+
+class OnlineStitcher(_PairStep, _Stitcher):
+    """One live two-view stream (the module docstring): the window fill (`_push`), then _PairStep's steady-state step with S = 1; the
+    tail behind the meshes is `_render` -- splines, watcher, footprints, exposure and every fusion mode, MULTIBAND included."""
     _MULTIBAND = True
 
     def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
@@ -1085,75 +1195,22 @@ class OnlineStitcher(_Stitcher):
 
     # ------------------------------------------------------------------ steady state (window full, canvas fixed)
     def _init_static(self):
-        d = self.dev
+        """The window fill's state in the S = 1 layout of _PairStep; an output canvas only where the graph renders."""
         e = 126
-        pair_s = torch.zeros((2, 2, e), device=d)
-        pair_s[:, 0] = self.prev_smotion.reshape(2, e)
-        ring = torch.stack([torch.cat(r, 0).reshape(WINDOW, e) for r in (self.ring_smesh[0], self.ring_smesh[1],
-                                                                          self.ring_tsm[0], self.ring_tsm[1])], 0).contiguous()
-        lr = torch.empty((2, 1, 3, pipeline.LR_H, pipeline.LR_W), device=d)       # both views back to back: one layout launch per push
-        # frame copies and an output canvas only where the graph renders (meshes_only: no render; direct: the push renders)
-        inside = not self.meshes_only and not self._direct()
-        hr = (lambda: torch.empty((1, 3, self.h, self.w), device=d)) if inside else (lambda: None)
-        self.static = {'hr1': hr(), 'hr2': hr(), 'lr1': lr[0], 'lr2': lr[1],
-                       'prev_feat': self.prev_feat.clone(), 'pair_s': pair_s, 'pair_t': torch.zeros((2, 2, e), device=d),
-                       'ring': ring, 'ts_out': torch.empty((2, 4, e), device=d),
-                       'out': torch.empty((3, self.hc, self.wc), device=d) if inside else None}
+        pair_s = torch.zeros((2, 2, 1, e), device=self.dev)
+        pair_s[:, 0, 0] = self.prev_smotion.reshape(2, e)
+        ring = torch.stack([torch.cat(r, 0).reshape(1, WINDOW, e) for r in (self.ring_smesh[0], self.ring_smesh[1],
+                                                                             self.ring_tsm[0], self.ring_tsm[1])], 0).contiguous()
+        self._pair_static(self.prev_feat.clone(), pair_s, ring)
+        if self.static['hr1'] is not None:
+            self.static['out'] = torch.empty((3, self.hc, self.wc), device=self.dev)
 
-    def _load(self, frames, u8):
-        st = self.static
-        if u8 is not None:                   # decoded uint8 frames (push_u8): the cv2-exact resize writes the graph's LR buffers itself
-            ops.ingest_u8(u8[0][None], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr1'])
-            ops.ingest_u8(u8[1][None], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr2'])
-            return
-        hr1, hr2, lr1, lr2 = frames
-        if not self.meshes_only and not self._direct():  # (meshes_only: the frames are not looked at, None will do; direct: rendered in place)
-            st['hr1'].copy_(hr1.reshape(st['hr1'].shape)); st['hr2'].copy_(hr2.reshape(st['hr2'].shape))
-        st['lr1'].copy_(lr1.reshape(st['lr1'].shape)); st['lr2'].copy_(lr2.reshape(st['lr2'].shape))
-
-    def _step_static(self):
-        """One steady-state push on the static buffers (capturable: no host sync, no data-dependent shapes; every result
-        lands in place -- no torch op in the step besides the copy of the cached features)."""
-        st = self.static
-        f2, off1 = self._stage_a(st['lr1'], st['lr2'])
-        self._stage_b(f2, off1, st['hr1'], st['hr2'], _DEFER if self._direct() else st['out'])
-
-    def _stage_a(self, lr1, lr2):
-        """First half of a steady-state push -- it touches NO stream state: both nets' stage-1 trunks on the two LR frames (one
-        grouped launch per layer: SpatialNet and TemporalNet read the same frames through trunks of identical architecture), then
-        SpatialNet's stage-2 trunk, contextual correlation and regressNet1 -> (f2 [2(net),2(view),45,60,128], offset_1 [1,8])."""
-        f2 = L.run_stage1_pair([lr1, lr2], self._trunk())
-        if not L.QUAD:
-            return f2, None
-        return f2, _heads_a(self.spatial, f2[0], 1)
-
-    def _stage_b(self, f2, off1, hr1, hr2, out):
-        """Second half: everything that reads or advances the stream's state (cached features, previous motions, the sliding
-        window) and the render of the new frame into `out`."""
-        st = self.static
-        e = 126
-        ps, pt = st['pair_s'], st['pair_t']
-        feat = f2[1]
-        tm_out = (pt[0, 1:2], pt[1, 1:2])
-        if off1 is None:
-            off1, off_ref, off_tgt = _spatial_temporal_heads(self.spatial, self.temporal, f2[0], st['prev_feat'], feat, 1, tm_out)
-        else:
-            off_ref, off_tgt = _heads_b(self.spatial, self.temporal, f2[0], off1, st['prev_feat'], feat, 1, tm_out)
-        ops.spatial_meshes(off1, off_ref, off_tgt, pipeline.LR_H, pipeline.LR_W,
-                           out=(ps[0, 1].view(1, 7, 9, 2), ps[1, 1].view(1, 7, 9, 2)))
-        st['prev_feat'].copy_(feat)
-        # tsmotion of both views as ONE batch of 4 frames (v0 prev, v0 new, v1 prev, v1 new): frame k pairs with frame k - 1,
-        # rows 1 and 3 are this pair's; row 2 (view 1's previous frame against view 0's new one) is computed and ignored
-        ops.tsmotion(ps.view(4, 7, 9, 2), pt.view(4, 7, 9, 2), pipeline.LR_H, pipeline.LR_W, out=(st['ts_out'][0], st['ts_out'][1]))
-        # shift the four rings by one frame, append this pair's rows, and make the current spatial motions the previous ones
-        ops.window_push(st['ring'], st['ts_out'], [1 * e, 3 * e, 5 * e, 7 * e], state=ps, blocks=2, block=e, stride=2 * e, delta=e)
-        r = st['ring'].view(4, WINDOW, 7, 9, 2)
-        outs, _ = self.smooth.run_windows(r[0], r[1], r[2], r[3], 1, WINDOW, 1, 1)
-        m1, m2 = outs['smooth_mesh1'][0], outs['smooth_mesh2'][0]
+    def _tail(self, m1, m2, hr1, hr2, out):
+        m1, m2 = m1[0, -1:], m2[0, -1:]          # the newest frame's meshes [1,7,9,2]
         if self.meshes_only:
-            self.last_meshes = (m1[-1:], m2[-1:])
+            self.last_meshes = (m1, m2)
             return
-        self._render(hr1, hr2, m1[-1:], m2[-1:], out=out)
+        self._render(hr1, hr2, m1, m2, out=out)
 
     @torch.no_grad()
     def push(self, hr1, hr2, lr1, lr2):
@@ -1183,12 +1240,7 @@ class OnlineStitcher(_Stitcher):
         if self.meshes_only:
             raise ValueError('push_u8 renders frames: not for meshes_only stitchers')
         _check_u8('two uint8 [H,W,3] frames', (img1, img2), (self.h, self.w, 3))
-        with ops.deterministic(self.deterministic):
-            if self._u8_steady():
-                return self._push_static(u8=(img1.contiguous(), img2.contiguous()))
-            hr, lr = ops.ingest_u8(torch.stack((img1, img2), 0), pipeline.LR_H, pipeline.LR_W)
-            frames = self._push(hr[0:1], hr[1:2], lr[0:1], lr[1:2])
-            return [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
+        return self._push_u8((img1, img2))
 
     def _lr_inputs(self):
         return [self.static['lr1'], self.static['lr2']]
@@ -1321,13 +1373,13 @@ class OnlineStitcher(_Stitcher):
         st['prev_feat'].copy_(F[:, k])
         ops.spatial_meshes(off1, off_ref, off_tgt, pipeline.LR_H, pipeline.LR_W,
                            out=(sw[0, 1:].view(k, 7, 9, 2), sw[1, 1:].view(k, 7, 9, 2)))
-        sw[:, 0].copy_(st['pair_s'][:, 0])
+        sw[:, 0].copy_(st['pair_s'][:, 0, 0])
         # tsmotion of both views as ONE batch of 2 (k + 1) rows [view][previous, the k frames]: row j pairs with row j - 1; the
         # rows of slot 0 are computed and ignored
         ops.tsmotion(sw.view(2 * (k + 1), 7, 9, 2), tt.view(2 * (k + 1), 7, 9, 2), pipeline.LR_H, pipeline.LR_W, out=(ts[0], ts[1]))
         # the k windows of every ring in `work`, the rings advanced by k frames, the newest spatial motions made the previous ones
         n1 = k + 1
-        ops.window_advance(st['ring'], B['work'], ts, [(0 * n1 + 1) * e, (1 * n1 + 1) * e, (2 * n1 + 1) * e, (3 * n1 + 1) * e], k,
+        ops.window_advance(st['ring'].view(4, WINDOW, e), B['work'], ts, [(0 * n1 + 1) * e, (1 * n1 + 1) * e, (2 * n1 + 1) * e, (3 * n1 + 1) * e], k,
                            state=st['pair_s'], state_src=sw.view(-1)[k * e:], blocks=2, block=e, stride=2 * e, src_stride=n1 * e)
         wk = B['work'].view(4, WINDOW - 1 + k, 7, 9, 2)
         outs, _ = self.smooth.run_windows(wk[0], wk[1], wk[2], wk[3], k, WINDOW, 1, 1)
@@ -1374,7 +1426,8 @@ class _TwoInFlight:
     grow='refit' (with a viewport) holds with two pushes in flight: only second halves touch the canvas box (the splines launch reads
     it, the launch that carries the watcher rewrites it), and the second halves and direct renders of consecutive pushes all run in
     order on the ONE stream sb -- the box push t rewrites is the box push t + 1 reads.  grow='recapture' is not offered.
-    A subclass provides _pipe_alloc / _pipe_load / _run_a / _run_b (and _pipe_empty for S streams)."""
+    The halves of a _PairStep push (_pipe_alloc / _pipe_load / _run_a / _run_b) are here; a subclass adds its output buffers to
+    _pipe_alloc (and _pipe_empty for S streams), PipelinedThreeViewOnlineStitcher has its own three-view loads and second half."""
     _LINEAR_DIRECT = False
     _MULTIBAND = False       # (MULTIBAND is launched by the push on the caller's frames: not with two pushes in flight)
 
@@ -1384,6 +1437,49 @@ class _TwoInFlight:
         self.pipe = None
         self._pending = None             # (event behind it, result) of the newest enqueued push
         self._t = 0
+
+    # ------------------------------------------------------------------ the halves of a _PairStep push, per buffer parity p
+    def _pipe_alloc(self):
+        """Both parities' inputs and hand-over buffers of S two-view streams; the class adds its outputs ('out', 'out_all')."""
+        d, S = self.dev, self.S
+        two = lambda *shape: [torch.empty(shape, device=d) for _ in range(2)]
+        return {'lr': two(2, S, 3, pipeline.LR_H, pipeline.LR_W),
+                'hr': [(None, None)] * 2 if self._direct() else two(2, S, 3, self.h, self.w),       # (direct render: no copies)
+                'f2': two(2, 2 * S, pipeline.LR_H // 8, pipeline.LR_W // 8, 128), 'off1': two(S, 8)}
+
+    def _pipe_load(self, p, sa, sb, hr1, hr2, lr1, lr2):
+        lr, hr = self.pipe['lr'][p], self.pipe['hr'][p]
+        if hr1.dtype == torch.uint8:         # push_u8: decoded frames -- the cv2-exact resize writes this parity's LR inputs
+            with torch.cuda.stream(sa):
+                for v, img in enumerate((hr1, hr2)):
+                    ops.ingest_u8(img.reshape(self.S, self.h, self.w, 3), pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=lr[v])
+            for t in (hr1, hr2):
+                t.record_stream(sa)
+                t.record_stream(sb)
+            return
+        with torch.cuda.stream(sa):
+            lr[0].copy_(lr1.reshape(lr[0].shape)); lr[1].copy_(lr2.reshape(lr[1].shape))
+        if not self._direct():                  # (direct render: the second stream's render reads the caller's frames)
+            with torch.cuda.stream(sb):
+                hr[0].copy_(hr1.reshape(hr[0].shape)); hr[1].copy_(hr2.reshape(hr[1].shape))
+        for t in (hr1, hr2):
+            t.record_stream(sb)
+        for t in (lr1, lr2):
+            t.record_stream(sa)
+
+    def _run_a(self, p):
+        """The first half; the two nets' features are handed over with a copy each (PipelinedOnlineStitcher: its own, with one)."""
+        P = self.pipe
+        f2, off1 = self._stage_a(P['lr'][p])
+        P['f2'][p][0].copy_(f2[0])
+        P['f2'][p][1].copy_(f2[1])
+        P['off1'][p].copy_(off1)
+
+    def _run_b(self, p):
+        P = self.pipe
+        f2, (hr1, hr2) = P['f2'][p], P['hr'][p]
+        out = P['out'][p] if P['out_all'][p] is None else P['out_all'][p]
+        self._stage_b(f2[0], f2[1], P['off1'][p], hr1, hr2, _DEFER if self._direct() else out)
 
     def _capture_pipe(self):
         """Warm both halves up eagerly on a copy of the state (parity 0 holds the current push's inputs), then capture each half for
@@ -1511,11 +1607,7 @@ class _TwoInFlight:
 
     def flush_u8(self):
         """`flush()` for streams fed through push_u8: the last result as uint8 video frames."""
-        def conv(x):
-            if torch.is_tensor(x):
-                return x if x.dtype == torch.uint8 else ops.canvas_to_u8(x.reshape((1,) + tuple(x.shape[-3:])))[0]
-            return [conv(y) for y in x]
-        return conv(self.flush())
+        return _to_u8(self.flush())
 
     def overflow_report(self):
         self._sync_state()
@@ -1540,6 +1632,18 @@ def _tensors_of(x):
             yield from _tensors_of(y)
 
 
+_BATCH_AND_NV12 = ('push_many', 'push_many_u8', 'push_nv12', 'push_many_nv12')
+
+
+def _refusals(cls, plain, *names):
+    """The entries `names` of the plain stitcher that its form with two pushes in flight does not offer: methods that refuse."""
+    def refusal(name):
+        def method(self, *frames, **kw):
+            raise ValueError('%s has no %s: use %s.%s' % (cls, name, plain, name))
+        return method
+    return [refusal(name) for name in names]
+
+
 class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
     """OnlineStitcher with TWO pushes in flight (round 6; opt-in; see _TwoInFlight).  Frames bit-identical to OnlineStitcher
     (tests/test_gpu_round6.py), handed out one push late:
@@ -1558,60 +1662,21 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
                                 meshes_only=False, deterministic=deterministic, viewport=viewport, zoom_limit=zoom_limit)
         self._pipe_init()
 
-    def push_many(self, *frames):
-        raise ValueError('PipelinedOnlineStitcher has no push_many: use OnlineStitcher.push_many')
-
-    def push_many_u8(self, *frames):
-        raise ValueError('PipelinedOnlineStitcher has no push_many_u8: use OnlineStitcher.push_many_u8')
-
-    def push_nv12(self, *frames, **kw):
-        raise ValueError('PipelinedOnlineStitcher has no push_nv12: use OnlineStitcher.push_nv12')
-
-    def push_many_nv12(self, *frames, **kw):
-        raise ValueError('PipelinedOnlineStitcher has no push_many_nv12: use OnlineStitcher.push_many_nv12')
+    push_many, push_many_u8, push_nv12, push_many_nv12 = _refusals('PipelinedOnlineStitcher', 'OnlineStitcher', *_BATCH_AND_NV12)
 
     def _pipe_alloc(self):
-        d = self.dev
-        two = lambda *shape: [torch.empty(shape, device=d) for _ in range(2)]
-        hr = (lambda: [None, None]) if self._direct() else (lambda: two(1, 3, self.h, self.w))     # direct render: no copies of the frames
-        return {'lr': two(2, 1, 3, pipeline.LR_H, pipeline.LR_W), 'hr1': hr(), 'hr2': hr(),
-                'f2': two(2, 2, pipeline.LR_H // 8, pipeline.LR_W // 8, 128), 'off1': two(1, 8),
-                'out': [None, None] if self._direct() else two(3, self.hc, self.wc)}
-
-    def _pipe_load(self, p, sa, sb, hr1, hr2, lr1, lr2):
-        P = self.pipe
-        if hr1.dtype == torch.uint8:         # push_u8: decoded [H,W,3] frames -- the cv2-exact resize writes this parity's LR inputs
-            with torch.cuda.stream(sa):
-                ops.ingest_u8(hr1[None], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=P['lr'][p][0])
-                ops.ingest_u8(hr2[None], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=P['lr'][p][1])
-            for t in (hr1, hr2):
-                t.record_stream(sa)
-                t.record_stream(sb)
-            return
-        with torch.cuda.stream(sa):
-            P['lr'][p][0].copy_(lr1.reshape(P['lr'][p][0].shape))
-            P['lr'][p][1].copy_(lr2.reshape(P['lr'][p][1].shape))
-        if not self._direct():                  # (direct render: the second stream's render reads the caller's frames)
-            with torch.cuda.stream(sb):
-                P['hr1'][p].copy_(hr1.reshape(P['hr1'][p].shape))
-                P['hr2'][p].copy_(hr2.reshape(P['hr2'][p].shape))
-        for t in (hr1, hr2):
-            t.record_stream(sb)
-        for t in (lr1, lr2):
-            t.record_stream(sa)
+        out = [None, None] if self._direct() else [torch.empty((3, self.hc, self.wc), device=self.dev) for _ in range(2)]
+        return dict(_TwoInFlight._pipe_alloc(self), out=out, out_all=[None, None])
 
     def _run_a(self, p):
+        """The first half; both nets' features are handed over with ONE copy (a graph node less than the shared form's two)."""
         P = self.pipe
-        f2, off1 = self._stage_a(P['lr'][p][0], P['lr'][p][1])
+        f2, off1 = self._stage_a(P['lr'][p])
         P['f2'][p].copy_(f2)
         P['off1'][p].copy_(off1)
 
-    def _run_b(self, p):
-        P = self.pipe
-        self._stage_b(P['f2'][p], P['off1'][p], P['hr1'][p], P['hr2'][p], _DEFER if self._direct() else P['out'][p])
 
-
-class MultiOnlineStitcher(_Stitcher):
+class MultiOnlineStitcher(_PairStep, _Stitcher):
     """S independent live video pairs advancing one frame per push as ONE batch (the sharding unit of the
     path -- independent streams -- inside one GPU).  A single stream at batch 1 is launch-bound (~150 small launches per
     pushed pair); S streams run the same launches on S-fold batches, so the aggregate frame rate grows almost linearly until
@@ -1623,7 +1688,8 @@ class MultiOnlineStitcher(_Stitcher):
         frames = st.push(hr1, hr2, lr1, lr2)      # hr* [S,3,H,W], lr* [S,3,360,480] -> S lists of new frames [3,Hc_s,Wc_s]
 
     The first WINDOW pushes fill every stream's window through S single-stream stitchers (eager; they hold the streams' canvases
-    afterwards); from then on the step runs on static buffers with a leading S and is captured into one HIP graph.  Results equal S
+    afterwards); from then on the step -- _PairStep's, the code OnlineStitcher runs with S = 1 -- runs on their states joined along
+    the stream axis and is captured into one HIP graph.  Results equal S
     single-stream stitchers up to the conv engine's launch-size-dependent kernel choice (Winograd / implicit GEMM / split-K are picked
     per launch size, so a batch of S sums in another order than S batches of one: motions differ by ~1e-5 px); within a batch every
     stream's result is independent of its neighbours bit for bit (tests/test_gpu_round4.py)."""
@@ -1665,26 +1731,15 @@ class MultiOnlineStitcher(_Stitcher):
         return [(s.hc, s.wc) for s in self.single]
 
     def _init_static(self):
-        """Batched steady-state buffers from the S single-stream states (each has just completed its first window):
-          pair_s / pair_t [2 views][prev, new][S][126], ring [4 kinds][S][7][126], prev_feat [2 views * S,45,60,128] view-major
-          (chain: [S + 1,45,60,128])."""
-        d, S, e = self.dev, self.S, 126
+        """The batched state from the S single-stream states (each has just completed its first window, in the same layout with
+        S = 1): joined along the stream axis."""
         one = [s.static for s in self.single]
-        lr = torch.empty((2, S, 3, pipeline.LR_H, pipeline.LR_W), device=d)       # both views back to back: one layout launch per push
-        # (copies of the frames only where the graph renders: meshes_only has no render, the direct render reads the caller's frames)
-        hr = None if self.meshes_only or self._direct() else torch.empty((2, S, 3, self.h, self.w), device=d)
-        st = {'hr1': None if hr is None else hr[0], 'hr2': None if hr is None else hr[1],
-              'lr1': lr[0], 'lr2': lr[1],
-              'lrc': torch.empty((S + 1, 3, pipeline.LR_H, pipeline.LR_W), device=d) if self.chain else None,
-              # (chain: the S + 1 views once -- pair s holds views s and s + 1; ops.cost_volume(chain=S) pairs them up)
-              'prev_feat': (torch.stack([o['prev_feat'][0] for o in one] + [one[-1]['prev_feat'][1]], 0).contiguous() if self.chain else
-                            torch.cat([torch.stack([o['prev_feat'][v] for o in one], 0) for v in range(2)], 0).contiguous()),
-              'pair_s': torch.stack([o['pair_s'] for o in one], 2).contiguous(),           # [2,2,S,126]
-              'pair_t': torch.zeros((2, 2, S, e), device=d),
-              'ring': torch.stack([o['ring'] for o in one], 1).contiguous(),               # [4,S,7,126]
-              'ts_out': torch.empty((2, 4 * S, e), device=d),
-              'out': None, 'out_all': None, 'one_size': False}
-        self.static = st
+        if self.chain:                    # each view once: the first view of every pair, then the last pair's second
+            prev_feat = torch.stack([o['prev_feat'][0] for o in one] + [one[-1]['prev_feat'][1]], 0).contiguous()
+        else:                             # [2,1,...] per stream -> view-major [2 S,...]
+            prev_feat = torch.stack([o['prev_feat'] for o in one], 1).flatten(0, 1)
+        self._pair_static(prev_feat, torch.cat([o['pair_s'] for o in one], 2), torch.cat([o['ring'] for o in one], 1))
+        st = self.static
         if not self.meshes_only:
             st['bboxes'] = torch.stack([s.bbox for s in self.single], 0).contiguous()        # [S,4] the streams' fixed canvases
             # the streams' watcher rows (their first windows are counted) go on as rows of one [S,4] state (ops.canvas_watch)
@@ -1732,69 +1787,14 @@ class MultiOnlineStitcher(_Stitcher):
             self.static['bboxes'][s].copy_(one.bbox)
         self._alloc_outputs()
 
-    def _load(self, frames, u8):
-        st = self.static
-        if u8 is not None:               # push_u8: decoded [S,H,W,3] frames of both views -- the cv2-exact resize writes the LR inputs
-            ops.ingest_u8(u8[0], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr1'])
-            ops.ingest_u8(u8[1], pipeline.LR_H, pipeline.LR_W, want_hr=False, lr_out=st['lr2'])
-            return
-        hr1, hr2, lr1, lr2 = frames
-        if self.chain:                   # (pair s = views s, s + 1: lr1 holds views 0 .. S-1, lr2's last row is view S)
-            st['lrc'][:self.S].copy_(lr1); st['lrc'][self.S:].copy_(lr2[self.S - 1:])
-        else:
-            st['lr1'].copy_(lr1); st['lr2'].copy_(lr2)
-        if not self.meshes_only and not self._direct():
-            st['hr1'].copy_(hr1); st['hr2'].copy_(hr2)
-
-    def _step_static(self):
-        st = self.static
-        f64, feat, off1 = self._stage_a(st['lrc'] if self.chain else [st['lr1'], st['lr2']])
-        self._stage_b(f64, feat, off1, st['hr1'], st['hr2'], st['out_all'], st['out'], defer=self._direct())
-
-    def _stage_a(self, lr):
-        """First half of a steady-state push (no stream state): trunks, SpatialNet's stage-2 trunk, CCL, regressNet1.
-        lr: [lr1, lr2] ([S,3,360,480] each) or, chain mode, the S + 1 views' frames [S+1,3,360,480] (each view once)
-        -> (f64 SpatialNet trunk features, feat TemporalNet features [2S, view-major] (chain: [S + 1], each view once), offset_1 [S,8] | None)."""
-        S = self.S
-        if self.chain:
-            fc = L.run_stage1_pair([lr], self._trunk())                            # [2(net), S + 1 views, 45,60,128]: each view once
-            feat = fc[1]                                                           # TemporalNet's features of the S + 1 views, each once
-            f64 = fc[0]
-        else:
-            f2 = L.run_stage1_pair(list(lr), self._trunk())                        # [2(net), 2S (view-major), 45,60,128]
-            feat, f64 = f2[1], f2[0]
-        return f64, feat, (_heads_a(self.spatial, f64, S, self.chain) if L.QUAD else None)
-
-    def _stage_b(self, f64, feat, off1, hr1, hr2, out_all, out, defer=False):
-        """Second half: everything that reads or advances the streams' state, and the render into out_all / out (defer: splines
-        and footprints only -- self._deferred: one _Deferred over the S streams, or one per stream -- the push launches the render
-        itself)."""
-        st, S, e = self.static, self.S, 126
-        ps, pt = st['pair_s'], st['pair_t']
-        tm_out = (pt[0, 1], pt[1, 1])
-        if off1 is None:
-            off1, off_ref, off_tgt = _spatial_temporal_heads(self.spatial, self.temporal, f64, st['prev_feat'], feat, S, tm_out,
-                                                             chain=self.chain)
-        else:
-            off_ref, off_tgt = _heads_b(self.spatial, self.temporal, f64, off1, st['prev_feat'], feat, S, tm_out, self.chain)
-        ops.spatial_meshes(off1, off_ref, off_tgt, pipeline.LR_H, pipeline.LR_W,
-                           out=(ps[0, 1].view(S, 7, 9, 2), ps[1, 1].view(S, 7, 9, 2)))
-        st['prev_feat'].copy_(feat)
-        # tsmotion of all streams and both views as ONE batch of 4 S frames laid out [view][prev, new][stream]: frame k pairs
-        # with frame k - S (its own stream's previous frame); the rows of the `prev` halves are computed and ignored
-        ops.tsmotion(ps.view(4 * S, 7, 9, 2), pt.view(4 * S, 7, 9, 2), pipeline.LR_H, pipeline.LR_W,
-                     out=(st['ts_out'][0], st['ts_out'][1]), lag=S)
-        # shift the 4 S rings, append this push's rows (smesh v0, smesh v1, tsm v0, tsm v1 of every stream), and make the
-        # current spatial motions the previous ones
-        ops.window_push(st['ring'] if S > 1 else st['ring'].view(4, WINDOW, e), st['ts_out'],
-                        [1 * S * e, 3 * S * e, (4 * S + 1 * S) * e, (4 * S + 3 * S) * e], state=ps,
-                        blocks=2, block=S * e, stride=2 * S * e, delta=S * e, per=S)
-        r = st['ring'].view(4, S * WINDOW, 7, 9, 2)
-        outs, _ = self.smooth.run_windows(r[0], r[1], r[2], r[3], S, WINDOW, WINDOW, 1)       # S windows, one per stream
-        m1, m2 = outs['smooth_mesh1'], outs['smooth_mesh2']                                    # [S,7,7,9,2]
+    def _tail(self, m1, m2, hr1, hr2, out):
+        """The S newest frames from the streams' smoothed windows m1, m2 [S,7,7,9,2]: rendered into `out` -- one tensor [S,3,Hc,Wc]
+        where the canvases share a size, else one per stream -- or, out=_DEFER, left as self._deferred (one _Deferred over the S
+        streams, or one per stream) for the push's own render."""
         if self.meshes_only:
             self.last_meshes = (m1[:, -1:], m2[:, -1:])                                       # [S,1,7,9,2]
             return
+        st, e, defer = self.static, 126, out is _DEFER
         # every stream's newest smoothed mesh on its own canvas: control points and ONE batched TPS solve for the 2 S splines in one
         # launch (a solve is latency-bound, ~48 us whether it holds 2 systems or 16), the watcher on the footprint launch(es), then
         # the render stream by stream
@@ -1808,7 +1808,7 @@ class MultiOnlineStitcher(_Stitcher):
             if defer:
                 self._deferred = left
             else:
-                mode.batch([hr1, hr2], left, hc, wc, out=out_all)
+                mode.batch([hr1, hr2], left, hc, wc, out=out)
             return
         # canvases of several sizes: stream by stream, on the streams' own stitchers (defer: their records, kept here)
         left = [one._render_solved(None if defer else [hr1[s:s + 1], hr2[s:s + 1]], src[s], T[s], out=_DEFER if defer else out[s],
@@ -1831,13 +1831,7 @@ class MultiOnlineStitcher(_Stitcher):
         if self.meshes_only or self.chain:
             raise ValueError('push_u8 renders frames of independent streams: not for meshes_only / chain stitchers')
         _check_u8('two uint8 [%d,H,W,3] tensors' % S, (frames1, frames2), (S, self.h, self.w, 3))
-        with ops.deterministic(self.deterministic):
-            if self._u8_steady():
-                return self._push_static(u8=(frames1.contiguous(), frames2.contiguous()))
-            hr1, lr1 = ops.ingest_u8(frames1, pipeline.LR_H, pipeline.LR_W)
-            hr2, lr2 = ops.ingest_u8(frames2, pipeline.LR_H, pipeline.LR_W)
-            outs = self._push(hr1, hr2, lr1, lr2)
-            return [[ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in per] for per in outs]
+        return self._push_u8((frames1, frames2))
 
     @torch.no_grad()
     def push_nv12(self, frames1, frames2, out='bgr'):
@@ -1900,18 +1894,12 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
                                      zoom_limit=zoom_limit)
         self._pipe_init()
 
-    def push_nv12(self, *frames, **kw):
-        raise ValueError('PipelinedMultiOnlineStitcher has no push_nv12: use MultiOnlineStitcher.push_nv12')
+    push_nv12, = _refusals('PipelinedMultiOnlineStitcher', 'MultiOnlineStitcher', 'push_nv12')
 
     def _pipe_alloc(self):
-        d, S = self.dev, self.S
-        two = lambda *shape: [torch.empty(shape, device=d) for _ in range(2)]
-        fh, fw = pipeline.LR_H // 8, pipeline.LR_W // 8
-        P = {'lr': two(2, S, 3, pipeline.LR_H, pipeline.LR_W),
-             'hr': [[None, None], [None, None]] if self._direct() else two(2, S, 3, self.h, self.w),     # (direct render: no copies)
-             'f64': two(2 * S, fh, fw, 128), 'feat': two(2 * S, fh, fw, 128), 'off1': two(S, 8)}
+        P, S = _TwoInFlight._pipe_alloc(self), self.S
         if self.static['one_size']:
-            P['out_all'] = two(S, 3, *self.canvas_sizes[0])
+            P['out_all'] = [torch.empty_like(self.static['out_all']) for _ in range(2)]
             P['out'] = [[oa[s] for s in range(S)] for oa in P['out_all']]
         else:
             P['out_all'] = [None, None]
@@ -1920,30 +1908,6 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
 
     def _pipe_empty(self):
         return [[] for _ in range(self.S)]
-
-    def _pipe_load(self, p, sa, sb, hr1, hr2, lr1, lr2):
-        P = self.pipe
-        with torch.cuda.stream(sa):
-            P['lr'][p][0].copy_(lr1); P['lr'][p][1].copy_(lr2)
-        if not self._direct():                  # (direct render: the second stream's render reads the caller's frames)
-            with torch.cuda.stream(sb):
-                P['hr'][p][0].copy_(hr1); P['hr'][p][1].copy_(hr2)
-        for t in (hr1, hr2):
-            t.record_stream(sb)
-        for t in (lr1, lr2):
-            t.record_stream(sa)
-
-    def _run_a(self, p):
-        P = self.pipe
-        f64, feat, off1 = self._stage_a([P['lr'][p][0], P['lr'][p][1]])
-        P['f64'][p].copy_(f64)
-        P['feat'][p].copy_(feat)
-        P['off1'][p].copy_(off1)
-
-    def _run_b(self, p):
-        P = self.pipe
-        self._stage_b(P['f64'][p], P['feat'][p], P['off1'][p], P['hr'][p][0], P['hr'][p][1], P['out_all'][p], P['out'][p],
-                      defer=self._direct())
 
 
 class ThreeViewOnlineStitcher(_Stitcher):
@@ -2030,6 +1994,10 @@ class ThreeViewOnlineStitcher(_Stitcher):
     def _state(self):
         return [self.chains.static[k] for k in _STATE] + [self.watch.wi, self.watch.wf] + self.watch.fit_state()
 
+    def _stage_a(self, lr):
+        """The first half of a push is the chains' (_PairStep._stage_a over the three views' frames [3,3,360,480])."""
+        return self.chains._stage_a(lr)
+
     def _step_static(self):
         ch, hr = self.chains, self.static['hr']
         ch._step_static()
@@ -2054,12 +2022,7 @@ class ThreeViewOnlineStitcher(_Stitcher):
         byte ops.ingest_u8 -> push -> ops.canvas_to_u8 (see OnlineStitcher.push_u8)."""
         imgs = (img1, img2, img3)
         _check_u8('three uint8 [H,W,3] frames', imgs, (self.h, self.w, 3))
-        with ops.deterministic(self.deterministic):
-            if self._u8_steady():
-                return self._push_static(u8=tuple(i.contiguous() for i in imgs))
-            hr, lr = ops.ingest_u8(torch.stack(imgs, 0), pipeline.LR_H, pipeline.LR_W)
-            frames = self.push(hr[0:1], hr[1:2], hr[2:3], lr[0:1], lr[1:2], lr[2:3])
-            return [ops.canvas_to_u8(f.reshape((1,) + tuple(f.shape[-3:])))[0] for f in frames]
+        return self._push_u8(imgs)
 
     def _lr_inputs(self):
         return [self.chains.static['lrc'][k:k + 1] for k in range(3)]
@@ -2210,47 +2173,31 @@ class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
                                          use_graph=True, grow=grow, viewport=viewport, zoom_limit=zoom_limit)
         self._pipe_init()
 
-    def push_many(self, *frames):
-        raise ValueError('PipelinedThreeViewOnlineStitcher has no push_many: use ThreeViewOnlineStitcher.push_many')
-
-    def push_many_u8(self, *frames):
-        raise ValueError('PipelinedThreeViewOnlineStitcher has no push_many_u8: use ThreeViewOnlineStitcher.push_many_u8')
-
-    def push_nv12(self, *frames, **kw):
-        raise ValueError('PipelinedThreeViewOnlineStitcher has no push_nv12: use ThreeViewOnlineStitcher.push_nv12')
-
-    def push_many_nv12(self, *frames, **kw):
-        raise ValueError('PipelinedThreeViewOnlineStitcher has no push_many_nv12: use ThreeViewOnlineStitcher.push_many_nv12')
+    push_many, push_many_u8, push_nv12, push_many_nv12 = _refusals('PipelinedThreeViewOnlineStitcher', 'ThreeViewOnlineStitcher',
+                                                                   *_BATCH_AND_NV12)
 
     def _pipe_alloc(self):
         d = self.dev
         two = lambda *shape: [torch.empty(shape, device=d) for _ in range(2)]
-        fh, fw = pipeline.LR_H // 8, pipeline.LR_W // 8
-        return {'lrc': two(3, 3, pipeline.LR_H, pipeline.LR_W), 'hr': [None, None] if self._direct() else two(3, 3, self.h, self.w),
-                'f64': two(3, fh, fw, 128),
-                'feat': two(3, fh, fw, 128), 'off1': two(2, 8), 'out': [None, None] if self._direct() else two(3, self.hc, self.wc)}
+        # (each view once: three LR frames, the trunks' features of three images; _TwoInFlight._run_a hands them over)
+        return {'lr': two(3, 3, pipeline.LR_H, pipeline.LR_W), 'hr': [None, None] if self._direct() else two(3, 3, self.h, self.w),
+                'f2': two(2, 3, pipeline.LR_H // 8, pipeline.LR_W // 8, 128), 'off1': two(2, 8),
+                'out': [None, None] if self._direct() else two(3, self.hc, self.wc)}
 
     def _pipe_load(self, p, sa, sb, hr1, hr2, hr3, lr1, lr2, lr3):
         P = self.pipe
         for k, (h, l) in enumerate(((hr1, lr1), (hr2, lr2), (hr3, lr3))):
             with torch.cuda.stream(sa):
-                P['lrc'][p][k:k + 1].copy_(l.reshape(P['lrc'][p][k:k + 1].shape))
+                P['lr'][p][k:k + 1].copy_(l.reshape(P['lr'][p][k:k + 1].shape))
             if not self._direct():              # (direct render: the second stream's render reads the caller's frames)
                 with torch.cuda.stream(sb):
                     P['hr'][p][k:k + 1].copy_(h.reshape(P['hr'][p][k:k + 1].shape))
             h.record_stream(sb)
             l.record_stream(sa)
 
-    def _run_a(self, p):
-        P = self.pipe
-        f64, feat, off1 = self.chains._stage_a(P['lrc'][p])
-        P['f64'][p].copy_(f64)
-        P['feat'][p].copy_(feat)
-        P['off1'][p].copy_(off1)
-
     def _run_b(self, p):
         P, ch = self.pipe, self.chains
-        ch._stage_b(P['f64'][p], P['feat'][p], P['off1'][p], None, None, None, None)
+        ch._stage_b(P['f2'][p][0], P['f2'][p][1], P['off1'][p], None, None, None)
         m1, m2 = ch.last_meshes                                  # [2,1,7,9,2]: stream 0 = pair (1,2), stream 1 = pair (2,3)
         hr = P['hr'][p]
         imgs = None if hr is None else [hr[0:1], hr[1:2], hr[2:3]]
@@ -2312,7 +2259,7 @@ class HostFrameStream:
         """Upload one group of the source's items (batch=1: one item, into slots of the item's own shape; else up to `batch` items
         into slots [batch,...] per view) -> (slot, items in it, the upload's end event)."""
         st = self.st
-        lead = (st.S,) if hasattr(st, 'S') else ()
+        lead = (st.S,) if isinstance(st, MultiOnlineStitcher) else ()      # (S streams: every view's frames carry a stream axis)
         shape = lead + ((st.h // 2 * 3, st.w) if self.frame_format == 'nv12' else (st.h, st.w, 3))
         items = []
         for frames in group:

@@ -422,6 +422,75 @@ def test_multi_stream_of_one_equals_single_stream(dev, hip_nets):
             assert torch.equal(fa, fb), t
 
 
+def _pushes_of_one_stream(dev, n=10, h=360, w=480, seed=9):
+    """The n pushes of one stream as MultiOnlineStitcher(streams=1) takes them ([1,3,H,W] per view): window fill, capture, replays."""
+    hr, lr = _stream_inputs(1, n, h, w, dev, seeds=[seed])
+    return [[hr[0][:, t].contiguous(), hr[1][:, t].contiguous(), lr[0][:, t].contiguous(), lr[1][:, t].contiguous()] for t in range(n)]
+
+
+def test_pipelined_multi_stream_of_one_equals_pipelined_single_stream(dev, hip_nets):
+    """With two pushes in flight too: PipelinedMultiOnlineStitcher(streams=1) hands out PipelinedOnlineStitcher's frames, bit for bit,
+    at every push and at flush()."""
+    from stabstitch2_amd.online import PipelinedMultiOnlineStitcher, PipelinedOnlineStitcher
+    h, w = 360, 480
+    a, b = PipelinedMultiOnlineStitcher(hip_nets, h, w, streams=1), PipelinedOnlineStitcher(hip_nets, h, w)
+    got = [(a.push(*x)[0], b.push(*x)) for x in _pushes_of_one_stream(dev)] + [(a.flush()[0], b.flush())]
+    assert [len(gb) for _, gb in got] == [0] * 6 + [7, 0] + [1] * 3        # (one push of lag behind the first window)
+    for t, (ga, gb) in enumerate(got):
+        assert len(ga) == len(gb), t
+        for fa, fb in zip(ga, gb):
+            assert torch.equal(fa, fb), t
+
+
+def test_multi_stream_of_one_push_u8_equals_single_stream(dev, hip_nets):
+    """MultiOnlineStitcher(streams=1).push_u8 against OnlineStitcher.push_u8 on the same decoded frames: byte-equal video frames."""
+    from stabstitch2_amd.online import MultiOnlineStitcher, OnlineStitcher
+    h, w = 360, 480
+    a, b = MultiOnlineStitcher(hip_nets, h, w, streams=1), OnlineStitcher(hip_nets, h, w)
+    frames = 0
+    for t, x in enumerate(_pushes_of_one_stream(dev)):
+        u8 = [f.clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous() for f in x[:2]]        # [1,H,W,3]
+        ga, gb = a.push_u8(*u8)[0], b.push_u8(u8[0][0], u8[1][0])
+        assert len(ga) == len(gb), t
+        for fa, fb in zip(ga, gb):
+            assert fa.dtype == torch.uint8 and torch.equal(fa, fb), t
+        frames += len(gb)
+    assert frames == 10
+
+
+@pytest.mark.parametrize('use_graph', [True, False])
+def test_multi_stream_of_one_meshes_equal_single_stream(dev, hip_nets, use_graph):
+    """meshes_only: MultiOnlineStitcher(streams=1) returns OnlineStitcher's smoothed meshes with a stream axis in front, bit for bit,
+    captured and eager."""
+    from stabstitch2_amd.online import MultiOnlineStitcher, OnlineStitcher
+    h, w = 360, 480
+    a = MultiOnlineStitcher(hip_nets, h, w, streams=1, meshes_only=True, use_graph=use_graph)
+    b = OnlineStitcher(hip_nets, h, w, meshes_only=True, use_graph=use_graph)
+    for t, x in enumerate(_pushes_of_one_stream(dev)):
+        ga, gb = a.push(None, None, x[2], x[3]), b.push(None, None, x[2], x[3])
+        assert (ga is None) == (gb is None) == (t < 6), t
+        if gb is not None:
+            k = 7 if t == 6 else 1
+            for ma, mb in zip(ga, gb):
+                assert tuple(ma.shape) == (1, k, 7, 9, 2) and tuple(mb.shape) == (k, 7, 9, 2) and torch.equal(ma[0], mb), t
+
+
+def test_pipelined_multi_stream_of_one_reports_as_the_plain_stitchers(dev, hip_nets):
+    """After the same ten pushes PipelinedMultiOnlineStitcher(streams=1) reads the same overflow_report() and canvas_box as the plain
+    stitchers: MultiOnlineStitcher(streams=1)'s lists, whose one entry is OnlineStitcher's."""
+    from stabstitch2_amd.online import MultiOnlineStitcher, OnlineStitcher, PipelinedMultiOnlineStitcher
+    h, w = 360, 480
+    p, m, o = (PipelinedMultiOnlineStitcher(hip_nets, h, w, streams=1), MultiOnlineStitcher(hip_nets, h, w, streams=1),
+               OnlineStitcher(hip_nets, h, w))
+    for x in _pushes_of_one_stream(dev):
+        p.push(*x), m.push(*x), o.push(*x)
+    want = o.overflow_report()
+    assert want['frames_seen'] == 10 and want['box'] is not None
+    assert p.overflow_report() == m.overflow_report() == [want]
+    assert p.canvas_box == m.canvas_box == [o.canvas_box]
+    p.flush()
+
+
 def test_multi_stream_shared_canvas_size_renders_as_one_clip(dev, hip_nets):
     """Streams whose canvases have one size (the caller fixed them) render in ONE launch per push (the S current frames are a
     clip): same bytes as the per-stream launches of single-stream stitchers with the same canvases' inputs."""
