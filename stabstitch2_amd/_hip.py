@@ -15,6 +15,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SIGNATURES, and has lib() and call().  The build, its surface check and the tests go over this list ("Adding a native
 # library").
 LIBRARIES = ('_hip', '_blend', '_seam', '_mbwarp', '_surfaces')
+# Libraries behind a path that the five above also cover (the same description, the same loader and launch path): the build and its
+# surface check go over them too.  _smoothtail: SmoothNet's Conv3d stack of a stitched clip.
+EXTRA_LIBRARIES = ('_smoothtail',)
 
 LIB_PATH = os.path.join(_HERE, 'libstabstitch_hip.so')
 HEADER, API, PREFIX = 'stabstitch_hip.h', 'SS_API', 'ss_'

@@ -10,7 +10,7 @@ import ctypes
 import torch
 
 from . import _hip as H
-from . import _blend as B, _mbwarp as W, _seam as S, _surfaces as F
+from . import _blend as B, _mbwarp as W, _seam as S, _smoothtail as ST, _surfaces as F
 
 
 def _f(t):
@@ -1806,3 +1806,60 @@ def smooth_stitch(sm1, sm2, ts1, ts2, delta, nw, t, want_paths=True):
            H.dptr(outs['ori_mesh1']), H.dptr(outs['ori_mesh2']), H.dptr(outs['smooth_mesh1']), H.dptr(outs['smooth_mesh2']),
            H.dptr(outs.get('ori_path2'), True), H.dptr(outs.get('smooth_path2'), True), nw, t, H.stream())
     return outs
+
+
+# ------------------------------------------------------------------ SmoothNet of a stitched clip (libstabstitch_smoothtail.so)
+SMOOTH_TAIL = os.environ.get('SS_SMOOTH_TAIL', '1') == '1'      # '0': smooth_stage runs every frame of every window on the conv engine
+SMOOTH_TAIL_FRAMES = ((0, 2), (2, 4), (4, 6))                   # (first_in, first_out) of the three Conv3d layers, window k >= 1
+
+
+def smooth_tail_usable(nw, t):
+    """Does pipeline.smooth_stage take the clip-only path for `nw` windows of `t` frames?  Not under the deterministic policy (it
+    promises clip == stream bit for bit and the stream keeps the conv engine's kernels), only for the 7-frame window the kernels are
+    written for, and only up to one launch's windows."""
+    return SMOOTH_TAIL and not is_deterministic() and t == 7 and 0 < nw <= ST.MAX_WINDOWS
+
+
+def smooth_tail_seg_tiles(nw):
+    """The K tiles of one partial sum: the cut ss_conv_nhwc makes for [nw,7,7,9,128] x Conv3d(128,128,(5,3,3)), so that the clip-only
+    layers add up what the full windows would, bit for bit (ss_conv_workspace_need = splits * M * cout floats, 0 without a cut)."""
+    need = _conv_ws_need(nw, 7, 7, 9, 128, 128, 5, 3, 3, 1, 2, 1, 1, 1)
+    splits = max(1, need // (nw * 7 * 63 * 128))
+    return -(-ST.K_TILES // splits)
+
+
+def smooth_tail_layer(x, wgt, bias, nw, first_in, first_out, seg_tiles=None):
+    """One ragged Conv3d(128,128,(5,3,3)) + bias + ReLU (sst_conv3d_layer): x compact [frames_in,63,128] (window 0: 7 frames, later
+    windows frames first_in..6; first_in = 0 is ss_smooth_embed's [nw,7,7,9,128]) -> compact [frames_out,63,128]."""
+    if seg_tiles is None:
+        seg_tiles = smooth_tail_seg_tiles(nw)
+    frames_in, frames_out = 7 + (nw - 1) * (7 - first_in), 7 + (nw - 1) * (7 - first_out)
+    if x.numel() != frames_in * 63 * 128 or tuple(wgt.shape) != (128, 5, 3, 3, 128):
+        raise ValueError('smooth_tail_layer: %s / %s do not match %d windows from frame %d' % (tuple(x.shape), tuple(wgt.shape), nw, first_in))
+    out = torch.empty((frames_out, 63, 128), device=x.device, dtype=torch.float32)
+    nseg = -(-ST.K_TILES // max(1, seg_tiles))
+    ws = torch.empty(nseg * out.numel(), device=x.device, dtype=torch.float32) if nseg > 1 else None
+    ST.call('sst_conv3d_layer', H.dptr(x), H.dptr(wgt), H.dptr(bias, True), H.dptr(out), H.dptr(ws, True),
+            0 if ws is None else ws.numel(), nw, first_in, first_out, seg_tiles, H.stream())
+    return out
+
+
+def smooth_tail_decode(hid, w, b, delta, nw, first=6):
+    """Linear(128,4) on compact rows, scattered into delta [nw,7,7,9,4] where ss_smooth_stitch reads (sst_decode_scatter); the
+    rest of delta stays as it is."""
+    if hid.numel() != (7 + (nw - 1) * (7 - first)) * 63 * 128 or delta.numel() != nw * 7 * 63 * 4 or tuple(w.shape) != (4, 128):
+        raise ValueError('smooth_tail_decode: %s / %s do not match %d windows from frame %d' % (tuple(hid.shape), tuple(delta.shape), nw, first))
+    ST.call('sst_decode_scatter', H.dptr(hid), H.dptr(w), H.dptr(b, True), H.dptr(delta), nw, first, H.stream())
+    return delta
+
+
+def smooth_tail_deltas(hid, convs, dec, nw, out=None):
+    """SmoothNet behind the embedding for a stitched clip: hid [nw,7,7,9,128] (ss_smooth_embed), convs: the three packed
+    (weight, bias) pairs, dec: the packed decoder -> delta [nw,7,7,9,4], written at window 0's frames and at frame 6 of every later
+    window (what ss_smooth_stitch reads; the other entries are never written).  Same launches as the conv engine takes."""
+    if out is None:
+        out = torch.empty((nw, 7, 7, 9, 4), device=hid.device, dtype=torch.float32)
+    seg_tiles = smooth_tail_seg_tiles(nw)
+    for (w, b), (first_in, first_out) in zip(convs, SMOOTH_TAIL_FRAMES):
+        hid = smooth_tail_layer(hid, w, b, nw, first_in, first_out, seg_tiles)
+    return smooth_tail_decode(hid, dec[0], dec[1], out, nw)

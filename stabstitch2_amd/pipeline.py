@@ -322,7 +322,12 @@ def smooth_stage(smooth_net, s1, s2, t1, t2):
     smesh1, tsm1 = ops.tsmotion(s1, t1, LR_H, LR_W)
     smesh2, tsm2 = ops.tsmotion(s2, t2, LR_H, LR_W)
     nw = n - (WINDOW - 1)
-    delta = smooth_net.window_deltas(smesh1, smesh2, tsm1, tsm2, nw, WINDOW, 1, 1)
+    from . import smooth_network
+    if ops.smooth_tail_usable(nw, WINDOW) and nw <= smooth_network.WINDOW_CHUNK:
+        # only what the stitch below reads: window 0, and frame 6 of every later window (SS_SMOOTH_TAIL=0: all of every window)
+        delta = smooth_net.clip_deltas(smesh1, smesh2, tsm1, tsm2, nw)
+    else:
+        delta = smooth_net.window_deltas(smesh1, smesh2, tsm1, tsm2, nw, WINDOW, 1, 1)
     out = ops.smooth_stitch(smesh1, smesh2, tsm1, tsm2, delta, nw, WINDOW)
     out['smotion1'], out['smotion2'], out['tmotion1'], out['tmotion2'] = s1, s2, t1, t2
     out['tsmotion1'], out['tsmotion2'] = tsm1, tsm2

@@ -61,6 +61,15 @@ class SmoothNet(L.PreparedMixin, nn.Module):
         return out
 
     @torch.no_grad()
+    def clip_deltas(self, smesh1, smesh2, ts1, ts2, nw):
+        """window_deltas(..., nw, 7, 1, 1) for a clip that is stitched from its windows (ops.smooth_stitch): the decoder output of
+        window 0 and of frame 6 of every later window, equal to window_deltas' there bit for bit; the other entries of
+        delta [nw,7,7,9,4] are never written, and the Conv3d layers compute only the frames those read (ops.smooth_tail_deltas)."""
+        p = self._prepared()
+        hid = ops.smooth_embed(smesh1, smesh2, ts1, ts2, p['e1'][0], p['e1'][1], p['e3'][0], p['e3'][1], nw, 7, 1, 1)
+        return ops.smooth_tail_deltas(hid, p['conv'], p['dec'], nw)
+
+    @torch.no_grad()
     def run_windows(self, smesh1, smesh2, ts1, ts2, nw, t, wstride, zero_first):
         """-> (dict of the 8 build_SmoothNet tensors, each [nw,t,7,9,2]; decoder output [nw,t,7,9,4])."""
         delta = self.window_deltas(smesh1, smesh2, ts1, ts2, nw, t, wstride, zero_first)
