@@ -900,6 +900,19 @@ def exposure_state(device):
     return st
 
 
+def _clip_views(views, u8=None):
+    """The views of one launch, all alike: decoded uint8 frames [n,h,w,3] or fp32 planes [n,3,h,w] (u8: which; default: what the
+    first view's type says) -> (n, h, w, u8)."""
+    if u8 is None:
+        u8 = views[0].dtype == torch.uint8
+    if u8:
+        n, h, w, _ = views[0].shape
+    else:
+        n, _, h, w = views[0].shape
+    assert all(tuple(t.shape) == ((n, h, w, 3) if u8 else (n, 3, h, w)) for t in views)
+    return n, h, w, u8
+
+
 def exposure_update(views, footprint, hc, wc, state, params=None, mode='NORMAL', gains=None, want_diag=False):
     """Exposure gains of n consecutive frames of a stream, smoothed through each of them: views = list of 2|3 contiguous device
     tensors [n,3,h,w] fp32 (0..255) or [n,h,w,3] uint8 (a single frame may come without the n axis); footprint [n, ss_render_footprint_floats]
@@ -909,14 +922,8 @@ def exposure_update(views, footprint, hc, wc, state, params=None, mode='NORMAL',
     host synchronisation.  Bit-identical to n single-frame calls."""
     p = ExposureParams() if params is None else params
     v = len(views)
-    u8 = views[0].dtype == torch.uint8
     views = [t if t.dim() == 4 else t[None] for t in views]
-    if u8:
-        n, h, w, _ = views[0].shape
-        assert all(tuple(t.shape) == (n, h, w, 3) for t in views)
-    else:
-        n, _, h, w = views[0].shape
-        assert all(tuple(t.shape) == (n, 3, h, w) for t in views)
+    n, h, w, u8 = _clip_views(views)
     fp = footprint if footprint.dim() == 2 else footprint[None]
     assert fp.shape[0] == n and fp.stride(1) == 1 and tuple(state.shape) == (12,)
     if gains is None:
@@ -949,9 +956,11 @@ def _render_average(views, source, T, hc, wc, mode, out, footprint, gains, u8, c
     if not u8 and not clip:
         views = [_f(i) for i in views]
     h, w = views[0].shape[-3:-1] if u8 else views[0].shape[-2:]
-    n = views[0].shape[0] if clip else 1
+    n = 1
     if clip:
-        assert all(tuple(t.shape) == ((n, h, w, 3) if u8 else (n, 3, h, w)) for t in views) and source.shape[0] == n and T.shape[0] == n
+        assert views[0].dim() == 4
+        n, h, w, _ = _clip_views(views, u8)
+        assert source.shape[0] == n and T.shape[0] == n
     arr = H.ptr_array(views, dtype=dt)
     shape = ((n,) if clip else ()) + ((hc, wc, 3) if u8 else (3, hc, wc))
     if out is None:
@@ -1241,13 +1250,7 @@ def render_linear_clip(views, source, T, hc, wc, mode='NORMAL', out=None, want_m
     want_masks: also return the blender's mask1 of every pass [n,V-1,hc,wc].  Bit-identical to the per-frame chain
     tps_warp_views + linear_blend (+ mask_union + linear_blend)."""
     v = len(views)
-    u8 = views[0].dtype == torch.uint8
-    if u8:
-        n, h, w, _ = views[0].shape
-        assert all(tuple(t.shape) == (n, h, w, 3) for t in views)
-    else:
-        n, _, h, w = views[0].shape
-        assert all(tuple(t.shape) == (n, 3, h, w) for t in views)
+    n, h, w, u8 = _clip_views(views)
     assert source.shape[0] == n and T.shape[0] == n
     dev = views[0].device
     arr = H.ptr_array(views, dtype=torch.uint8 if u8 else torch.float32)
@@ -1283,13 +1286,7 @@ def render_linear_frames(views, source, T, sizes, mode='NORMAL', outs=None, ws=N
     ws: linear_frames_workspace(sizes, V, device).  Bit-identical, frame by frame, to render_linear_clip called with that one
     frame on that canvas."""
     v = len(views)
-    u8 = views[0].dtype == torch.uint8
-    if u8:
-        n, h, w, _ = views[0].shape
-        assert all(tuple(t.shape) == (n, h, w, 3) for t in views)
-    else:
-        n, _, h, w = views[0].shape
-        assert all(tuple(t.shape) == (n, 3, h, w) for t in views)
+    n, h, w, u8 = _clip_views(views)
     assert source.shape[0] == n and T.shape[0] == n and len(sizes) == n
     dev, dt = views[0].device, views[0].dtype
     sizes = [(int(a), int(b)) for a, b in sizes]

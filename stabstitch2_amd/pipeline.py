@@ -20,6 +20,7 @@ Long videos: `run_two_view_long` keeps the reference's ONE global canvas (test_o
 memory -- pass 1 estimates the meshes chunk by chunk from the LR frames only, pass 2 renders chunk by chunk onto the
 shared canvas.
 """
+import collections
 import glob
 import os
 
@@ -495,15 +496,6 @@ LINEAR_CLIP = os.environ.get('SS_LINEAR_CLIP', '1') == '1'
 LINEAR_CLIP_FRAMES = int(os.environ.get('SS_LINEAR_CLIP_FRAMES', '64'))     # frames per launch group (workspace: 44 MB per 720p frame and view)
 
 
-def _linear_clip(clips, src, T, hc, wc, warp_mode, out, gains=None):
-    n = src.shape[0]
-    for s in range(0, n, LINEAR_CLIP_FRAMES):
-        e = min(s + LINEAR_CLIP_FRAMES, n)
-        ops.render_linear_clip([c[s:e] for c in clips], src[s:e], T[s:e], hc, wc, warp_mode, out=out[s:e],
-                               gains=None if gains is None else gains[s:e])
-    return out
-
-
 # MULTIBAND fusion (ops.render_multiband): frames per call -- the warped planes and the pyramids of one 720p frame are about 160 MB
 MULTIBAND_FRAMES = 8
 
@@ -540,69 +532,79 @@ def exposure_params(exposure, exposure_state=None):
     return exposure
 
 
-def _multiband_frames(img_lists, src, T, hc, wc, warp_mode, bands, out, dev, seam=None, seam_state=None, gains=None):
-    """Clips held as tensors go in chunks of MULTIBAND_FRAMES frames (the launches of one frame each), lists frame by frame.
-    seam: seam_options(); with the DP seam one state (seam_state, or a fresh one) is carried from chunk to chunk, so that a clip equals
-    its frames rendered one by one.  gains [n,V,3] (clips only: _exposed_frames takes lists itself): ops.render_multiband's."""
-    n = src.shape[0]
+def _seam_kw(seam, views, hc, wc, dev, seam_state=None):
+    """seam_options() -> ops.render_multiband's seam keywords on a hc x wc canvas ({} for the geometric seam): the cell settled, and ONE
+    state (seam_state, or a fresh one) for every chunk and frame that follows, so that a clip equals its frames rendered one by one."""
     seam = dict(seam or {})
     if seam:
         seam['seam_cell'] = ops.seam_cell(hc, wc, seam['seam_cell'])
-        seam['seam_state'] = ops.seam_state(len(img_lists), hc, wc, seam['seam_cell'], dev) if seam_state is None else seam_state
-    clips = [_as_clip(x, n) for x in img_lists]
-    if all(c is not None for c in clips):
-        for s in range(0, n, MULTIBAND_FRAMES):
-            e = min(s + MULTIBAND_FRAMES, n)
-            more = {} if gains is None else {'gains': gains[s:e]}
-            ops.render_multiband([c[s:e] for c in clips], src[s:e], T[s:e], hc, wc, warp_mode, bands, out=out[s:e], **seam, **more)
-        return out
-    assert gains is None
-    for i in range(n):
-        ops.render_multiband([x[i].to(dev, non_blocking=True) for x in img_lists], src[i], T[i], hc, wc, warp_mode, bands, out=out[i],
-                             u8=False, **seam)
-    return out
+        seam['seam_state'] = ops.seam_state(views, hc, wc, seam['seam_cell'], dev) if seam_state is None else seam_state
+    return seam
 
 
-def _exposed_frames(img_lists, src, T, img_h, img_w, hc, wc, warp_mode, fusion_mode, bands, out, dev, seam, seam_state, params, state):
-    """render_frames with exposure compensation: the clip's footprints (the estimator's sample lattice, whatever the fusion mode and
-    SKIP_OUTSIDE -- tile skipping stays SKIP_OUTSIDE's), the gains of ops.exposure_update on the frames the render reads with ONE
-    state run through the clip in order (`state`, or a fresh one), then the render each case has with gains=.  Clips held as tensors:
-    one update for all n frames; lists: one per frame with that frame's footprint row (bit-identical either way)."""
-    n, v = src.shape[0], len(img_lists)
-    fp = ops.render_footprints(src, T, img_h, img_w, hc, wc)
-    st = ops.exposure_state(dev) if state is None else state
-    fused = ops.fused_render(fusion_mode)
+# what a clip render is asked for: uint8 clips to uint8 frames or fp32, warp and fusion mode, MULTIBAND's bands, seam_options() with the
+# caller's state, exposure_params() with the caller's
+_RenderOpt = collections.namedtuple('_RenderOpt', 'u8 warp fusion bands seam seam_state exposure exposure_state')
+
+
+def _render_clip(views, src, T, img_h, img_w, hc, wc, out, dev, opt):
+    """How a fusion mode renders a clip: the route table of DESIGN.md 7k, the only place that decides it.  views: V clips or lists
+    of frames; out: fp32 [n,3,hc,wc], or with opt.u8 uint8 [n,hc,wc,3] for decoded uint8 clips [n,h,w,3]; opt: a _RenderOpt.  One
+    exposure state and one seam state run through the frames in order, whichever route they take."""
+    n, v, u8 = src.shape[0], len(views), opt.u8
+    fused = ops.fused_render(opt.fusion)                 # AVERAGE | FEATHER: the one-launch render, the formula its `fusion`
+    # footprints: the exposure estimator's sample lattice whatever the mode, and the fused render's tile skipping (SKIP_OUTSIDE's alone)
+    fp = ops.render_footprints(src, T, img_h, img_w, hc, wc) if (opt.exposure is not None or (SKIP_OUTSIDE and fused)) else None
     skip = fp if (SKIP_OUTSIDE and fused) else None
-    clips = [_as_clip(x, n) for x in img_lists]
-    if all(c is not None for c in clips):
-        gains = ops.exposure_update(clips, fp, hc, wc, st, params, warp_mode)
-        if fused:
-            ops.render_average_clip(clips, src, T, hc, wc, warp_mode, out=out, footprint=skip, gains=gains, fusion=fusion_mode)
-        elif fusion_mode == 'MULTIBAND':
-            _multiband_frames(clips, src, T, hc, wc, warp_mode, bands, out, dev, seam, seam_state, gains=gains)
-        elif LINEAR_CLIP:
-            _linear_clip(clips, src, T, hc, wc, warp_mode, out, gains=gains)
-        else:                                # the per-frame chain has no gains: the ragged-canvas render at n = 1, as the stitcher does
+    seam = _seam_kw(opt.seam, v, hc, wc, dev, opt.seam_state)
+    st = opt.exposure_state
+    if opt.exposure is not None and st is None:
+        st = ops.exposure_state(dev)
+    clips = [f.contiguous() for f in views] if u8 else [_as_clip(x, n) for x in views]
+    if all(c is not None for c in clips):                # views held as contiguous clip tensors: ONE update for all n frames
+        gains = None if opt.exposure is None else ops.exposure_update(clips, fp, hc, wc, st, opt.exposure, opt.warp)
+        if fused or (u8 and opt.fusion != 'LINEAR'):     # (uint8 has no MULTIBAND: the fused render's ValueError)
+            render = ops.render_average_clip_u8 if u8 else ops.render_average_clip
+            render(clips, src, T, hc, wc, opt.warp, out=out, footprint=skip, gains=gains, fusion=opt.fusion)
+            return
+        if opt.fusion == 'MULTIBAND':
+            for s in range(0, n, MULTIBAND_FRAMES):
+                e = min(s + MULTIBAND_FRAMES, n)
+                ops.render_multiband([c[s:e] for c in clips], src[s:e], T[s:e], hc, wc, opt.warp, opt.bands, out=out[s:e],
+                                     gains=None if gains is None else gains[s:e], **seam)
+            return
+        # any other name renders as LINEAR, as the reference's `else` does -- without gains only 'LINEAR' itself through the clip render
+        if u8 or (LINEAR_CLIP and (opt.fusion == 'LINEAR' or gains is not None)):
+            for s in range(0, n, LINEAR_CLIP_FRAMES):
+                e = min(s + LINEAR_CLIP_FRAMES, n)
+                ops.render_linear_clip([c[s:e] for c in clips], src[s:e], T[s:e], hc, wc, opt.warp, out=out[s:e],
+                                       gains=None if gains is None else gains[s:e])
+            return
+        if gains is not None:                            # the per-frame chain has no gains: the ragged-canvas render at n = 1, as the stitcher does
             for i in range(n):
-                ops.render_linear_frames([c[i:i + 1] for c in clips], src[i:i + 1], T[i:i + 1], [(hc, wc)], warp_mode, outs=[out[i]],
+                ops.render_linear_frames([c[i:i + 1] for c in clips], src[i:i + 1], T[i:i + 1], [(hc, wc)], opt.warp, outs=[out[i]],
                                          gains=gains[i:i + 1])
-        return out
-    seam = dict(seam or {})
-    if seam:
-        seam['seam_cell'] = ops.seam_cell(hc, wc, seam['seam_cell'])
-        seam['seam_state'] = ops.seam_state(v, hc, wc, seam['seam_cell'], dev) if seam_state is None else seam_state
-    for i in range(n):
-        imgs = [ops._f(img_lists[k][i].to(dev, non_blocking=True)) for k in range(v)]
-        imgs = [t if t.dim() == 4 else t[None] for t in imgs]
-        gains = ops.exposure_update(imgs, fp[i], hc, wc, st, params, warp_mode)
+            return
+    for i in range(n):                                 # lists of separate frames (and LINEAR without its clip render or gains)
+        imgs = [views[k][i].to(dev, non_blocking=True) for k in range(v)]
+        gains = None
+        if opt.exposure is not None:                     # the update and the render read the same uploaded planes [1,3,h,w]
+            imgs = [t if t.dim() == 4 else t[None] for t in map(ops._f, imgs)]
+            gains = ops.exposure_update(imgs, fp[i], hc, wc, st, opt.exposure, opt.warp)
         if fused:
-            ops.render_average(imgs, src[i], T[i], hc, wc, warp_mode, out=out[i], footprint=None if skip is None else skip[i],
-                               gains=gains, fusion=fusion_mode)
-        elif fusion_mode == 'MULTIBAND':
-            ops.render_multiband(imgs, src[i], T[i], hc, wc, warp_mode, bands, out=out[i], u8=False, gains=gains, **seam)
+            ops.render_average(imgs, src[i], T[i], hc, wc, opt.warp, out=out[i], footprint=None if skip is None else skip[i],
+                               gains=gains, fusion=opt.fusion)
+        elif opt.fusion == 'MULTIBAND':
+            ops.render_multiband(imgs, src[i], T[i], hc, wc, opt.warp, opt.bands, out=out[i], u8=False, gains=gains, **seam)
+        elif gains is not None:
+            ops.render_linear_frames(imgs, src[i:i + 1], T[i:i + 1], [(hc, wc)], opt.warp, outs=[out[i]], gains=gains)
         else:
-            ops.render_linear_frames(imgs, src[i:i + 1], T[i:i + 1], [(hc, wc)], warp_mode, outs=[out[i]], gains=gains)
-    return out
+            w = ops.tps_warp_views(imgs, src[i], T[i], hc, wc, opt.warp)              # [V,4,Hc,Wc]
+            if v == 2:
+                ops.linear_blend(w[0, 0:3], w[1, 0:3], w[0, 3], w[1, 3], out=out[i])
+            else:
+                f = ops.linear_blend(w[0, 0:3], w[1, 0:3], w[0, 3], w[1, 3])
+                ops.linear_blend(f, w[2, 0:3], ops.mask_union(w[0, 3], w[1, 3]), w[2, 3], out=out[i])
 
 
 @torch.no_grad()
@@ -610,14 +612,13 @@ def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', 
                   size=None, bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, seam_state=None, exposure=None,
                   exposure_state=None):
     """img_lists: V lists (or tensors [N,3,H,W]) of HR frames (0..255); meshes: V tensors [1,N,7,9,2].
-    -> (frames [N,3,Hc,Wc] device tensor, Hc, Wc).  AVERAGE and FEATHER fusion of clips held as tensors is ONE launch for the whole
-    clip (ops.render_average_clip); lists of separate frames and LINEAR fusion go frame by frame.
+    -> (frames [N,3,Hc,Wc] device tensor, Hc, Wc).  Which launches render which fusion mode, for clips held as tensors and for lists
+    of separate frames: _render_clip, the route table of DESIGN.md 7k.
     With SKIP_OUTSIDE (default) a view contributes exactly 0 on canvas tiles it cannot reach, where the reference's
     clamped sampler leaves a rounding residue of <~ 1e-2 grey levels (ops.render_average).
-    MULTIBAND fusion (bands= pyramid levels, default ops.MULTIBAND_BANDS): one warp launch and the pyramid launches per chunk of
-    MULTIBAND_FRAMES frames of a clip, or per frame of a list (ops.render_multiband).  seam='dp' (MULTIBAND only; seam_cell=, seam_mu=,
-    seam_prior=: ops.multiband_seam) puts the content-aware seam between the warp and the blend; its temporal state runs through the
-    whole clip (seam_state: an ops.seam_state to continue from and leave behind, for a video rendered in several calls).
+    bands: MULTIBAND's pyramid levels (default ops.MULTIBAND_BANDS).  seam='dp' (MULTIBAND only; seam_cell=, seam_mu=, seam_prior=:
+    ops.multiband_seam) puts the content-aware seam between the warp and the blend; its temporal state runs through the whole clip
+    (seam_state: an ops.seam_state to continue from and leave behind, for a video rendered in several calls).
     exposure (None | True | ops.ExposureParams): exposure compensation in every fusion mode -- per frame, view and channel the gains of
     ops.exposure_update on the clip's footprints, smoothed through the clip in order, scale the sampled colours (min(g * s, 255)); for
     MULTIBAND in the warp, in front of the seam and the blend.  exposure_state: an ops.exposure_state to continue from and leave
@@ -627,43 +628,15 @@ def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', 
     if seam_state is not None and not seam:
         raise ValueError("seam_state= belongs to seam='dp'")
     exposure = exposure_params(exposure, exposure_state)
-    v = len(img_lists)
     dev = meshes[0].device
     n = meshes[0].shape[1]
-    first = img_lists[0][0]
-    img_h, img_w = first.shape[-2:]
+    img_h, img_w = img_lists[0][0].shape[-2:]
     hc, wc, src, T = render_plan(meshes, img_h, img_w, prescaled, bbox, size)
     if out is None or tuple(out.shape) != (n, 3, hc, wc) or not out.is_contiguous():
         out = torch.empty((n, 3, hc, wc), device=dev, dtype=torch.float32)      # (a buffer of another canvas is not reused)
-    if exposure is not None:
-        _exposed_frames(img_lists, src, T, img_h, img_w, hc, wc, warp_mode, fusion_mode, ops.MULTIBAND_BANDS if bands is None else bands,
-                        out, dev, seam, seam_state, exposure, exposure_state)
-        return out, hc, wc
-    if fusion_mode == 'MULTIBAND':
-        _multiband_frames(img_lists, src, T, hc, wc, warp_mode, ops.MULTIBAND_BANDS if bands is None else bands, out, dev, seam,
-                          seam_state)
-        return out, hc, wc
-    fused = ops.fused_render(fusion_mode)                # AVERAGE | FEATHER: the one-launch render, the formula its `fusion`
-    fp = ops.render_footprints(src, T, img_h, img_w, hc, wc) if (SKIP_OUTSIDE and fused) else None
-    clips = [_as_clip(x, n) for x in img_lists]
-    if fused and all(c is not None for c in clips):
-        ops.render_average_clip(clips, src, T, hc, wc, warp_mode, out=out, footprint=fp, fusion=fusion_mode)
-        return out, hc, wc
-    if fusion_mode == 'LINEAR' and LINEAR_CLIP and all(c is not None for c in clips):
-        _linear_clip(clips, src, T, hc, wc, warp_mode, out)
-        return out, hc, wc
-    for i in range(n):
-        imgs = [img_lists[k][i].to(dev, non_blocking=True) for k in range(v)]
-        if fused:
-            ops.render_average(imgs, src[i], T[i], hc, wc, warp_mode, out=out[i], footprint=None if fp is None else fp[i],
-                               fusion=fusion_mode)
-        else:
-            w = ops.tps_warp_views(imgs, src[i], T[i], hc, wc, warp_mode)            # [V,4,Hc,Wc]
-            if v == 2:
-                ops.linear_blend(w[0, 0:3], w[1, 0:3], w[0, 3], w[1, 3], out=out[i])
-            else:
-                f = ops.linear_blend(w[0, 0:3], w[1, 0:3], w[0, 3], w[1, 3])
-                ops.linear_blend(f, w[2, 0:3], ops.mask_union(w[0, 3], w[1, 3]), w[2, 3], out=out[i])
+    opt = _RenderOpt(False, warp_mode, fusion_mode, ops.MULTIBAND_BANDS if bands is None else bands, seam, seam_state, exposure,
+                     exposure_state)
+    _render_clip(img_lists, src, T, img_h, img_w, hc, wc, out, dev, opt)
     return out, hc, wc
 
 
@@ -777,34 +750,20 @@ def _u8_fused(fusion_mode):
 def render_frames_u8(frame_lists, meshes, warp_mode='NORMAL', out=None, bbox=None, size=None, prescaled=False,
                      fusion_mode='AVERAGE', exposure=None, exposure_state=None):
     """frame_lists: V device tensors [N,H,W,3] uint8; meshes: V tensors [1,N,7,9,2] -> (uint8 [N,Hc,Wc,3], Hc, Wc):
-    `render_frames(..., fusion_mode)` followed by `to_video_frames`, fused: one launch for the clip (AVERAGE, FEATHER), three / four
-    (LINEAR: the warped planes are fp32 either way, the blend writes the video frame).  exposure, exposure_state: as render_frames
+    `render_frames(..., fusion_mode)` followed by `to_video_frames`, fused -- the uint8 routes of _render_clip's table (DESIGN.md 7k;
+    LINEAR: the warped planes are fp32 either way, the blend writes the video frame).  exposure, exposure_state: as render_frames
     takes them -- the gains of ops.exposure_update on the uint8 frames, into the renders' _gains entries."""
     exposure = exposure_params(exposure, exposure_state)
+    dev = meshes[0].device
     n = meshes[0].shape[1]
     img_h, img_w = frame_lists[0].shape[1], frame_lists[0].shape[2]
     hc, wc, src, T = render_plan(meshes, img_h, img_w, prescaled, bbox=bbox, size=size)
     if callable(out):                                   # a buffer provider (HostClipRunner's ring of result buffers)
         out = out((n, hc, wc, 3))
     if out is None or tuple(out.shape) != (n, hc, wc, 3) or not out.is_contiguous():
-        out = torch.empty((n, hc, wc, 3), device=meshes[0].device, dtype=torch.uint8)
-    if exposure is not None:
-        clips = [f if f.is_contiguous() else f.contiguous() for f in frame_lists]
-        fp = ops.render_footprints(src, T, img_h, img_w, hc, wc)
-        st = ops.exposure_state(meshes[0].device) if exposure_state is None else exposure_state
-        gains = ops.exposure_update(clips, fp, hc, wc, st, exposure, warp_mode)
-        if fusion_mode == 'LINEAR':
-            _linear_clip(clips, src, T, hc, wc, warp_mode, out, gains=gains)
-        else:
-            ops.render_average_clip_u8(clips, src, T, hc, wc, warp_mode, out=out, footprint=fp if SKIP_OUTSIDE else None, gains=gains,
-                                       fusion=fusion_mode)
-        return out, hc, wc
-    if fusion_mode == 'LINEAR':
-        _linear_clip([f if f.is_contiguous() else f.contiguous() for f in frame_lists], src, T, hc, wc, warp_mode, out)
-        return out, hc, wc
-    fp = ops.render_footprints(src, T, img_h, img_w, hc, wc) if SKIP_OUTSIDE else None
-    ops.render_average_clip_u8([f if f.is_contiguous() else f.contiguous() for f in frame_lists], src, T, hc, wc, warp_mode,
-                               out=out, footprint=fp, fusion=fusion_mode)
+        out = torch.empty((n, hc, wc, 3), device=dev, dtype=torch.uint8)
+    opt = _RenderOpt(True, warp_mode, fusion_mode, None, {}, None, exposure, exposure_state)
+    _render_clip(frame_lists, src, T, img_h, img_w, hc, wc, out, dev, opt)
     return out, hc, wc
 
 
@@ -812,6 +771,24 @@ def _as_device_u8(frames, device):
     if not torch.is_tensor(frames):
         frames = torch.from_numpy(frames)
     return frames.to(device, non_blocking=True).contiguous()
+
+
+def _ingest_views(u8_views, fusion_mode):
+    """Decoded uint8 clips [N,H,W,3] on the device -> (hr planes per view | None, lr frames per view): ONE ss_ingest_u8 per view.
+    None: the fused uint8 render takes this fusion mode (_u8_fused) and samples the uint8 frames themselves."""
+    want_hr = not _u8_fused(fusion_mode)
+    io = [ops.ingest_u8(f, want_hr=want_hr) for f in u8_views]
+    return ([x[0] for x in io] if want_hr else None), [x[1] for x in io]
+
+
+def _video_frames(u8_views, hrs, meshes, warp_mode, fusion_mode, out=None, bands=None, seam=None, **kw):
+    """The uint8 video frames of a uint8 clip -> (uint8 [N,Hc,Wc,3], Hc, Wc): render_frames_u8 on the frames themselves where
+    _ingest_views left no fp32 planes (hrs None), else render_frames on those planes (bands and the seam= keywords are its alone:
+    MULTIBAND is never fused) + canvas_to_u8.  out: render_frames_u8's; kw: what both renders take (prescaled, bbox, size, exposure)."""
+    if hrs is None:
+        return render_frames_u8(u8_views, meshes, warp_mode, out=out, fusion_mode=fusion_mode, **kw)
+    frames, hc, wc = render_frames(hrs, meshes, warp_mode, fusion_mode, bands=bands, **(seam or {}), **kw)
+    return ops.canvas_to_u8(frames, out=out((frames.shape[0], hc, wc, 3)) if callable(out) else out), hc, wc
 
 
 @torch.no_grad()
@@ -822,18 +799,12 @@ def run_two_view_u8(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVE
     check_fusion(fusion_mode, bands)
     seam_options(fusion_mode, **seam)        # (MULTIBAND's seam= keywords: render_frames)
     exposure = exposure_params(exposure)     # (refused before the networks run)
-    if _u8_fused(fusion_mode):
-        f1, f2 = _as_device_u8(frames1, device), _as_device_u8(frames2, device)
-        _, lr1 = ops.ingest_u8(f1, want_hr=False)
-        _, lr2 = ops.ingest_u8(f2, want_hr=False)
-        acc = estimate_meshes(nets, lr1, lr2)
-        m1, m2 = acc['smooth_mesh1'], acc['smooth_mesh2']
-        u8, hc, wc = render_frames_u8([f1, f2], [m1, m2], warp_mode, fusion_mode=fusion_mode, exposure=exposure)
-        return (u8.cpu().numpy() if to_host else u8), hc, wc, m1, m2
-    hr1, lr1 = load_frames_u8(frames1, device=device)
-    hr2, lr2 = load_frames_u8(frames2, device=device)
-    frames, hc, wc, m1, m2 = run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode, fusion_mode, bands=bands, exposure=exposure, **seam)
-    return to_video_frames(frames, to_host), hc, wc, m1, m2
+    f = [_as_device_u8(frames1, device), _as_device_u8(frames2, device)]
+    hrs, lrs = _ingest_views(f, fusion_mode)
+    acc = estimate_meshes(nets, lrs[0], lrs[1])
+    m1, m2 = acc['smooth_mesh1'], acc['smooth_mesh2']
+    u8, hc, wc = _video_frames(f, hrs, [m1, m2], warp_mode, fusion_mode, bands=bands, seam=seam, exposure=exposure)
+    return (u8.cpu().numpy() if to_host else u8), hc, wc, m1, m2
 
 
 @torch.no_grad()
@@ -846,17 +817,13 @@ def run_three_view_u8(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusio
     f = [_as_device_u8(x, device) for x in (frames1, frames2, frames3)]
     img_h, img_w = f[0].shape[1], f[0].shape[2]
     seam_options(fusion_mode, **seam)        # (MULTIBAND's seam= keywords: render_frames)
-    if _u8_fused(fusion_mode):
-        lr = [ops.ingest_u8(x, want_hr=False)[1] for x in f]
-        a12 = estimate_meshes(nets, lr[0], lr[1], keep_spatial_cache2=True)
-        a23 = estimate_meshes(nets, lr[1], lr[2], tmotion1=a12['tmotion2'], spatial_cache1=a12.get('spatial_cache2'))
-        ms = three_view_compose(a12['smooth_mesh1'], a12['smooth_mesh2'], a23['smooth_mesh1'], a23['smooth_mesh2'], img_h, img_w)
-        u8, hc, wc = render_frames_u8(f, list(ms), warp_mode, prescaled=True, fusion_mode=fusion_mode, exposure=exposure)
-        return (u8.cpu().numpy() if to_host else u8), hc, wc, ms[0], ms[1], ms[2]
-    io = [ops.ingest_u8(x) for x in f]
-    frames, hc, wc, m1, mid, m3 = run_three_view(io[0][0], io[1][0], io[2][0], io[0][1], io[1][1], io[2][1], nets, warp_mode,
-                                                 fusion_mode, bands=bands, exposure=exposure, **seam)
-    return to_video_frames(frames, to_host), hc, wc, m1, mid, m3
+    hrs, lr = _ingest_views(f, fusion_mode)
+    # the middle view's TemporalNet motions and SpatialNet trunk features are computed once and reused by pair (2,3)
+    a12 = estimate_meshes(nets, lr[0], lr[1], keep_spatial_cache2=True)
+    a23 = estimate_meshes(nets, lr[1], lr[2], tmotion1=a12['tmotion2'], spatial_cache1=a12.get('spatial_cache2'))
+    ms = three_view_compose(a12['smooth_mesh1'], a12['smooth_mesh2'], a23['smooth_mesh1'], a23['smooth_mesh2'], img_h, img_w)
+    u8, hc, wc = _video_frames(f, hrs, list(ms), warp_mode, fusion_mode, bands=bands, seam=seam, prescaled=True, exposure=exposure)
+    return (u8.cpu().numpy() if to_host else u8), hc, wc, ms[0], ms[1], ms[2]
 
 
 def io_streams(dev):
@@ -1007,17 +974,10 @@ class HostClipRunner:
     def _compute(self, d, ev):
         self.comp.wait_event(ev)
         with torch.cuda.stream(self.comp):
-            if _u8_fused(self.fusion_mode):
-                _, lr1 = ops.ingest_u8(d[0], want_hr=False)
-                _, lr2 = ops.ingest_u8(d[1], want_hr=False)
-                acc = estimate_meshes(self.nets, lr1, lr2)
-                u8, hc, wc = render_frames_u8(list(d), [acc['smooth_mesh1'], acc['smooth_mesh2']], self.warp_mode,
-                                              out=self.out_buffer, fusion_mode=self.fusion_mode)
-            else:
-                hr1, lr1 = ops.ingest_u8(d[0])
-                hr2, lr2 = ops.ingest_u8(d[1])
-                frames, hc, wc, _, _ = run_two_view(hr1, hr2, lr1, lr2, self.nets, self.warp_mode, self.fusion_mode)
-                u8 = ops.canvas_to_u8(frames, out=self.out_buffer(tuple(frames.shape[0:1]) + (hc, wc, 3)))
+            hrs, lrs = _ingest_views(d[:2], self.fusion_mode)
+            acc = estimate_meshes(self.nets, lrs[0], lrs[1])
+            u8, hc, wc = _video_frames(list(d), hrs, [acc['smooth_mesh1'], acc['smooth_mesh2']], self.warp_mode, self.fusion_mode,
+                                       out=self.out_buffer)
             ev2 = torch.cuda.Event()
             ev2.record(self.comp)
         self.consumed(d, ev2)
@@ -1178,21 +1138,14 @@ class LongVideoStitcher:
         io = self.io
         pending = None
         k = 0
-        seam = dict(self.seam)
-        if seam:                             # the seam's temporal state runs through the chunks
-            seam['seam_state'] = ops.seam_state(len(views), self.hc, self.wc, seam['seam_cell'], self.dev)
+        seam = _seam_kw(self.seam, len(views), self.hc, self.wc, self.dev)      # the seam's temporal state runs through the chunks
         for s, e, d, ev in self._uploads(views):
             io.comp.wait_event(ev)
             with torch.cuda.stream(io.comp):
                 ms = [m[:, s:e].contiguous() for m in self.meshes]
-                if _u8_fused(self.fusion_mode):
-                    u8, _, _ = render_frames_u8(list(d), ms, self.warp_mode, out=io.out_buffer, bbox=self.bbox,
-                                                size=(self.hc, self.wc), prescaled=self.prescaled, fusion_mode=self.fusion_mode)
-                else:
-                    hrs = [ops.ingest_u8(t)[0] for t in d]
-                    fr, _, _ = render_frames(hrs, ms, self.warp_mode, self.fusion_mode, prescaled=self.prescaled,
-                                             bbox=self.bbox, size=(self.hc, self.wc), bands=self.bands, **seam)
-                    u8 = ops.canvas_to_u8(fr, out=io.out_buffer((e - s, self.hc, self.wc, 3)))
+                hrs = None if _u8_fused(self.fusion_mode) else [ops.ingest_u8(t)[0] for t in d]
+                u8, _, _ = _video_frames(list(d), hrs, ms, self.warp_mode, self.fusion_mode, out=io.out_buffer, bands=self.bands, seam=seam,
+                                         prescaled=self.prescaled, bbox=self.bbox, size=(self.hc, self.wc))
                 ev2 = torch.cuda.Event()
                 ev2.record(io.comp)
             io.consumed(d, ev2)
