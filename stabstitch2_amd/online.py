@@ -28,7 +28,8 @@ own time at batch 1) disappears.  `use_graph=False` runs the same code eagerly.
 
 That step -- from the LR frames to the newest smoothed meshes -- is written once (_PairStep) for S two-view streams: OnlineStitcher
 runs it with S = 1, MultiOnlineStitcher with its S, ThreeViewOnlineStitcher through a chain of two pairs; a class adds only what
-follows the meshes (its render), and the forms with two pushes in flight (_TwoInFlight) cut the same step in two.
+follows the meshes (its render), and the forms with two pushes in flight (_TwoInFlight) cut the same step in two.  The k-frame step
+behind push_many is written once beside it (_PairStep._batch_meshes: one pair, or the two pairs of a chain of three views).
 """
 import collections
 import contextlib
@@ -934,7 +935,8 @@ class _Stitcher:
 
     # ------------------------------------------------------------------ k frames of every view per call (one canvas)
     # A subclass provides _push (one plain push), push_u8, _batch_buffers (the per-k work buffers, 'lr' [V,k,3,360,480] among
-    # them) and _step_batch (the capturable batched step, ending with _leave_batch: the _Deferred in B['deferred']).
+    # them: _PairStep's) and _step_batch (the capturable batched step: _PairStep._batch_meshes, then what follows the meshes,
+    # ending with _leave_batch: the _Deferred in B['deferred']).
     def _push_many(self, frames):
         """push_many of V views: frames = the V HR batches [k,3,H,W] then the V LR batches [k,3,360,480]."""
         k = self._check_many(frames)
@@ -1051,7 +1053,8 @@ class _PairStep:
       pair_t [2 views][zero, new][S][126]   temporal motions (slot 0 stays zero; rewritten in full by every push)
       ring   [smesh v0, smesh v1, tsm v0, tsm v1][S][7][126]     the sliding SmoothNet windows
       prev_feat [2 S,45,60,128] view-major (chain: [S+1,45,60,128])   TemporalNet stage-1 features of the previous frame
-    A class provides _init_static (the state its window fill left -> _pair_static) and _tail (what follows the meshes)."""
+    A class provides _init_static (the state its window fill left -> _pair_static) and _tail (what follows the meshes).
+    push_many's k frames per call advance the same state through `_batch_meshes` (one pair, or the pairs of a chain)."""
     S, chain = 1, False
 
     def _pair_static(self, prev_feat, pair_s, ring):
@@ -1127,6 +1130,80 @@ class _PairStep:
         r = st['ring'].view(4, S * WINDOW, 7, 9, 2)
         outs, _ = self.smooth.run_windows(r[0], r[1], r[2], r[3], S, WINDOW, WINDOW, 1)       # S windows, one per stream
         self._tail(outs['smooth_mesh1'], outs['smooth_mesh2'], hr1, hr2, out)                # [S,7,7,9,2]
+
+    # ------------------------------------------------------------------ k frames of every view per call
+    def _batch_buffers(self, k):
+        """The work buffers of `_batch_meshes` at batch size k (its docstring has their layout)."""
+        d, S, e = self.dev, self.S, 126
+        fh, fw = pipeline.LR_H // 8, pipeline.LR_W // 8
+        B = {'lr': torch.empty((S + 1, k, 3, pipeline.LR_H, pipeline.LR_W), device=d),
+             'feat': torch.empty((S + 1, k + 1, fh, fw, 128), device=d),
+             'sw': torch.empty((2, S, k + 1, e), device=d),
+             'tt': torch.zeros((2, S, k + 1, e), device=d),              # (slot 0 stays zero)
+             'ts': torch.empty((2, 2 * S * (k + 1), e), device=d),
+             'work': torch.empty((4 * S, WINDOW - 1 + k, e), device=d)}
+        if S > 1:                        # the heads' outputs [pair view][pair][k], back to back: see _batch_meshes
+            B['sn'], B['tn'] = torch.empty((2, S * k, e), device=d), torch.empty((2, S * k, e), device=d)
+        return B
+
+    def _batch_meshes(self, B):
+        """A chain of V = S + 1 views advanced by k frames from B['lr'] (capturable) -> the smoothed windows (m1, m2) [nw,7,7,9,2];
+        prev_feat, the previous motions pair_s[:, 0] and ring are read once and left as k `_step_static` runs leave them (the
+        `new` slot pair_s[:, 1], scratch of a single push, is not written).  Per frame the launches of
+        `_stage_a` / `_stage_b`, the networks seeing the k frames as one batch.  A single pair is the chain of two views: this
+        runs for OnlineStitcher (S = 1) and for ThreeViewOnlineStitcher's chains (S = 2, chain) and for nothing else --
+        independent streams times k frames would need another trunk layout.  Layout (B = _batch_buffers(k)):
+          lr   [V][k]        the views' LR frames, each view once: one trunk pass over V k images, view-major; pair (s, j) --
+                             chain s, frame j -- is images (s k + j, (s + 1) k + j) of its output
+          feat [V][k + 1]    TemporalNet's features [previous frame, the k frames]: volume (v, j) pairs slots (j, j + 1) of view
+                             v, read where they lie (ss_cost_volume_chain_frames)
+          sw, tt [2 pair views][S][k + 1][126]   spatial / temporal motions [previous | zero, the k frames] of every sequence
+          ts   [2][2 S (k + 1)][126]             tsmotion's (smesh, tsmotion) of those rows: row j pairs with row j - 1 of its
+                                                 sequence, slot 0's rows are computed and ignored
+          work [4 S][W - 1 + k][126]             the k sliding windows of ring r = q S + s, ring kind q (smesh of the first /
+                                                 second pair view, tsmotion of the first / second) <- rows 1 .. k of its sequence
+        SmoothNet runs each kind's rows as ONE run of nw windows, window w starting at row w: frame j of chain s is window
+        s (W - 1 + k) + j (the W - 1 windows that straddle two chains are computed and ignored), its mesh that window's last."""
+        st, S, k, e = self.static, self.S, B['k'], 126
+        assert (S, self.chain) in ((1, False), (2, True)), 'the k-frame step runs one pair, or the two pairs of a chain of three views'
+        F, sw, tt, ts = B['feat'], B['sw'], B['tt'], B['ts']
+        f2 = L.run_stage1_pair([B['lr'].view((S + 1) * k, 3, pipeline.LR_H, pipeline.LR_W)], self._trunk())   # [2(net), V k, 45,60,128]
+        f64 = f2[0]
+        off1 = _heads_a(self.spatial, f64, S * k, k)
+        F[:, 0].copy_(st['prev_feat'])
+        F[:, 1:].copy_(f2[1].view(F[:, 1:].shape))
+        cv_s = self.spatial.cv_from_offset1(f64[:S * k], f64[k:k + S * k], off1, pipeline.LR_H, pipeline.LR_W)
+        cv_t = ops.cost_volume_chain_frames(F, 3)                               # [2 (pair view), S, k, 45,60,52]
+        off_ref = torch.empty((S * k, e), device=self.dev, dtype=torch.float32)
+        off_tgt = torch.empty((S * k, e), device=self.dev, dtype=torch.float32)
+        # the heads write [pair view][pair][k] rows back to back.  S = 1: those are rows 1 .. k of sw[v] / tt[v], written in place;
+        # S > 1: there they are strided by pair, so sn / tn take them
+        sn, tn = (sw[:, 0, 1:], tt[:, 0, 1:]) if S == 1 else (B['sn'], B['tn'])
+        L.run_regressor_quad(cv_s, cv_t.view((2, S * k) + tuple(cv_t.shape[3:])), L.get_quad(self.spatial, self.temporal),
+                             [off_ref, off_tgt, tn[0], tn[1]])
+        st['prev_feat'].copy_(F[:, k])
+        ops.spatial_meshes(off1, off_ref, off_tgt, pipeline.LR_H, pipeline.LR_W,
+                           out=(sn[0].view(S * k, 7, 9, 2), sn[1].view(S * k, 7, 9, 2)))
+        ps = st['pair_s']                                                       # [pair view][previous, new][S][126]
+        # the previous spatial motions into slot 0 of every sequence, and the newest made the previous ones (pair_s[:, 0]; the `new`
+        # slot pair_s[:, 1], which every push writes before it reads it, stays as it is).  S = 1: ss_window_advance below carries
+        # that move (`move`); S > 1: sw and tt are put together from sn / tn, and the move is a copy
+        if S == 1:
+            sw[:, :, 0].copy_(ps[:, 0])
+            move = dict(state=ps, state_src=sw.view(-1)[k * e:], blocks=2, block=e, stride=2 * e, src_stride=(k + 1) * e)
+        else:
+            torch.cat((ps[:, 0].view(2, S, 1, e), sn.view(2, S, k, e)), 2, out=sw)
+            tt[:, :, 1:].copy_(tn.view(2, S, k, e))
+            ps[:, 0].copy_(sw[:, :, k])
+            move = {}
+        ops.tsmotion(sw.view(-1, 7, 9, 2), tt.view(-1, 7, 9, 2), pipeline.LR_H, pipeline.LR_W, out=(ts[0], ts[1]))
+        n1 = k + 1
+        offs = [((q // 2) * 2 * S * n1 + ((q % 2) * S + s) * n1 + 1) * e for q in range(4) for s in range(S)]
+        ops.window_advance(st['ring'].view(4 * S, WINDOW, e), B['work'], ts, offs, k, **move)
+        wk = B['work'].view(4, S * (WINDOW - 1 + k), 7, 9, 2)
+        nw = (S - 1) * (WINDOW - 1 + k) + k
+        outs, _ = self.smooth.run_windows(wk[0], wk[1], wk[2], wk[3], nw, WINDOW, 1, 1)
+        return outs['smooth_mesh1'], outs['smooth_mesh2']
 
 
 class OnlineStitcher(_PairStep, _Stitcher):
@@ -1341,50 +1418,11 @@ class OnlineStitcher(_PairStep, _Stitcher):
         fusion mode, seam=, viewport=, every grow and exposure= work as they do there.  Interleaves freely with the other entries."""
         return self._push_many_nv12((frames1, frames2), out)
 
-    def _batch_buffers(self, k):
-        d, e = self.dev, 126
-        fh, fw = pipeline.LR_H // 8, pipeline.LR_W // 8
-        return {'lr': torch.empty((2, k, 3, pipeline.LR_H, pipeline.LR_W), device=d),     # both views back to back
-                'feat': torch.empty((2, k + 1, fh, fw, 128), device=d),        # TemporalNet features [view][previous frame, the k frames]
-                'sw': torch.zeros((2, k + 1, e), device=d),                    # spatial motions [view][previous frame, the k frames]
-                'tt': torch.zeros((2, k + 1, e), device=d),                    # temporal motions [view][zero, the k frames]
-                'ts': torch.empty((2, 2 * (k + 1), e), device=d),              # tsmotion's (smesh, tsmotion) rows of both
-                'work': torch.empty((4, WINDOW - 1 + k, e), device=d)}         # the k sliding windows of the four rings
-
     def _step_batch(self, B):
-        """k consecutive steady-state frame pairs of the stream from B['lr'] (capturable; the state is read once and left as k
-        `_step_static` runs leave it).  Per frame the launches of `_stage_a` / `_stage_b` at batch k: TemporalNet's pair (t - 1, t)
-        is shifted by one image inside [previous frame, the k frames], tsmotion pairs each row with the one before, the k SmoothNet
-        windows slide over the UNsmoothed work rows.  Ends with the splines, the watcher and the footprints in B['deferred']."""
-        st, k, e = self.static, B['k'], 126
-        F, sw, tt, ts = B['feat'], B['sw'], B['tt'], B['ts']
-        f2 = L.run_stage1_pair([B['lr'][0], B['lr'][1]], self._trunk())          # [2(net), 2k (view-major), 45,60,128]
-        f64 = f2[0]
-        off1 = _heads_a(self.spatial, f64, k)
-        F[:, 0].copy_(st['prev_feat'])
-        F[:, 1:].copy_(f2[1].view(F[:, 1:].shape))
-        cv_s = self.spatial.cv_from_offset1(f64[:k], f64[k:], off1, pipeline.LR_H, pipeline.LR_W)
-        Ff = F.view((2 * (k + 1),) + tuple(F.shape[2:]))
-        cv_t = ops.cost_volume(Ff[:-1], Ff[1:], 3, n=2 * k, split=k, shift=1)     # volume (v, j) = (frame j - 1, frame j) of view v
-        off_ref = torch.empty((k, e), device=self.dev, dtype=torch.float32)
-        off_tgt = torch.empty((k, e), device=self.dev, dtype=torch.float32)
-        L.run_regressor_quad(cv_s, cv_t.view((2, k) + tuple(cv_t.shape[1:])), L.get_quad(self.spatial, self.temporal),
-                             [off_ref, off_tgt, tt[0, 1:], tt[1, 1:]])
-        st['prev_feat'].copy_(F[:, k])
-        ops.spatial_meshes(off1, off_ref, off_tgt, pipeline.LR_H, pipeline.LR_W,
-                           out=(sw[0, 1:].view(k, 7, 9, 2), sw[1, 1:].view(k, 7, 9, 2)))
-        sw[:, 0].copy_(st['pair_s'][:, 0, 0])
-        # tsmotion of both views as ONE batch of 2 (k + 1) rows [view][previous, the k frames]: row j pairs with row j - 1; the
-        # rows of slot 0 are computed and ignored
-        ops.tsmotion(sw.view(2 * (k + 1), 7, 9, 2), tt.view(2 * (k + 1), 7, 9, 2), pipeline.LR_H, pipeline.LR_W, out=(ts[0], ts[1]))
-        # the k windows of every ring in `work`, the rings advanced by k frames, the newest spatial motions made the previous ones
-        n1 = k + 1
-        ops.window_advance(st['ring'].view(4, WINDOW, e), B['work'], ts, [(0 * n1 + 1) * e, (1 * n1 + 1) * e, (2 * n1 + 1) * e, (3 * n1 + 1) * e], k,
-                           state=st['pair_s'], state_src=sw.view(-1)[k * e:], blocks=2, block=e, stride=2 * e, src_stride=n1 * e)
-        wk = B['work'].view(4, WINDOW - 1 + k, 7, 9, 2)
-        outs, _ = self.smooth.run_windows(wk[0], wk[1], wk[2], wk[3], k, WINDOW, 1, 1)
-        m1, m2 = outs['smooth_mesh1'], outs['smooth_mesh2']                      # [k,7,7,9,2]: frame j's mesh is window j's last
-        src, T = ops.stream_splines([m1[0, -1], m2[0, -1]], WINDOW * e, self.bbox, self.nrigid, self.h, self.w, frames=k)
+        """k consecutive steady-state frame pairs of the stream from B['lr'] (capturable): _PairStep's k-frame step, then the
+        splines of the k frames in one launch; ends with the watcher and the footprints in B['deferred']."""
+        m1, m2 = self._batch_meshes(B)                                           # [k,7,7,9,2]: frame j's mesh is window j's last
+        src, T = ops.stream_splines([m1[0, -1], m2[0, -1]], WINDOW * 126, self.bbox, self.nrigid, self.h, self.w, frames=B['k'])
         self._leave_batch(B, src, T)
 
 
@@ -2097,61 +2135,17 @@ class ThreeViewOnlineStitcher(_Stitcher):
         return self._push_many_nv12((frames1, frames2, frames3), out)
 
     def _batch_buffers(self, k):
-        d, e, S = self.dev, 126, 2
-        fh, fw = pipeline.LR_H // 8, pipeline.LR_W // 8
-        return {'lr': torch.empty((3, k, 3, pipeline.LR_H, pipeline.LR_W), device=d),     # the three views back to back
-                'feat': torch.empty((3, k + 1, fh, fw, 128), device=d),        # TemporalNet features [view][previous frame, the k frames]
-                'sn': torch.empty((2, S * k, e), device=d),                    # new spatial motions [first | second view][pair][k]
-                'tn': torch.empty((2, S * k, e), device=d),                    # their temporal motions, same layout
-                'sw': torch.empty((2, S, k + 1, e), device=d),                 # spatial motions [pair view][pair][previous, the k frames]
-                'tt': torch.zeros((2, S, k + 1, e), device=d),                 # temporal motions [pair view][pair][zero, the k frames]
-                'ts': torch.empty((2, 2 * S * (k + 1), e), device=d),          # tsmotion's (smesh, tsmotion) rows
-                'work': torch.empty((4 * S, WINDOW - 1 + k, e), device=d)}     # the k sliding windows of the eight rings
+        return self.chains._batch_buffers(k)
 
     def _step_batch(self, B):
-        """k consecutive steady-state frame triples from B['lr'] (capturable; the chains' state is read once and left as k
-        `_step_static` runs leave it).  The three views' k frames pass the twin trunks once (3k images); pair (s, j) -- chain s,
-        frame j -- is images (s k + j, (s + 1) k + j) of the [view][frame] trunk output; TemporalNet's 2 S k volumes come from the
-        features stored once, [view][previous frame, the k frames] (ss_cost_volume_chain_frames); tsmotion pairs each row of
-        [pair view][pair][previous, the k frames] with the one before; the eight rings advance by k; SmoothNet runs the windows of
-        both chains as ONE run over each ring kind's rows (the W - 1 windows that straddle the two chains are computed and
-        ignored); composition + splines of the k frames in one launch.  Ends with the watcher and the footprints (B['deferred'])."""
-        ch = self.chains
-        cs, k, e, S = ch.static, B['k'], 126, 2
-        F, sn, tn, sw, tt, ts = B['feat'], B['sn'], B['tn'], B['sw'], B['tt'], B['ts']
-        fc = L.run_stage1_pair([B['lr'].view(3 * k, 3, pipeline.LR_H, pipeline.LR_W)], ch._trunk())   # [2(net), 3k, 45,60,128]
-        f64 = fc[0]
-        off1 = _heads_a(self.spatial, f64, S * k, k)
-        F[:, 0].copy_(cs['prev_feat'])
-        F[:, 1:].copy_(fc[1].view(F[:, 1:].shape))
-        cv_s = self.spatial.cv_from_offset1(f64[:S * k], f64[k:k + S * k], off1, pipeline.LR_H, pipeline.LR_W)
-        cv_t = ops.cost_volume_chain_frames(F, 3)                               # [2 (pair view), S, k, 45,60,52]
-        off_ref = torch.empty((S * k, e), device=self.dev, dtype=torch.float32)
-        off_tgt = torch.empty((S * k, e), device=self.dev, dtype=torch.float32)
-        L.run_regressor_quad(cv_s, cv_t.view((2, S * k) + tuple(cv_t.shape[3:])), L.get_quad(self.spatial, self.temporal),
-                             [off_ref, off_tgt, tn[0], tn[1]])
-        cs['prev_feat'].copy_(F[:, k])
-        ops.spatial_meshes(off1, off_ref, off_tgt, pipeline.LR_H, pipeline.LR_W,
-                           out=(sn[0].view(S * k, 7, 9, 2), sn[1].view(S * k, 7, 9, 2)))
-        ps = cs['pair_s']                                                       # [pair view][previous, new][S][126]
-        torch.cat((ps[:, 0].view(2, S, 1, e), sn.view(2, S, k, e)), 2, out=sw)
-        tt[:, :, 1:].copy_(tn.view(2, S, k, e))
-        ps[:, 0].copy_(sw[:, :, k])                                             # the newest spatial motions become the previous ones
-        # tsmotion of every (pair view, pair) sequence as ONE batch of 2 S (k + 1) rows: row j pairs with row j - 1; slot 0's rows
-        # are computed and ignored
-        ops.tsmotion(sw.view(-1, 7, 9, 2), tt.view(-1, 7, 9, 2), pipeline.LR_H, pipeline.LR_W, out=(ts[0], ts[1]))
-        # ring r = kind q * S + s (kinds: smesh of the first / second view, tsmotion of the first / second view) <- rows 1 .. k of its
-        # sequence in ts
-        n1 = k + 1
-        offs = [((q // 2) * 2 * S * n1 + ((q % 2) * S + s) * n1 + 1) * e for q in range(4) for s in range(S)]
-        ops.window_advance(cs['ring'].view(4 * S, WINDOW, e), B['work'], ts, offs, k)
-        wk = B['work'].view(4, S * (WINDOW - 1 + k), 7, 9, 2)
-        nw = (S - 1) * (WINDOW - 1 + k) + k                     # window w starts at row w: chain s's frame j is window s (W - 1 + k) + j
-        outs, _ = self.smooth.run_windows(wk[0], wk[1], wk[2], wk[3], nw, WINDOW, 1, 1)
-        m1, m2 = outs['smooth_mesh1'], outs['smooth_mesh2']                      # [nw,7,7,9,2]: a frame's mesh is its window's last
+        """k consecutive steady-state frame triples from B['lr'] (capturable): the chains' k-frame step (_PairStep._batch_meshes
+        over the three views), then composition + splines of the k frames in one launch; ends with the watcher and the footprints
+        (B['deferred'])."""
+        k = B['k']
+        m1, m2 = self.chains._batch_meshes(B)                    # [nw,7,7,9,2]: pair (2,3)'s windows start WINDOW - 1 + k further
         c1 = WINDOW - 1 + k
         meshes, src, T = ops.three_view_splines(m1[0, -1], m2[0, -1], m1[c1, -1], m2[c1, -1], self.first_canvas, self.bbox,
-                                                self.nrigid, self.h, self.w, frames=k, frame_stride=WINDOW * e)
+                                                self.nrigid, self.h, self.w, frames=k, frame_stride=WINDOW * 126)
         self.last_composed = meshes
         self._leave_batch(B, src, T)
 

@@ -11,7 +11,7 @@ import torch
 from stabstitch2_amd import ops, synth
 from test_gpu_parity import dev, hip_nets, close_boxes  # noqa: F401  (fixtures / helpers)
 from test_gpu_stream_oracle import _equal
-from test_gpu_push_many import _fresh_nets
+from test_gpu_push_many import _fresh_nets, _clip as _pair_clip
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -23,9 +23,11 @@ E = 126
 @pytest.mark.parametrize('k', [1, 3, 8, 32])
 def test_cost_volume_chain_frames_equals_gathered_pairs(dev, k):
     """ss_cost_volume_chain_frames == ss_cost_volume on the gathered contiguous pairs (F[s + h][j], F[s + h][j + 1]), bit for bit,
-    for a chain of three views (and of two at k = 3) on TemporalNet's feature geometry; a NaN guard behind `out` stays untouched."""
+    for a chain of three views and of two (one pair: OnlineStitcher's batched step) on TemporalNet's feature geometry; a NaN guard
+    behind `out` stays untouched.  Two views: also equal to ss_cost_volume_shifted(n = 2 k, split = k, shift = 1) over the same
+    features, the launch that step made before."""
     g = torch.Generator().manual_seed(100 + k)
-    for views in ((3, 2) if k == 3 else (3,)):
+    for views in (3, 2):
         S = views - 1
         F = torch.randn((views, k + 1, 45, 60, 128), generator=g).to(dev)
         shape = (2, S, k, 45, 60, 52)
@@ -38,6 +40,11 @@ def test_cost_volume_chain_frames_equals_gathered_pairs(dev, k):
         torch.cuda.synchronize()
         assert torch.equal(got.reshape(ref.shape), ref), (views, k)
         assert bool(torch.isnan(buf[n:]).all()), 'wrote past out'
+        if views == 2:
+            Ff = F.view((2 * (k + 1),) + tuple(F.shape[2:]))
+            old = ops.cost_volume(Ff[:-1], Ff[1:], 3, n=2 * k, split=k, shift=1)
+            torch.cuda.synchronize()
+            assert torch.equal(got.reshape(old.shape), old), ('split / shift', k)
 
 
 def test_three_view_splines_frame_stride(dev):
@@ -175,6 +182,44 @@ def test_three_view_push_many_u8_equals_push_u8(dev, hip_nets, fusion):
     assert len(got) == n and all(f.dtype == torch.uint8 and f.shape[-1] == 3 for f in got)
     _equal(got, ref, 'three-view push_many_u8 vs push_u8 %s' % fusion)
     _same_stream(st, ref_st, 'u8 ' + fusion)
+
+
+@pytest.mark.parametrize('use_graph', [True, False], ids=['graph', 'eager'])
+@pytest.mark.parametrize('views', [2, 3], ids=['two-view', 'three-view'])
+def test_batched_step_leaves_the_state_of_single_pushes(dev, hip_nets, views, use_graph):
+    """The k-frame step both classes share (_PairStep._batch_meshes) against single pushes, deterministic=True, 180x320: 7 plain
+    pushes, then push_many of k = 1 (one new row: the in-place views degenerate), k = 2 (the smallest k with a shifted pair inside
+    the batch) and k = 8 > WINDOW (every ring row comes from the work rows); a reference stitcher takes the same 18 frames one push
+    at a time.  Every returned frame and overflow_report(), then prev_feat, ring and the previous motions pair_s[:, 0] (three
+    views: the chains') bit for bit.  pair_s[:, 1], the `new` slot, is not compared: a single push writes it before it reads it and
+    leaves it equal to slot 0, a batched step does not write it (it holds what the last single push left), and nothing reads it
+    before the next write."""
+    from stabstitch2_amd.online import OnlineStitcher, ThreeViewOnlineStitcher, WINDOW
+    h, w, ks = 180, 320, (1, 2, 8)
+    assert ks[-1] > WINDOW
+    n = 7 + sum(ks)
+    if views == 2:
+        hr, lr = _pair_clip(n, h, w, 31)
+        frames = [t.to(dev) for t in (hr[0], hr[1], lr[0], lr[1])]
+    else:
+        frames = [t.to(dev) for t in _clip(n, h, w, 31)]
+    cls = OnlineStitcher if views == 2 else ThreeViewOnlineStitcher
+    mk = lambda: cls(hip_nets, h, w, use_graph=use_graph, deterministic=True)
+    ref_st, st = mk(), mk()
+    ref = _singles(ref_st, n, frames)
+    got, t = _singles(st, 7, frames), 7
+    for k in ks:
+        got += st.push_many(*[f[t:t + k] for f in frames])
+        t += k
+    torch.cuda.synchronize()
+    assert len(got) == n == len(ref)
+    _equal(got, ref, '%d-view batched step vs single pushes, graph=%s' % (views, use_graph))
+    rep = _same_stream(st, ref_st, 'batched step')
+    assert rep['frames_seen'] == n
+    a, b = (st.static, ref_st.static) if views == 2 else (st.chains.static, ref_st.chains.static)
+    for name in ('prev_feat', 'ring'):
+        assert torch.equal(a[name], b[name]), name
+    assert torch.equal(a['pair_s'][:, 0], b['pair_s'][:, 0]), 'pair_s[:, 0]'
 
 
 def test_three_view_push_many_passes_each_view_once(dev, hip_nets):
