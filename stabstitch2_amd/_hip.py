@@ -18,6 +18,9 @@ LIBRARIES = ('_hip', '_blend', '_seam', '_mbwarp', '_surfaces')
 # Libraries behind a path that the five above also cover (the same description, the same loader and launch path): the build and its
 # surface check go over them too.  _smoothtail: SmoothNet's Conv3d stack of a stitched clip.
 EXTRA_LIBRARIES = ('_smoothtail',)
+# Libraries of features added since (what the renders do not change for): the tuple a later library's module goes to.  The two above
+# are pinned by their tests.  _cover: coverage bitmaps and the largest fully covered rectangle.
+FEATURE_LIBRARIES = ('_cover',)
 
 LIB_PATH = os.path.join(_HERE, 'libstabstitch_hip.so')
 HEADER, API, PREFIX = 'stabstitch_hip.h', 'SS_API', 'ss_'

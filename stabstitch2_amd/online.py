@@ -238,6 +238,11 @@ def _no_exposure(cls, exposure):
         raise ValueError('%s has no exposure compensation yet: it is built for OnlineStitcher only' % cls)
 
 
+def _no_coverage(cls, track_coverage):
+    if track_coverage:
+        raise ValueError('%s has no track_coverage: it is built for OnlineStitcher and ThreeViewOnlineStitcher' % cls)
+
+
 def _canvas_size(bb):
     """(Hc, Wc) of a canvas (wmin, wmax, hmin, hmax), CPU fp32 [4]."""
     return int((bb[3] - bb[2]).int()), int((bb[1] - bb[0]).int())
@@ -655,7 +660,7 @@ class _Stitcher:
     _MULTIBAND = False       # does the class render MULTIBAND fusion?  (one canvas, one push in flight: the two plain stitchers)
 
     def __init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only=False, canvases=1,
-                 viewport=None, zoom_limit=2.0, exposure=None, bands=None, seam=None):
+                 viewport=None, zoom_limit=2.0, exposure=None, bands=None, seam=None, track_coverage=False):
         self.exposure = _exposure_params(exposure, meshes_only)      # None: no launch, buffer or graph node of it exists
         self.bands = None
         # MULTIBAND's seam (seam = the dict of the constructor's seam= keywords): {} = the geometric one
@@ -709,6 +714,19 @@ class _Stitcher:
         # batch renders all ask `mode`, not the mode's name
         self.mode = (_FusedRender if self._fused else _MultibandRender if fusion_mode == 'MULTIBAND' else _LinearRender)(self)
         self._deferred = None            # direct render: the _Deferred the step left for the push's render
+        # track_coverage: one ops.coverage_state of the current canvas, every frame handed out on it AND-ed in behind its render, outside
+        # the graph; off: no launch, buffer or field of it does anything
+        self.track_coverage = bool(track_coverage)
+        if self.track_coverage:
+            if meshes_only:
+                raise ValueError('track_coverage follows rendered frames: not for meshes_only stitchers')
+            if grow == 'refit':
+                raise ValueError("track_coverage has no grow='refit' form: the box moves on the device without the host knowing")
+            if use_graph and not self.mode.direct:
+                raise ValueError('track_coverage needs the push to launch its render itself: not with a captured step that renders '
+                                 'inside its graph (SS_DIRECT_RENDER=0 / SS_DIRECT_LINEAR=0 with use_graph=True)')
+        self._cover = None               # the ops.CoverageState, from _set_canvas on
+        self.coverage_frames = 0         # frames handed out on the current canvas (track_coverage)
         # overflow of the fixed canvas(es), and the device-side refit of their boxes; meshes_only: never started
         self.watch = _CanvasWatch(canvases, margin, self.dev, viewport, grow == 'refit', zoom_limit)
         self.static = None               # steady-state buffers (inputs, rings, output) once the window is full
@@ -770,18 +788,45 @@ class _Stitcher:
         if self.viewport is not None:
             self.bbox = self.bbox.to(torch.float32).contiguous()
             self.watch.start(self.watch.fit_boxes(self.bbox))
+            self._cover_reset()
             return
         bb = self.bbox.cpu()
         self.hc, self.wc = _canvas_size(bb)
         self.watch.start(bb[None])
+        self._cover_reset()
 
     def _regrown(self, rows):
         """grow='recapture': the watcher re-fixed the canvas -- new box, new size, a new output buffer (the graph is captured again)."""
         self.bbox = self.watch.boxes[0].to(self.dev)
         self.hc, self.wc = _canvas_size(self.watch.boxes[0])
         self.mode.canvas_changed()
+        self._cover_reset()
         if self.static['out'] is not None:
             self.static['out'] = torch.empty((3, self.hc, self.wc), device=self.dev)
+
+    # ------------------------------------------------------------------ coverage of the frames handed out (track_coverage)
+    def _cover_reset(self):
+        """The canvas was set or regrown: coverage starts again, on its size."""
+        if self.track_coverage:
+            self._cover = ops.coverage_state(self.hc, self.wc, self.dev)
+            self.coverage_frames = 0
+
+    def _cover_add(self, src, T):
+        """The frame(s) of the splines src [V,63,2] | [k,V,63,2], T were handed out on the current canvas: one accumulate launch on
+        the push's stream, behind their render."""
+        if self._cover is not None:
+            ops.coverage_update(self._cover, src, T, self.h, self.w, self.warp_mode)
+            self.coverage_frames += 1 if src.dim() == 3 else int(src.shape[0])
+
+    def covered_rect(self, even=False):
+        """(y0, x0, h, w): the largest rectangle that every frame handed out on the current canvas covers (ops.covered_rect: largest
+        area, then smallest y0, smallest x0, largest width; even: h and w rounded down to even) -- the window to cut from all of them
+        for a video without a border; None before the canvas is fixed.  track_coverage stitchers only.  Synchronises (16 bytes)."""
+        if not self.track_coverage:
+            raise ValueError('covered_rect needs a stitcher built with track_coverage=True')
+        if self._cover is None:
+            return None
+        return tuple(int(v) for v in ops.covered_rect(self._cover, even).cpu().tolist())
 
     # ------------------------------------------------------------------ steady state
     def _versions(self):
@@ -866,8 +911,12 @@ class _Stitcher:
         if self.grow == 'recapture':
             self.watch.post_copy()
         if nv12 is not None:
-            return [self.mode.frame_nv12(nv12[0], self._deferred, self.hc, self.wc, nv12[1])]
-        return self._take(self._deferred, self.static['out'], u8 or frames[:len(frames) // 2], u8 is not None)
+            out = [self.mode.frame_nv12(nv12[0], self._deferred, self.hc, self.wc, nv12[1])]
+        else:
+            out = self._take(self._deferred, self.static['out'], u8 or frames[:len(frames) // 2], u8 is not None)
+        if self._cover is not None and self._direct():       # (a step that renders itself has added its frame: _render_solved)
+            self._cover_add(self._deferred.src, self._deferred.T)
+        return out
 
     def _take(self, left, out, imgs, u8):
         """A push's frames: without the direct render copies of the step's output `out`; with it, rendered now from the caller's
@@ -889,7 +938,9 @@ class _Stitcher:
         gains = None
         if efp is not None:
             gains = self._exposure_gains([f.reshape(1, 3, self.h, self.w) for f in imgs], efp)
-        return self.mode.render_into(imgs, left, self.hc, self.wc, gains, out)
+        frame = self.mode.render_into(imgs, left, self.hc, self.wc, gains, out)
+        self._cover_add(src, T)
+        return frame
 
     def _grown(self, bb):
         """A box (wmin, wmax, hmin, hmax) grown by the margin on every side, on the device."""
@@ -1026,7 +1077,9 @@ class _Stitcher:
         self.frames_in += k
         if self.grow == 'recapture':
             self.watch.post_copy()
-        return self._render_batch(B['deferred'], u8 if u8 is not None else frames[:views], u8 is not None)
+        out = self._render_batch(B['deferred'], u8 if u8 is not None else frames[:views], u8 is not None)
+        self._cover_add(B['deferred'].src, B['deferred'].T)
+        return out
 
     def _leave_batch(self, B, src, T):
         """End of a batched step: the watcher over its k frames src [k,V,63,2], the footprints where the step needs them, and the
@@ -1213,8 +1266,12 @@ class OnlineStitcher(_PairStep, _Stitcher):
 
     def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
                  use_graph=True, grow='never', meshes_only=False, deterministic=False, viewport=None, zoom_limit=2.0, exposure=None,
-                 bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None):
+                 bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, track_coverage=False):
         """canvas: optional (wmin, wmax, hmin, hmax) in HR pixels (e.g. the offline bbox).
+        track_coverage: keep, on the device, which canvas pixels EVERY frame handed out so far covers: one small launch
+        per push (per push_many call) behind the render, outside the graph; `covered_rect()` then gives the largest rectangle with
+        picture in every pixel of every frame, `coverage_frames` the frames it stands for.  It starts again when the canvas changes
+        (grow='recapture').  Not with meshes_only, grow='refit', or a captured step that renders inside its graph.
         seam: None / 'geometric' (MULTIBAND's seam where the warped weight planes cross) or 'dp' -- the content-aware seam (DESIGN.md 7f;
         only with MULTIBAND): ops.multiband_seam between the warp and the blend of every frame handed out, on a grid of seam_cell x
         seam_cell cells, with seam_mu holding the seam to the previous frame's and seam_prior to the geometric one (defaults:
@@ -1252,7 +1309,8 @@ class OnlineStitcher(_PairStep, _Stitcher):
         _exposure_params(exposure, meshes_only)
         _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only,
                            viewport=viewport, zoom_limit=zoom_limit, exposure=exposure, bands=bands,
-                           seam=dict(seam=seam, seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior))
+                           seam=dict(seam=seam, seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior),
+                           track_coverage=track_coverage)
         self.deterministic = bool(deterministic)
         self.last_meshes = None
         self.bbox = None if canvas is None else torch.tensor(canvas, dtype=torch.float32, device=self.dev)
@@ -1692,9 +1750,10 @@ class PipelinedOnlineStitcher(_TwoInFlight, OnlineStitcher):
     overflow is counted as in OnlineStitcher) or, with a viewport, re-fixed on the device (grow='refit').  LINEAR fusion renders inside the graphs (no direct LINEAR render: _TwoInFlight)."""
 
     def __init__(self, nets, height, width, canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE', deterministic=False,
-                 grow='never', viewport=None, zoom_limit=2.0, exposure=None):
+                 grow='never', viewport=None, zoom_limit=2.0, exposure=None, track_coverage=False):
         """grow: 'never', or 'refit' with a viewport (see OnlineStitcher and _TwoInFlight)."""
         _no_exposure('PipelinedOnlineStitcher', exposure)
+        _no_coverage('PipelinedOnlineStitcher', track_coverage)
         self._check_grow(grow)
         OnlineStitcher.__init__(self, nets, height, width, canvas, margin, warp_mode, fusion_mode, use_graph=True, grow=grow,
                                 meshes_only=False, deterministic=deterministic, viewport=viewport, zoom_limit=zoom_limit)
@@ -1734,7 +1793,7 @@ class MultiOnlineStitcher(_PairStep, _Stitcher):
 
     def __init__(self, nets, height, width, streams, canvases=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
                  use_graph=True, grow='never', meshes_only=False, deterministic=False, chain=False, viewport=None, zoom_limit=2.0,
-                 exposure=None):
+                 exposure=None, track_coverage=False):
         """grow: as OnlineStitcher -- 'never' counts the frames whose mesh left their stream's canvas (`clipped_frames`, per
         stream), 'recapture' re-fixes the canvases of the streams that come near an edge and captures the graph again, 'refit' (with
         a viewport) re-fixes each stream's box on the device inside the push's launches.
@@ -1743,6 +1802,7 @@ class MultiOnlineStitcher(_PairStep, _Stitcher):
         7th push, then 1) or None; ThreeViewOnlineStitcher runs its two pair chains as such a batch of two and captures the graph
         itself (use_graph is ignored)."""
         _no_exposure(type(self).__name__, exposure)
+        _no_coverage(type(self).__name__, track_coverage)
         _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, meshes_only,
                            canvases=max(1, int(streams)), viewport=viewport, zoom_limit=zoom_limit)
         self.deterministic = bool(deterministic)      # geometry-only kernel policy: S batched streams == S single streams, bit for bit
@@ -1923,9 +1983,10 @@ class PipelinedMultiOnlineStitcher(_TwoInFlight, MultiOnlineStitcher):
     _U8_STEADY = False       # push_u8: ingest_u8 -> push -> canvas_to_u8
 
     def __init__(self, nets, height, width, streams, canvases=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 deterministic=False, grow='never', viewport=None, zoom_limit=2.0, exposure=None):
+                 deterministic=False, grow='never', viewport=None, zoom_limit=2.0, exposure=None, track_coverage=False):
         """grow: 'never', or 'refit' with a viewport (see MultiOnlineStitcher and _TwoInFlight)."""
         _no_exposure('PipelinedMultiOnlineStitcher', exposure)
+        _no_coverage('PipelinedMultiOnlineStitcher', track_coverage)
         self._check_grow(grow)
         MultiOnlineStitcher.__init__(self, nets, height, width, streams, canvases, margin, warp_mode, fusion_mode, use_graph=True,
                                      grow=grow, meshes_only=False, deterministic=deterministic, viewport=viewport,
@@ -1971,11 +2032,12 @@ class ThreeViewOnlineStitcher(_Stitcher):
 
     def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
                  use_graph=True, grow='never', deterministic=False, viewport=None, zoom_limit=2.0, exposure=None, bands=None, seam=None,
-                 seam_cell=None, seam_mu=None, seam_prior=None):
+                 seam_cell=None, seam_mu=None, seam_prior=None, track_coverage=False):
         """deterministic: every push under the conv engine's geometry-only kernel policy (ops.deterministic; as OnlineStitcher's):
         push_many's frames then equal single pushes' bit for bit.
         fusion_mode='MULTIBAND', bands= and seam= (seam_cell=, seam_mu=, seam_prior=): as OnlineStitcher's, over the three views at once
-        (two seams, between the views that neighbour each other on the canvas)."""
+        (two seams, between the views that neighbour each other on the canvas).  track_coverage: as OnlineStitcher's, over the three
+        views."""
         pipeline.seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)
         _no_exposure(type(self).__name__, exposure)
         # the two pair chains as a batch of two streams over the CHAIN of three views: every launch serves both pairs, view 2's
@@ -1984,7 +2046,8 @@ class ThreeViewOnlineStitcher(_Stitcher):
                                           use_graph=False, meshes_only=True, deterministic=deterministic, chain=True)
         _Stitcher.__init__(self, nets, height, width, margin, warp_mode, fusion_mode, use_graph, grow, viewport=viewport,
                            zoom_limit=zoom_limit, bands=bands,
-                           seam=dict(seam=seam, seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior))
+                           seam=dict(seam=seam, seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior),
+                           track_coverage=track_coverage)
         self.deterministic = bool(deterministic)
         box = lambda b: None if b is None else torch.tensor(b, dtype=torch.float32, device=self.dev)
         self.bbox, self.first_canvas = box(canvas), box(first_canvas)
@@ -2159,9 +2222,10 @@ class PipelinedThreeViewOnlineStitcher(_TwoInFlight, ThreeViewOnlineStitcher):
     _U8_STEADY = False       # push_u8: ingest_u8 -> push -> canvas_to_u8
 
     def __init__(self, nets, height, width, canvas=None, first_canvas=None, margin=0.03, warp_mode='NORMAL', fusion_mode='AVERAGE',
-                 grow='never', viewport=None, zoom_limit=2.0, exposure=None):
+                 grow='never', viewport=None, zoom_limit=2.0, exposure=None, track_coverage=False):
         """grow: 'never', or 'refit' with a viewport (see ThreeViewOnlineStitcher and _TwoInFlight)."""
         _no_exposure('PipelinedThreeViewOnlineStitcher', exposure)
+        _no_coverage('PipelinedThreeViewOnlineStitcher', track_coverage)
         self._check_grow(grow)
         ThreeViewOnlineStitcher.__init__(self, nets, height, width, canvas, first_canvas, margin, warp_mode, fusion_mode,
                                          use_graph=True, grow=grow, viewport=viewport, zoom_limit=zoom_limit)

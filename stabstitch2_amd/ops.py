@@ -10,7 +10,7 @@ import ctypes
 import torch
 
 from . import _hip as H
-from . import _blend as B, _mbwarp as W, _seam as S, _smoothtail as ST, _surfaces as F
+from . import _blend as B, _cover as CV, _mbwarp as W, _seam as S, _smoothtail as ST, _surfaces as F
 
 
 def _f(t):
@@ -1860,3 +1860,120 @@ def smooth_tail_deltas(hid, convs, dec, nw, out=None):
     for (w, b), (first_in, first_out) in zip(convs, SMOOTH_TAIL_FRAMES):
         hid = smooth_tail_layer(hid, w, b, nw, first_in, first_out, seg_tiles)
     return smooth_tail_decode(hid, dec[0], dec[1], out, nw)
+
+
+# ------------------------------------------------------------------ coverage and the largest covered rectangle (libstabstitch_cover.so)
+MIN_MASK = 0.5       # a view covers a pixel where its warped ones-mask is >= this: MULTIBAND's validity rule (tests/multiband_ref.py)
+
+
+class CoverageState(collections.namedtuple('CoverageState', 'bitmap ws hc wc')):
+    """A running coverage of a hc x wc canvas: bitmap int64 [hc, ceil(wc / 64)] (bit i of word j = column 64 j + i; the AND of every
+    frame's coverage so far) and the workspace `ws` (uint8) that covered_rect searches it with."""
+    __slots__ = ()
+
+
+def coverage_words(wc):
+    return (int(wc) + 63) // 64
+
+
+def _cover_canvas(what, hc, wc):
+    for v in (hc, wc):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError('%s: the canvas size must be two ints, got %r x %r' % (what, hc, wc))
+    if hc <= 1 or wc <= 1 or wc > CV.MAX_WIDTH or hc * wc >= 2 ** 31 or (hc + 7) // 8 > 65535:
+        raise ValueError('%s: no coverage of a %d x %d canvas (2 .. %d columns, fewer than 2^31 pixels)' % (what, hc, wc, CV.MAX_WIDTH))
+
+
+def _cover_args(what, source, T, h, w, mode, min_mask):
+    """The checks coverage and coverage_update share -> (source [n,V,63,2], T, n, v, min_mask)."""
+    if not torch.is_tensor(source) or not torch.is_tensor(T):
+        raise ValueError('%s takes the splines as tensors: source [n,V,63,2], T [n,V,2,66]' % what)
+    if source.dim() == 3:
+        source = source[None]
+    if source.dim() != 4 or tuple(source.shape[2:]) != (63, 2) or source.shape[1] not in (2, 3) or source.shape[0] < 1:
+        raise ValueError('%s: source must be [n,V,63,2] with V = 2 | 3, got %s' % (what, tuple(source.shape)))
+    n, v = int(source.shape[0]), int(source.shape[1])
+    if T.numel() != n * v * 132 or tuple(T.shape[-2:]) != (2, 66):
+        raise ValueError('source %s and T %s do not match %d frames of %d views' % (tuple(source.shape), tuple(T.shape), n, v))
+    if source.dtype != torch.float32 or T.dtype != torch.float32:
+        raise ValueError('%s takes fp32 splines, got %s and %s' % (what, source.dtype, T.dtype))
+    if mode not in MODES:
+        raise ValueError("%s: mode must be 'NORMAL' or 'FAST', got %r" % (what, mode))
+    for x in (h, w):
+        if isinstance(x, bool) or not isinstance(x, int) or x <= 1:
+            raise ValueError('%s: the image size must be two ints > 1, got %r x %r' % (what, h, w))
+    if isinstance(min_mask, bool) or not isinstance(min_mask, (int, float)) or not 0.0 < float(min_mask) <= 1.0:
+        raise ValueError('%s: min_mask must lie in (0, 1], got %r' % (what, min_mask))
+    return source, T, n, v, float(min_mask)
+
+
+def coverage(source, T, h, w, hc, wc, mode='NORMAL', min_mask=MIN_MASK):
+    """Which pixels of the hc x wc canvas each frame covers, one launch: source [n,V,63,2] ([V,63,2]: one frame), T [n,V,2,66]: the
+    splines the renders take, of V images h x w -> bitmaps int64 [n, hc, ceil(wc / 64)], bit i of word j = column 64 j + i (pad bits
+    0).  A pixel is covered where some view's warped ones-mask -- the mask plane of tps_warp(..., with_mask=True) and of
+    multiband_warp, bit for bit -- is >= min_mask."""
+    source, T, n, v, min_mask = _cover_args('coverage', source, T, h, w, mode, min_mask)
+    _cover_canvas('coverage', hc, wc)
+    if n > CV.MAX_FRAMES:
+        raise ValueError('coverage takes at most %d frames per call, got %d' % (CV.MAX_FRAMES, n))
+    out = torch.empty((n, hc, coverage_words(wc)), device=source.device, dtype=torch.int64)
+    CV.call('ssc_coverage', H.dptr(_f(source)), H.dptr(_f(T)), H.dptr(out, dtype=torch.int64), n, v, h, w, hc, wc, MODES[mode], min_mask,
+            0, H.stream())
+    return out
+
+
+def coverage_state(hc, wc, device):
+    """A fresh CoverageState of a hc x wc canvas: every column < wc covered, and covered_rect's workspace."""
+    _cover_canvas('coverage_state', hc, wc)
+    bitmap = torch.full((hc, coverage_words(wc)), -1, device=device, dtype=torch.int64)
+    if wc % 64:
+        bitmap[:, -1] = (1 << (wc % 64)) - 1
+    ws = torch.empty(int(CV.lib().ssc_rect_workspace_bytes(hc, wc)), device=device, dtype=torch.uint8)
+    return CoverageState(bitmap, ws, hc, wc)
+
+
+def coverage_update(state, source, T, h, w, mode='NORMAL', min_mask=MIN_MASK):
+    """state.bitmap &= the coverage of every frame of source [n,V,63,2] / T [n,V,2,66] (as `coverage` takes them), in one launch
+    that loops over the frames; -> state."""
+    if not isinstance(state, CoverageState):
+        raise ValueError('coverage_update takes a CoverageState (ops.coverage_state), got %r' % type(state).__name__)
+    source, T, n, v, min_mask = _cover_args('coverage_update', source, T, h, w, mode, min_mask)
+    CV.call('ssc_coverage', H.dptr(_f(source)), H.dptr(_f(T)), H.dptr(state.bitmap, dtype=torch.int64), n, v, h, w, state.hc, state.wc,
+            MODES[mode], min_mask, 1, H.stream())
+    return state
+
+
+def covered_rect(bitmap_or_state, even=False, wc=None, ws=None):
+    """The largest rectangle of covered pixels -> int32 [4] = (y0, x0, h, w) on the device (largest area, then smallest y0, then
+    smallest x0, then largest width; zeros when nothing is covered; even: h and w rounded down to even).  Nothing synchronises.
+    bitmap_or_state: a CoverageState, or a bitmap int64 [hc, W64] ([1, hc, W64]) with wc= its width in pixels (ws: a workspace of
+    ssc_rect_workspace_bytes(hc, wc) bytes to search it with, else a new one).  A stack of n > 1 bitmaps is refused: the library
+    ANDs frames where it computes them -- run the frames through coverage_update and pass the state."""
+    if isinstance(bitmap_or_state, CoverageState):
+        if wc is not None or ws is not None:
+            raise ValueError('covered_rect: wc= and ws= belong to a bare bitmap, a CoverageState has its own')
+        bitmap, ws, hc, wc = bitmap_or_state
+    else:
+        bitmap = bitmap_or_state
+        if not torch.is_tensor(bitmap) or bitmap.dtype != torch.int64 or bitmap.dim() not in (2, 3):
+            raise ValueError('covered_rect takes a CoverageState or an int64 bitmap [hc, W64]')
+        if bitmap.dim() == 3:
+            if bitmap.shape[0] != 1:
+                raise ValueError('covered_rect takes one bitmap, got a stack of %d: AND the frames with coverage_update and pass '
+                                 'its state' % bitmap.shape[0])
+            bitmap = bitmap[0]
+        if isinstance(wc, bool) or not isinstance(wc, int):
+            raise ValueError('covered_rect: a bare bitmap needs wc=, its width in pixels')
+        hc = int(bitmap.shape[0])
+        _cover_canvas('covered_rect', hc, wc)
+        if bitmap.shape[1] != coverage_words(wc):
+            raise ValueError('covered_rect: a bitmap of %d words per row is not %d pixels wide' % (bitmap.shape[1], wc))
+        need = int(CV.lib().ssc_rect_workspace_bytes(hc, wc))
+        if ws is None:
+            ws = torch.empty(need, device=bitmap.device, dtype=torch.uint8)
+        elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need:
+            raise ValueError('covered_rect: ws must be a uint8 tensor of at least %d bytes' % need)
+    rect = torch.empty(4, device=bitmap.device, dtype=torch.int32)
+    CV.call('ssc_covered_rect', H.dptr(bitmap, dtype=torch.int64), hc, wc, int(bool(even)), H.dptr(ws, dtype=torch.uint8), ws.numel(),
+            H.dptr(rect, dtype=torch.int32), H.stream())
+    return rect

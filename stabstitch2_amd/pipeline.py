@@ -542,6 +542,72 @@ def _seam_kw(seam, views, hc, wc, dev, seam_state=None):
     return seam
 
 
+class Crop:
+    """crop= of the offline routes: crop every frame of the call to the largest rectangle that all of them cover.
+    even: round the rectangle's height and width down to even (video encoders); min_mask in (0, 1]: a view covers a pixel where its
+    warped ones-mask reaches it (0.5: MULTIBAND's validity rule).  After a call it carries `.rect = (y0, x0, h, w)` on the uncropped
+    canvas `.canvas = (Hc, Wc)`.  A Crop whose `.rect` is set is applied as given, without a coverage pass: hand the first call's Crop
+    to the later calls of a video rendered in several (on one bbox=), or set `.rect` from `covered_rect` on a box fixed in advance."""
+
+    def __init__(self, even=False, min_mask=ops.MIN_MASK):
+        if isinstance(min_mask, bool) or not isinstance(min_mask, (int, float)) or not 0.0 < float(min_mask) <= 1.0:
+            raise ValueError('Crop: min_mask must lie in (0, 1], got %r' % (min_mask,))
+        self.even, self.min_mask = bool(even), float(min_mask)
+        self.rect = None
+        self.canvas = None
+
+    def __repr__(self):
+        return 'Crop(even=%r, min_mask=%r, rect=%r, canvas=%r)' % (self.even, self.min_mask, self.rect, self.canvas)
+
+
+def check_crop(crop):
+    """crop= of the offline routes -> None | Crop; ValueError for anything else, and for a `.rect` that is no (y0, x0, h, w)."""
+    if crop is None:
+        return None
+    if not isinstance(crop, Crop):
+        raise ValueError('crop must be None or a pipeline.Crop, got %r' % (crop,))
+    if crop.rect is not None:
+        r = crop.rect
+        if not isinstance(r, (tuple, list)) or len(r) != 4 or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in r):
+            raise ValueError('Crop.rect must be (y0, x0, h, w) as non-negative ints, got %r' % (r,))
+    return crop
+
+
+def _clip_rect(src, T, img_h, img_w, hc, wc, warp_mode, even, min_mask):
+    """(y0, x0, h, w) of the largest rectangle every frame of the plan (src, T) covers: one accumulate launch over the frames, the
+    three of the search, one 16-byte read."""
+    state = ops.coverage_update(ops.coverage_state(hc, wc, src.device), src, T, img_h, img_w, warp_mode, min_mask)
+    return tuple(int(v) for v in ops.covered_rect(state, even).cpu().tolist())
+
+
+def _settle_crop(crop, src, T, img_h, img_w, hc, wc, warp_mode):
+    """The rectangle of a call's Crop on its hc x wc canvas: the one it carries, else the largest one all frames of the plan cover."""
+    if crop.rect is None:
+        crop.rect = _clip_rect(src, T, img_h, img_w, hc, wc, warp_mode, crop.even, crop.min_mask)
+    else:
+        y0, x0, h, w = crop.rect
+        if y0 + h > hc or x0 + w > wc:
+            raise ValueError('Crop.rect %r does not lie on the %d x %d canvas of this call' % (tuple(crop.rect), hc, wc))
+        crop.rect = tuple(crop.rect)
+    crop.canvas = (hc, wc)
+    return crop.rect
+
+
+def _cropped(crop, out, u8=False):
+    """-> (the window crop.rect of the frames `out` ([n,3,Hc,Wc], or uint8 [n,Hc,Wc,3]), its h, its w): a view."""
+    y0, x0, h, w = crop.rect
+    return (out[:, y0:y0 + h, x0:x0 + w, :] if u8 else out[:, :, y0:y0 + h, x0:x0 + w]), h, w
+
+
+@torch.no_grad()
+def covered_rect(meshes, img_h, img_w, warp_mode='NORMAL', prescaled=False, bbox=None, size=None, even=False, min_mask=ops.MIN_MASK):
+    """(y0, x0, h, w) of the largest rectangle that every frame of `meshes` covers on their canvas, as render_plan lays it out
+    (meshes, prescaled, bbox, size: render_plan's; even, min_mask: Crop's) -- what `crop=Crop(...)` would cut, without rendering."""
+    c = Crop(even, min_mask)
+    hc, wc, src, T = render_plan(meshes, img_h, img_w, prescaled, bbox, size)
+    return _clip_rect(src, T, img_h, img_w, hc, wc, warp_mode, c.even, c.min_mask)
+
+
 # what a clip render is asked for: uint8 clips to uint8 frames or fp32, warp and fusion mode, MULTIBAND's bands, seam_options() with the
 # caller's state, exposure_params() with the caller's
 _RenderOpt = collections.namedtuple('_RenderOpt', 'u8 warp fusion bands seam seam_state exposure exposure_state')
@@ -610,7 +676,7 @@ def _render_clip(views, src, T, img_h, img_w, hc, wc, out, dev, opt):
 @torch.no_grad()
 def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, prescaled=False, bbox=None,
                   size=None, bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, seam_state=None, exposure=None,
-                  exposure_state=None):
+                  exposure_state=None, crop=None, _crop_view=True):
     """img_lists: V lists (or tensors [N,3,H,W]) of HR frames (0..255); meshes: V tensors [1,N,7,9,2].
     -> (frames [N,3,Hc,Wc] device tensor, Hc, Wc).  Which launches render which fusion mode, for clips held as tensors and for lists
     of separate frames: _render_clip, the route table of DESIGN.md 7k.
@@ -622,7 +688,10 @@ def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', 
     exposure (None | True | ops.ExposureParams): exposure compensation in every fusion mode -- per frame, view and channel the gains of
     ops.exposure_update on the clip's footprints, smoothed through the clip in order, scale the sampled colours (min(g * s, 255)); for
     MULTIBAND in the warp, in front of the seam and the blend.  exposure_state: an ops.exposure_state to continue from and leave
-    advanced (a video rendered in several calls); without it every call starts fresh."""
+    advanced (a video rendered in several calls); without it every call starts fresh.
+    crop (None | Crop): the frames render as ever; what comes back is their window [:, :, y0:y0+h, x0:x0+w] (a view) on the largest
+    rectangle every frame of the call covers, with that h, w as Hc, Wc; the Crop carries the rectangle and the uncropped size."""
+    check_crop(crop)
     check_fusion(fusion_mode, bands)
     seam = seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)
     if seam_state is not None and not seam:
@@ -637,6 +706,10 @@ def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', 
     opt = _RenderOpt(False, warp_mode, fusion_mode, ops.MULTIBAND_BANDS if bands is None else bands, seam, seam_state, exposure,
                      exposure_state)
     _render_clip(img_lists, src, T, img_h, img_w, hc, wc, out, dev, opt)
+    if crop is not None:
+        _settle_crop(crop, src, T, img_h, img_w, hc, wc, warp_mode)
+        if _crop_view:                   # (_video_frames converts the whole canvas first: its uint8 frames are the window)
+            return _cropped(crop, out)
     return out, hc, wc
 
 
@@ -650,19 +723,21 @@ def get_stable_sqe(img1_list, img2_list, smooth_mesh1, smooth_mesh2, warp_mode, 
 
 @torch.no_grad()
 def run_two_view(hr1, hr2, lr1, lr2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', to_host=False, out=None, deterministic=False,
-                 bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, exposure=None):
+                 bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, exposure=None, crop=None):
     """-> (frames, Hc, Wc, smooth_mesh1, smooth_mesh2); frames = device tensor [N,3,Hc,Wc]
     (or list of HWC ndarrays with to_host=True).  out: the frames tensor of a previous call to render into; it is reused
     when the canvas still has that size (same-size clips of one stream), else a new one is allocated.
     deterministic: the conv engine's geometry-only kernel policy (ops.deterministic): a frame's bits do not depend on how many
     frames share its launches -- resident clip == chunked passes == stream.
-    seam, seam_cell, seam_mu, seam_prior: MULTIBAND's seam (render_frames); exposure: exposure compensation (render_frames)."""
+    seam, seam_cell, seam_mu, seam_prior: MULTIBAND's seam (render_frames); exposure: exposure compensation (render_frames);
+    crop: a Crop -- the frames cut to the largest rectangle all of them cover (render_frames)."""
     seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)      # (refused before the networks run)
+    check_crop(crop)
     exposure = exposure_params(exposure)
     with ops.deterministic(deterministic):
         acc = estimate_meshes(nets, lr1, lr2)
     frames, hc, wc = render_frames([hr1, hr2], [acc['smooth_mesh1'], acc['smooth_mesh2']], warp_mode, fusion_mode, out=out, bands=bands,
-                                   seam=seam, seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior, exposure=exposure)
+                                   seam=seam, seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior, exposure=exposure, crop=crop)
     if to_host:
         host = frames.permute(0, 2, 3, 1).cpu().numpy()
         frames = [host[i] for i in range(host.shape[0])]
@@ -691,17 +766,18 @@ def three_view_compose(w12_m1, w12_m2, w23_m1, w23_m2, img_h, img_w, first_canva
 
 @torch.no_grad()
 def three_view_render(img1, img2, img3, mesh1, middle, mesh3, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, bands=None,
-                      exposure=None, exposure_state=None, **seam):
+                      exposure=None, exposure_state=None, crop=None, **seam):
     """Meshes are HR-scale canvas pixels here (output of three_view_compose).  seam: render_frames' seam= keywords; exposure,
-    exposure_state: render_frames'."""
+    exposure_state, crop: render_frames'."""
     return render_frames([img1, img2, img3], [mesh1, middle, mesh3], warp_mode, fusion_mode, out=out, prescaled=True, bands=bands,
-                         exposure=exposure, exposure_state=exposure_state, **seam)
+                         exposure=exposure, exposure_state=exposure_state, crop=crop, **seam)
 
 
 @torch.no_grad()
 def run_three_view(hr1, hr2, hr3, lr1, lr2, lr3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', out=None, deterministic=False,
-                   bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, exposure=None):
+                   bands=None, seam=None, seam_cell=None, seam_mu=None, seam_prior=None, exposure=None, crop=None):
     seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)
+    check_crop(crop)
     exposure = exposure_params(exposure)     # (refused before the networks run)
     # the middle view's TemporalNet motions and SpatialNet trunk features are computed once and reused by pair (2,3)
     with ops.deterministic(deterministic):
@@ -711,7 +787,7 @@ def run_three_view(hr1, hr2, hr3, lr1, lr2, lr3, nets, warp_mode='NORMAL', fusio
     m1, mid, m3 = three_view_compose(a12['smooth_mesh1'], a12['smooth_mesh2'], a23['smooth_mesh1'],
                                      a23['smooth_mesh2'], img_h, img_w)
     frames, hc, wc = three_view_render(hr1, hr2, hr3, m1, mid, m3, warp_mode, fusion_mode, out=out, bands=bands, seam=seam,
-                                       seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior, exposure=exposure)
+                                       seam_cell=seam_cell, seam_mu=seam_mu, seam_prior=seam_prior, exposure=exposure, crop=crop)
     return frames, hc, wc, m1, mid, m3
 
 
@@ -748,11 +824,13 @@ def _u8_fused(fusion_mode):
 
 @torch.no_grad()
 def render_frames_u8(frame_lists, meshes, warp_mode='NORMAL', out=None, bbox=None, size=None, prescaled=False,
-                     fusion_mode='AVERAGE', exposure=None, exposure_state=None):
+                     fusion_mode='AVERAGE', exposure=None, exposure_state=None, crop=None):
     """frame_lists: V device tensors [N,H,W,3] uint8; meshes: V tensors [1,N,7,9,2] -> (uint8 [N,Hc,Wc,3], Hc, Wc):
     `render_frames(..., fusion_mode)` followed by `to_video_frames`, fused -- the uint8 routes of _render_clip's table (DESIGN.md 7k;
     LINEAR: the warped planes are fp32 either way, the blend writes the video frame).  exposure, exposure_state: as render_frames
-    takes them -- the gains of ops.exposure_update on the uint8 frames, into the renders' _gains entries."""
+    takes them -- the gains of ops.exposure_update on the uint8 frames, into the renders' _gains entries.  crop: render_frames', the
+    window being [:, y0:y0+h, x0:x0+w, :]."""
+    check_crop(crop)
     exposure = exposure_params(exposure, exposure_state)
     dev = meshes[0].device
     n = meshes[0].shape[1]
@@ -764,6 +842,9 @@ def render_frames_u8(frame_lists, meshes, warp_mode='NORMAL', out=None, bbox=Non
         out = torch.empty((n, hc, wc, 3), device=dev, dtype=torch.uint8)
     opt = _RenderOpt(True, warp_mode, fusion_mode, None, {}, None, exposure, exposure_state)
     _render_clip(frame_lists, src, T, img_h, img_w, hc, wc, out, dev, opt)
+    if crop is not None:
+        _settle_crop(crop, src, T, img_h, img_w, hc, wc, warp_mode)
+        return _cropped(crop, out, u8=True)
     return out, hc, wc
 
 
@@ -781,38 +862,43 @@ def _ingest_views(u8_views, fusion_mode):
     return ([x[0] for x in io] if want_hr else None), [x[1] for x in io]
 
 
-def _video_frames(u8_views, hrs, meshes, warp_mode, fusion_mode, out=None, bands=None, seam=None, **kw):
+def _video_frames(u8_views, hrs, meshes, warp_mode, fusion_mode, out=None, bands=None, seam=None, crop=None, **kw):
     """The uint8 video frames of a uint8 clip -> (uint8 [N,Hc,Wc,3], Hc, Wc): render_frames_u8 on the frames themselves where
     _ingest_views left no fp32 planes (hrs None), else render_frames on those planes (bands and the seam= keywords are its alone:
-    MULTIBAND is never fused) + canvas_to_u8.  out: render_frames_u8's; kw: what both renders take (prescaled, bbox, size, exposure)."""
+    MULTIBAND is never fused) + canvas_to_u8.  out: render_frames_u8's; kw: what both renders take (prescaled, bbox, size, exposure);
+    crop: theirs too -- the fp32 route converts the whole canvas and hands out the window of its uint8 frames."""
     if hrs is None:
-        return render_frames_u8(u8_views, meshes, warp_mode, out=out, fusion_mode=fusion_mode, **kw)
-    frames, hc, wc = render_frames(hrs, meshes, warp_mode, fusion_mode, bands=bands, **(seam or {}), **kw)
-    return ops.canvas_to_u8(frames, out=out((frames.shape[0], hc, wc, 3)) if callable(out) else out), hc, wc
+        return render_frames_u8(u8_views, meshes, warp_mode, out=out, fusion_mode=fusion_mode, crop=crop, **kw)
+    frames, hc, wc = render_frames(hrs, meshes, warp_mode, fusion_mode, bands=bands, crop=crop, _crop_view=False, **(seam or {}), **kw)
+    u8 = ops.canvas_to_u8(frames, out=out((frames.shape[0], hc, wc, 3)) if callable(out) else out)
+    return (u8, hc, wc) if crop is None else _cropped(crop, u8, u8=True)
 
 
 @torch.no_grad()
 def run_two_view_u8(frames1, frames2, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False, bands=None,
-                    exposure=None, **seam):
+                    exposure=None, crop=None, **seam):
     """uint8 in, uint8 out: ingest -> estimate -> render -> video frames.  -> (uint8 [N,Hc,Wc,3], Hc, Wc, m1, m2).
-    bands: MULTIBAND's pyramid levels (render_frames; None: ops.MULTIBAND_BANDS); exposure: exposure compensation (render_frames)."""
+    bands: MULTIBAND's pyramid levels (render_frames; None: ops.MULTIBAND_BANDS); exposure: exposure compensation (render_frames);
+    crop: a Crop (render_frames_u8)."""
     check_fusion(fusion_mode, bands)
     seam_options(fusion_mode, **seam)        # (MULTIBAND's seam= keywords: render_frames)
+    check_crop(crop)
     exposure = exposure_params(exposure)     # (refused before the networks run)
     f = [_as_device_u8(frames1, device), _as_device_u8(frames2, device)]
     hrs, lrs = _ingest_views(f, fusion_mode)
     acc = estimate_meshes(nets, lrs[0], lrs[1])
     m1, m2 = acc['smooth_mesh1'], acc['smooth_mesh2']
-    u8, hc, wc = _video_frames(f, hrs, [m1, m2], warp_mode, fusion_mode, bands=bands, seam=seam, exposure=exposure)
+    u8, hc, wc = _video_frames(f, hrs, [m1, m2], warp_mode, fusion_mode, bands=bands, seam=seam, exposure=exposure, crop=crop)
     return (u8.cpu().numpy() if to_host else u8), hc, wc, m1, m2
 
 
 @torch.no_grad()
 def run_three_view_u8(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusion_mode='AVERAGE', device='cuda', to_host=False, bands=None,
-                      exposure=None, **seam):
+                      exposure=None, crop=None, **seam):
     """`run_three_view` from decoded uint8 frames [N,H,W,3] to uint8 video frames (device-resident clip); bands: as run_two_view_u8.
-    -> (uint8 [N,Hc,Wc,3], Hc, Wc, mesh1, middle, mesh3)."""
+    -> (uint8 [N,Hc,Wc,3], Hc, Wc, mesh1, middle, mesh3).  crop: a Crop (render_frames_u8)."""
     check_fusion(fusion_mode, bands)
+    check_crop(crop)
     exposure = exposure_params(exposure)     # (refused before the networks run)
     f = [_as_device_u8(x, device) for x in (frames1, frames2, frames3)]
     img_h, img_w = f[0].shape[1], f[0].shape[2]
@@ -822,7 +908,8 @@ def run_three_view_u8(frames1, frames2, frames3, nets, warp_mode='NORMAL', fusio
     a12 = estimate_meshes(nets, lr[0], lr[1], keep_spatial_cache2=True)
     a23 = estimate_meshes(nets, lr[1], lr[2], tmotion1=a12['tmotion2'], spatial_cache1=a12.get('spatial_cache2'))
     ms = three_view_compose(a12['smooth_mesh1'], a12['smooth_mesh2'], a23['smooth_mesh1'], a23['smooth_mesh2'], img_h, img_w)
-    u8, hc, wc = _video_frames(f, hrs, list(ms), warp_mode, fusion_mode, bands=bands, seam=seam, prescaled=True, exposure=exposure)
+    u8, hc, wc = _video_frames(f, hrs, list(ms), warp_mode, fusion_mode, bands=bands, seam=seam, prescaled=True, exposure=exposure,
+                               crop=crop)
     return (u8.cpu().numpy() if to_host else u8), hc, wc, ms[0], ms[1], ms[2]
 
 
