@@ -21,6 +21,14 @@ EXTRA_LIBRARIES = ('_smoothtail',)
 # Libraries of features added since (what the renders do not change for): the tuple a later library's module goes to.  The two above
 # are pinned by their tests.  _cover: coverage bitmaps and the largest fully covered rectangle.
 FEATURE_LIBRARIES = ('_cover',)
+# That tuple is pinned by its test as well (tests/test_cover_abi.py), so this is the open one: a later library's module goes to ITS
+# end, and its test asserts membership, not equality.  _resample: fixed-size antialiased output of the covered rectangle.
+LATER_LIBRARIES = ('_resample',)
+
+
+def all_libraries():
+    """Every native library's binding module name, oldest first: what the build compiles and its surface check goes over."""
+    return LIBRARIES + EXTRA_LIBRARIES + FEATURE_LIBRARIES + LATER_LIBRARIES
 
 LIB_PATH = os.path.join(_HERE, 'libstabstitch_hip.so')
 HEADER, API, PREFIX = 'stabstitch_hip.h', 'SS_API', 'ss_'

@@ -7,6 +7,7 @@
 #                                              stabstitch2_amd/libstabstitch_surfaces.so    (NV12 surfaces -> BGR frames, surfaces.hip)
 #                                              stabstitch2_amd/libstabstitch_smoothtail.so  (SmoothNet's clip-only Conv3d stack, smoothtail.hip)
 #                                              stabstitch2_amd/libstabstitch_cover.so       (coverage bitmaps, largest covered rectangle, cover.hip)
+#                                              stabstitch2_amd/libstabstitch_resample.so    (fixed-size antialiased output of a rectangle, resample.hip)
 #   stabstitch2_amd/csrc/build.sh tuning    -> tools/libstabstitch_hip_tuning.so            (-DSS_TUNING: adds the
 #       ss_debug_set / ss_debug_ptr knobs, the per-workgroup s_memtime stamps of tools/diag_*.py and the comparison kernels
 #       that tests and tools/ab_*.py measure the product against; concluded experiments are not kept in it: LAB_NOTES.md,
@@ -31,7 +32,7 @@ echo "built $OUT"
 if [ "$1" != "tuning" ]; then
     # every later feature is a library of its own (NAME.hip, include/stabstitch_NAME.h), so that the surface and the machine code of
     # libstabstitch_hip.so stay as they are
-    for NAME in blend seam mbwarp surfaces smoothtail cover; do
+    for NAME in blend seam mbwarp surfaces smoothtail cover resample; do
         SIDE="$HERE/../libstabstitch_$NAME.so"
         "$HIPCC" $FLAGS "$HERE/$NAME.hip" -o "$SIDE"
         echo "built $SIDE"

@@ -828,6 +828,39 @@ class _Stitcher:
             return None
         return tuple(int(v) for v in ops.covered_rect(self._cover, even).cpu().tolist())
 
+    def covered_rect_device(self, even=False):
+        """covered_rect() left on the device: int32 [4] = (y0, x0, h, w) of the state at this moment, a new tensor per call -- the
+        search's three launches on the push's stream, no synchronisation, nothing read back; None before the canvas is fixed.
+        What ops.resample and to_size take as rect=."""
+        if not self.track_coverage:
+            raise ValueError('covered_rect_device needs a stitcher built with track_coverage=True')
+        if self._cover is None:
+            return None
+        return ops.covered_rect(self._cover, even)
+
+    def to_size(self, frames, size, aspect='fill', rect=None, out=None, out_format='bgr'):
+        """What a push* just returned -- fp32 [3,hc,wc] | [k,3,hc,wc], or uint8 [hc,wc,3] | [k,hc,wc,3] -- resampled to exactly
+        size = (Hout, Wout) on the covered rectangle: ops.resample (aspect, out, out_format: its own), one launch, nothing read back.
+        rect=None uses covered_rect_device() of this moment: every frame is free of border, and the picture zooms in a little whenever
+        the rectangle shrinks.  rect= a tensor the caller holds (an earlier covered_rect_device(), say after a warm-up) gives a
+        steady zoom, at the price of border wherever a later frame covers less.  Which one is the caller's choice; the push, its
+        graph and its frames are the same either way."""
+        if not self.track_coverage:
+            raise ValueError('to_size needs a stitcher built with track_coverage=True')
+        ops._resample_size('to_size', size, aspect)
+        if self._cover is None:
+            raise ValueError('to_size: no canvas is fixed yet, so no frame has been handed out')
+        want = (self.hc, self.wc)
+        if not torch.is_tensor(frames) or frames.dim() not in (3, 4) or \
+                (tuple(frames.shape[-3:-1]) if frames.dtype == torch.uint8 else tuple(frames.shape[-2:])) != want:
+            raise ValueError('to_size takes frames of the current %d x %d canvas, as a push returns them, got %s'
+                             % (want + ((frames.dtype, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames).__name__,)))
+        if rect is None:
+            rect = self.covered_rect_device()
+        elif not torch.is_tensor(rect):
+            raise ValueError('to_size: rect is None or an int32 [4] device tensor (covered_rect_device), got %r' % (rect,))
+        return ops.resample(frames, size, rect=rect, aspect=aspect, out=out, out_format=out_format)
+
     # ------------------------------------------------------------------ steady state
     def _versions(self):
         return tuple(n.weights_version for n in self.nets)

@@ -10,7 +10,7 @@ import ctypes
 import torch
 
 from . import _hip as H
-from . import _blend as B, _cover as CV, _mbwarp as W, _seam as S, _smoothtail as ST, _surfaces as F
+from . import _blend as B, _cover as CV, _mbwarp as W, _resample as RS, _seam as S, _smoothtail as ST, _surfaces as F
 
 
 def _f(t):
@@ -1977,3 +1977,110 @@ def covered_rect(bitmap_or_state, even=False, wc=None, ws=None):
     CV.call('ssc_covered_rect', H.dptr(bitmap, dtype=torch.int64), hc, wc, int(bool(even)), H.dptr(ws, dtype=torch.uint8), ws.numel(),
             H.dptr(rect, dtype=torch.int32), H.stream())
     return rect
+
+
+# ------------------------------------------------------------------ fixed-size output of a rectangle (libstabstitch_resample.so)
+def _resample_size(what, size, aspect):
+    if not isinstance(size, (tuple, list)) or len(size) != 2 or any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in size):
+        raise ValueError('%s: size must be (Hout, Wout) as two ints >= 1, got %r' % (what, size))
+    if not isinstance(aspect, str) or aspect not in RS.ASPECTS:
+        raise ValueError("%s: aspect must be 'fill' or 'stretch', got %r" % (what, aspect))
+    return int(size[0]), int(size[1]), RS.ASPECTS[aspect]
+
+
+def _resample_rect(what, rect, hc, wc, dev):
+    """rect of resample / to_size -> (rect_dev pointer | None, y0, x0, h, w)."""
+    if rect is None:
+        return None, 0, 0, hc, wc
+    if torch.is_tensor(rect):
+        if rect.dtype != torch.int32 or tuple(rect.shape) != (4,) or not rect.is_contiguous():
+            raise ValueError('%s: a rect tensor is int32 [4] = (y0, x0, h, w), as covered_rect returns it, got %s %s'
+                             % (what, rect.dtype, tuple(rect.shape)))
+        if rect.device != dev:
+            raise ValueError('%s: the rect tensor lives on %s, the frames on %s' % (what, rect.device, dev))
+        return rect, 0, 0, 0, 0
+    if not isinstance(rect, (tuple, list)) or len(rect) != 4 or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in rect):
+        raise ValueError('%s: rect must be None, (y0, x0, h, w) as non-negative ints or an int32 [4] device tensor, got %r' % (what, rect))
+    return (None,) + tuple(int(v) for v in rect)
+
+
+def resample_window(rect, frame_hw, size, aspect='fill'):
+    """(fy, fx, fh, fw): the window of rect = (y0, x0, h, w) on a frame of frame_hw = (Hc, Wc) that `resample` reads for an output of
+    `size` -- ssr_source_window, the function the kernel runs; zeros when the rectangle misses the frame."""
+    hout, wout, asp = _resample_size('resample_window', size, aspect)
+    hc, wc, _ = _resample_size('resample_window', frame_hw, aspect)
+    if torch.is_tensor(rect):
+        raise ValueError('resample_window takes the rectangle as four ints: a device rectangle stays on the device')
+    _, y0, x0, h, w = _resample_rect('resample_window', rect, hc, wc, None)
+    out = (ctypes.c_double * 4)()
+    H.check_side(RS.lib().ssr_source_window((ctypes.c_int * 4)(y0, x0, h, w), hc, wc, hout, wout, asp, out), 'ssr_source_window')
+    return tuple(float(v) for v in out)
+
+
+def resample(frames, size, rect=None, aspect='fill', out=None, out_format='bgr'):
+    """The rectangle `rect` of every frame, resampled with the triangle prefilter (PIL's; interpolate(mode='bilinear',
+    antialias=True)) to exactly size = (Hout, Wout), ONE launch whatever n:
+    fp32 [n,3,H,W] -> fp32 [n,3,Hout,Wout], unrounded; uint8 [n,H,W,3] -> uint8 [n,Hout,Wout,3] (floor(v + 0.5)), or with
+    out_format='nv12' -> NV12 [n,Hout*3/2,Wout], byte for byte bgr_to_nv12 of those bytes (Hout, Wout even).  A single frame
+    ([3,H,W] / [H,W,3]) gives a single frame.
+    rect: None (the whole frame), (y0, x0, h, w) as non-negative ints, or the int32 [4] device tensor covered_rect returns -- that
+    one is read inside the kernel: nothing synchronises, nothing is read back.  The rectangle is clipped to the frame; where
+    nothing is left the output is black.  aspect: 'fill' resamples the centred part of the rectangle with the output's aspect,
+    'stretch' all of it.  No pixel outside the rectangle contributes.
+    out: a tensor to write -- NV12 with its row stride as the pitch (as bgr_to_nv12 takes it), BGR frames with a free frame stride
+    (as nv12_to_bgr takes them), fp32 dense."""
+    what = 'resample'
+    if not torch.is_tensor(frames) or frames.dtype not in (torch.float32, torch.uint8) or frames.dim() not in (3, 4):
+        raise ValueError('resample takes fp32 [n,3,H,W] or uint8 [n,H,W,3] frames (or one frame), got %s'
+                         % ((frames.dtype, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames).__name__,))
+    u8 = frames.dtype == torch.uint8
+    single = frames.dim() == 3
+    if single:
+        frames = frames[None]
+    if frames.shape[3 if u8 else 1] != 3 or 0 in frames.shape:
+        raise ValueError('resample takes fp32 [n,3,H,W] or uint8 [n,H,W,3] frames, got %s %s' % (frames.dtype, tuple(frames.shape)))
+    n = int(frames.shape[0])
+    hc, wc = (int(frames.shape[1]), int(frames.shape[2])) if u8 else (int(frames.shape[2]), int(frames.shape[3]))
+    hout, wout, asp = _resample_size(what, size, aspect)
+    if out_format not in ('bgr', 'nv12'):
+        raise ValueError("resample: out_format must be 'bgr' or 'nv12', got %r" % (out_format,))
+    nv12 = out_format == 'nv12'
+    if nv12 and (not u8 or hout % 2 or wout % 2):
+        raise ValueError("resample: out_format='nv12' takes uint8 frames and an even size, got %s and %d x %d" % (frames.dtype, hout, wout))
+    if n > RS.MAX_FRAMES or hc * wc >= 2 ** 31 or hout * wout >= 2 ** 31 or (hout + 15) // 16 > 65535 or (wout + 63) // 64 > 65535:
+        raise ValueError('resample: at most %d frames of fewer than 2^31 pixels, in and out, per call' % RS.MAX_FRAMES)
+    dev = frames.device
+    rdev, y0, x0, h, w = _resample_rect(what, rect, hc, wc, dev)
+    shape = (n, hout // 2 * 3, wout) if nv12 else (n, hout, wout, 3) if u8 else (n, 3, hout, wout)
+    if out is not None:
+        if torch.is_tensor(out) and single and out.dim() == len(shape) - 1:
+            out = out[None]
+        ok = torch.is_tensor(out) and out.dtype == frames.dtype and tuple(out.shape) == shape and out.device == dev
+        if ok and nv12:
+            ok = out.stride(2) == 1 and out.stride(1) >= wout and out.stride(1) % 2 == 0 and out.stride(0) % 2 == 0 \
+                and (n == 1 or out.stride(0) >= out.stride(1) * shape[1])
+        elif ok and u8:
+            ok = out[0].is_contiguous() and (n == 1 or out.stride(0) >= 3 * hout * wout)
+        elif ok:
+            ok = out.is_contiguous()
+        if not ok:
+            raise ValueError('resample: out must be %s %s on %s (NV12: dense columns, an even row stride >= Wout; BGR: dense frames, a '
+                             'frame stride >= a frame; fp32: dense), got %s'
+                             % (frames.dtype, list(shape), dev, (out.dtype, tuple(out.shape), tuple(out.stride()), out.device)
+                                if torch.is_tensor(out) else type(out).__name__))
+    if not frames.is_cuda:
+        raise ValueError('resample needs device tensors (got %s); there is no CPU path' % dev)
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=frames.dtype)
+    if not frames.is_contiguous():
+        frames = frames.contiguous()
+    tail = (n, hc, wc, hout, wout, asp, H.dptr(rdev, allow_none=True, dtype=torch.int32), y0, x0, h, w, H.stream())
+    if nv12:
+        pitch = out.stride(1)
+        fs = out.stride(0) if n > 1 else pitch * shape[1]
+        RS.call('ssr_resample_u8_nv12', _u8ptr(frames), _nv12_ptr(out), _nv12_ptr(out, hout * pitch), pitch, fs, *tail)
+    elif u8:
+        RS.call('ssr_resample_u8', _u8ptr(frames), _nv12_ptr(out), out.stride(0) if n > 1 else 3 * hout * wout, *tail)
+    else:
+        RS.call('ssr_resample_f32', H.dptr(frames), H.dptr(out), *tail)
+    return out[0] if single else out

@@ -547,17 +547,28 @@ class Crop:
     even: round the rectangle's height and width down to even (video encoders); min_mask in (0, 1]: a view covers a pixel where its
     warped ones-mask reaches it (0.5: MULTIBAND's validity rule).  After a call it carries `.rect = (y0, x0, h, w)` on the uncropped
     canvas `.canvas = (Hc, Wc)`.  A Crop whose `.rect` is set is applied as given, without a coverage pass: hand the first call's Crop
-    to the later calls of a video rendered in several (on one bbox=), or set `.rect` from `covered_rect` on a box fixed in advance."""
+    to the later calls of a video rendered in several (on one bbox=), or set `.rect` from `covered_rect` on a box fixed in advance.
+    size=(Hout, Wout): what comes back is not the view but the rectangle resampled to exactly that size (ops.resample: the triangle
+    prefilter, one launch more), `aspect` 'fill' (the centred part of the rectangle with the output's aspect) or
+    'stretch'; the routes then return size as their h, w.  `.rect` and `.canvas` mean what they do without it."""
 
-    def __init__(self, even=False, min_mask=ops.MIN_MASK):
+    def __init__(self, even=False, min_mask=ops.MIN_MASK, size=None, aspect='fill'):
         if isinstance(min_mask, bool) or not isinstance(min_mask, (int, float)) or not 0.0 < float(min_mask) <= 1.0:
             raise ValueError('Crop: min_mask must lie in (0, 1], got %r' % (min_mask,))
         self.even, self.min_mask = bool(even), float(min_mask)
+        self.size, self.aspect = _crop_size(size, aspect)
         self.rect = None
         self.canvas = None
 
     def __repr__(self):
-        return 'Crop(even=%r, min_mask=%r, rect=%r, canvas=%r)' % (self.even, self.min_mask, self.rect, self.canvas)
+        return 'Crop(even=%r, min_mask=%r, size=%r, aspect=%r, rect=%r, canvas=%r)' % (self.even, self.min_mask, self.size, self.aspect,
+                                                                                       self.rect, self.canvas)
+
+
+def _crop_size(size, aspect):
+    """Crop's size= and aspect= -> (None | (Hout, Wout), aspect); ValueError for anything ops.resample would refuse."""
+    h, w, _ = ops._resample_size('Crop', (1, 1) if size is None else size, aspect)
+    return (None if size is None else (h, w)), aspect
 
 
 def check_crop(crop):
@@ -570,6 +581,7 @@ def check_crop(crop):
         r = crop.rect
         if not isinstance(r, (tuple, list)) or len(r) != 4 or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in r):
             raise ValueError('Crop.rect must be (y0, x0, h, w) as non-negative ints, got %r' % (r,))
+    _crop_size(crop.size, crop.aspect)       # (the fields are plain attributes: a Crop changed after it was built)
     return crop
 
 
@@ -594,7 +606,10 @@ def _settle_crop(crop, src, T, img_h, img_w, hc, wc, warp_mode):
 
 
 def _cropped(crop, out, u8=False):
-    """-> (the window crop.rect of the frames `out` ([n,3,Hc,Wc], or uint8 [n,Hc,Wc,3]), its h, its w): a view."""
+    """-> (the window crop.rect of the frames `out` ([n,3,Hc,Wc], or uint8 [n,Hc,Wc,3]), its h, its w): a view; with crop.size the
+    window resampled to that size (one launch), and the size."""
+    if crop.size is not None:
+        return ops.resample(out, crop.size, rect=tuple(crop.rect), aspect=crop.aspect), crop.size[0], crop.size[1]
     y0, x0, h, w = crop.rect
     return (out[:, y0:y0 + h, x0:x0 + w, :] if u8 else out[:, :, y0:y0 + h, x0:x0 + w]), h, w
 
@@ -690,7 +705,8 @@ def render_frames(img_lists, meshes, warp_mode='NORMAL', fusion_mode='AVERAGE', 
     MULTIBAND in the warp, in front of the seam and the blend.  exposure_state: an ops.exposure_state to continue from and leave
     advanced (a video rendered in several calls); without it every call starts fresh.
     crop (None | Crop): the frames render as ever; what comes back is their window [:, :, y0:y0+h, x0:x0+w] (a view) on the largest
-    rectangle every frame of the call covers, with that h, w as Hc, Wc; the Crop carries the rectangle and the uncropped size."""
+    rectangle every frame of the call covers, with that h, w as Hc, Wc; the Crop carries the rectangle and the uncropped size.
+    Crop(size=(Hout, Wout)): that window resampled to exactly that size instead (ops.resample, one launch more), Hout, Wout as Hc, Wc."""
     check_crop(crop)
     check_fusion(fusion_mode, bands)
     seam = seam_options(fusion_mode, seam, seam_cell, seam_mu, seam_prior)
